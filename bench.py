@@ -3,7 +3,7 @@
 MI355X, each workload with the roofline that bounds its kernel and the NumPy CPU baseline timed beside it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--head c3|c2|c4|c5] [--workload c2|c3|c4|c5|c1|all]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR]
 
 The ONE JSON line rank 0 prints has the workload BASELINE.json's numeric target is stated on (C3, ProductOfT
 512 x 100 000: ">= 50x the NumPy reference at 1 GPU"; in the reference's arithmetic: c3f64) as its top-level workload
@@ -13,11 +13,13 @@ or bytes the chain NEEDS / time / peak -- one meaning for every workload), cK_fr
 cK_one_iter_ms/_frac/_call_ms (one sampling_iteration per call: launches by HIP events; the whole call by the wall clock), cK_shard{2,4,8}_{ms,frac,eff}, cK_sample<n>_incl_download,
 cK_autocor_on_device; the complete records go to --detail.
 
-A "step" is one MarkovJumpHMC.sampling_iteration over all particles; --steps K is the batch one
-mjhmc_iterate call runs back to back with a single host sync.  The timed region is R such calls (R chosen so that it
-lasts >= 0.5 s: a 3 ms region measures the clock ramp, not the kernel), every call bracketed by barrier + stream sync
-on both sides, MAX over ranks; value = all ranks' particle-steps / the summed time, median and spread over the R
-calls reported next to it.  Inputs are resident in HBM before the timed region starts.
+A "step" is one MarkovJumpHMC.sampling_iteration over all particles; --steps K is the number of timed
+steps: ONE mjhmc_iterate call of K iterations back to back with a single host sync, bracketed by barrier + stream sync
+on both sides, MAX over ranks; value = all ranks' particle-steps / its time, ms_per_step = its time / K.  Before it:
+calls of K for ~0.2 s to bring the clocks up (from a snapshot of the initial state, put back afterwards), then the W
+= --warmup iterations, so the timed call's inputs are the same in every run with the same arguments.  Inputs are
+resident in HBM before the timed region starts.  --dump-outputs DIR writes what the head workload's timed call
+computed in its last step as DIR/<workload>_<name>.npy (bench.py:dump_outputs).
 
 N > 1: one rank per GPU.  Either  python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...  (the ranks
 find RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment and pass the RCCL id through the launcher's store)
@@ -45,7 +47,6 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 L2_PEAK_GBS = 34500.0      # aggregate L2 bandwidth measured in the same guide (memory hierarchy, L2)
-MIN_TIMED_S = 0.5
 
 WORKLOADS = {
     # BASELINE.json configs[1]
@@ -375,9 +376,28 @@ class Rig(object):
         return [float(v) for v in self.comm.allreduce_f64(np.asarray(list(values), dtype=np.float64), 'max')]
 
 
-def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=1):
+def dump_outputs(smp, key, last, out_dir):
+    """--dump-outputs: what the timed call handed its caller after its last step -- the state (X, V: a fixed, seeded
+    sample of particle columns, the same for every run of a workload; EX, EV, dwelling times, transitions of those
+    columns) and the last step's IterStats -- as float64 <key>_<name>.npy, under 64 MB in all."""
+    from mjhmc_amd import _lib
+    D, N = smp.ndims, smp.nparticles
+    n = int(min(N, (48 << 20) // (8 * (2 * D + 5))))
+    cols = np.sort(np.random.RandomState(0).choice(N, n, replace=False))
+    out = {'columns': cols.astype(np.float64),
+           'X': smp.read(_lib.F_X)[:, cols], 'V': smp.read(_lib.F_V)[:, cols],
+           'EX': smp.read(_lib.F_EX)[cols], 'EV': smp.read(_lib.F_EV)[cols],
+           'dwell': smp.read(_lib.F_DWELL)[cols], 'transitions': smp.read(_lib.F_TRANS)[cols].astype(np.float64),
+           'stats': np.array([getattr(last, f) for f, _ in last._fields_], dtype=np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, '%s_%s.npy' % (key, name)), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=1, dump_dir=None):
     """shard_of = G > 1: the workload at N/G particles on this one GPU -- what each rank of a G-GPU strong-scaled run
-    executes (no timed region holds a collective, so t(G GPUs, N) = t(1 GPU, N/G)); same kernels, same flags."""
+    executes (no timed region holds a collective, so t(G GPUs, N) = t(1 GPU, N/G)); same kernels, same flags.
+    dump_dir: write the timed call's outputs there (dump_outputs)."""
     from mjhmc_amd import engine, _lib
     rank, world = rig.rank, rig.world
     w = dict(WORKLOADS[key])
@@ -400,19 +420,23 @@ def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=
     p_r = -np.log(1 - w['beta']) * 0.5
     smp.set_hparams(w['eps'], w['L'], p_r, 1.0)
 
-    # warm-up: the requested W iterations, then calls of K until the chip has been busy for ~0.2 s (sustained clocks)
+    # clock ramp: calls of K until the chip has been busy for ~0.2 s (sustained clocks), from a snapshot of the initial
+    # state that is put back afterwards -- however many calls the ramp took, the timed call starts from the state after
+    # exactly the W warm-up iterations (same inputs in every run with the same arguments: --dump-outputs compares them)
+    smp.checkpoint()
+    smp.sync()
+    t0 = time.perf_counter()
+    n_ramp = 0
+    while time.perf_counter() - t0 < 0.2 or n_ramp < 2:
+        smp.iterate(steps)
+        smp.sync()
+        n_ramp += 1
+    smp.restore()
+    # warm-up: the requested W iterations (they also rebuild the caches a call hands to the next)
     if warmup > 0:
         smp.iterate(warmup)
     smp.sync()
-    t0 = time.perf_counter()
-    calib = []
-    while time.perf_counter() - t0 < 0.2 or len(calib) < 2:
-        tc = time.perf_counter()
-        smp.iterate(steps)
-        smp.sync()
-        calib.append(time.perf_counter() - tc)
-    per_call = rig.max_over_ranks([min(calib)])[0]
-    reps = int(min(max(1, np.ceil(MIN_TIMED_S / per_call)), 4096))
+    reps = 1                                        # the timed region: ONE call of exactly K = --steps iterations
 
     call_s, kern_ms, launches = [], 0.0, 0
     agg = np.zeros(7)                               # l moves, cold caches, E evaluations, dEdX evaluations, f moves, r moves, inverse-L trajectories run
@@ -433,6 +457,8 @@ def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=
                 sum(s.dEdX_evals for s in stats), sum(s.f for s in stats), sum(s.r for s in stats),
                 sum(s.n_flf_run for s in stats)]
     device = rig.monitor.stop()
+    if dump_dir and rank == 0:
+        dump_outputs(smp, key, stats[-1], dump_dir)
     call_s = rig.max_over_ranks(call_s)
     elapsed = float(np.sum(call_s))
     iters = steps * reps
@@ -996,6 +1022,9 @@ def main(argv=None):
                          '1/2/4/8"), 8 for the others; "1" = none.  Ignored at --gpus > 1')
     ap.add_argument('--detail', default=os.path.join(ROOT, 'gpurun_out', 'bench_detail.json'),
                     help='file that receives the complete per-workload records (the printed line carries numbers only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the head workload computed in its last step (float64 .npy, '
+                         'a fixed sample of particle columns, < 64 MB) into DIR')
     ap.add_argument('--spawn-check', action='store_true',
                     help='ranks report their environment and the rendezvous channel, then exit before touching a GPU')
     args = ap.parse_args(argv)
@@ -1039,7 +1068,8 @@ def main(argv=None):
     for key in [k for k in ('c1', 'c2', 'c4', 'c3', 'c3f64', 'c5', 'c5bf16') if k in keys]:
         steps, warm = budget(key)
         cpu_s = 0 if (args.no_cpu_baseline or cpu_key.get(key, key) != key) else (12.0 if key == head else 6.0)
-        results[key] = run_workload(rig, key, steps, warm, cpu_s, args.scaling)
+        results[key] = run_workload(rig, key, steps, warm, cpu_s, args.scaling,
+                                    dump_dir=args.dump_outputs if key == head else None)
         progress('workload_done ' + key)
         if results[key] is not None:
             results[key]['steps'] = steps

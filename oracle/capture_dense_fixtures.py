@@ -5,12 +5,14 @@ come from the torch restatement of the reference's forward graphs with AUTOGRAD 
 (oracle/autograd_energies.py) -- independent of the hand-derived gradients in oracle/mjhmc_oracle.py.
 
 Also converts the particle states the reference ships (initializations/*.pickle, burn-in end points of its own
-samplers) into .npz inputs.  Needs /root/reference for those; the GPU box never sees the reference.
+samplers) into .npz inputs, and keeps the three files themselves, gzipped, for the loader test.  Needs the reference
+checkout (--ref) for those; the GPU box never sees the reference.
 
     python oracle/capture_dense_fixtures.py [--ref /root/reference]
-      -> tests/golden/g2_dense.npz, tests/golden/ref_init_states.npz
+      -> tests/golden/g2_dense.npz, tests/golden/ref_init_states.npz, tests/golden/ref_init_<name>.pickle.gz
 """
 import argparse
+import gzip
 import hashlib
 import os
 import pickle
@@ -100,6 +102,12 @@ def main():
         init.update({name + '_X': Xs, name + '_E': E, name + '_g': g})
     np.savez_compressed(os.path.join(OUT, 'ref_init_states.npz'), **init)
     print('ref_init_states.npz:', {k: v.shape for k, v in init.items()})
+    # the files byte for byte (tests/test_oracle_autograd.py::test_reference_written_initialisation_files_load)
+    for name in ('ProductOfT_6123388416598428958', 'SparseImageCode_-2828851975638192263', 'Funnel_3713081631925750456'):
+        with open(os.path.join(args.ref, 'initializations', name + '.pickle'), 'rb') as f:
+            raw = f.read()
+        with open(os.path.join(OUT, 'ref_init_%s.pickle.gz' % name), 'wb') as f:
+            f.write(gzip.compress(raw, 9, mtime=0))
 
 
 if __name__ == '__main__':
