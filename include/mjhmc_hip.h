@@ -71,8 +71,9 @@ typedef enum {
   MJHMC_E_PRODUCT_OF_T = 6,
   MJHMC_E_SPARSE_CODE = 7,
   MJHMC_E_USER_EXPR = 8,     /* created by mjhmc_energy_create_expr only */
-  MJHMC_E_HOST = 9           /* no parameters: E and dE/dX are evaluated by the CALLER (opaque Python callables of
+  MJHMC_E_HOST = 9,          /* no parameters: E and dE/dX are evaluated by the CALLER (opaque Python callables of
                                 LambdaDistribution, README.md:27-36); samplers of it are driven by mjhmc_traj_* below */
+  MJHMC_E_LINEAR_EXPR = 10   /* created by mjhmc_energy_create_linear only */
 } mjhmc_energy_kind;
 
 /* arithmetic type of state and force.  BF16: bfloat16 state in HBM and as MFMA operands, float32
@@ -160,6 +161,26 @@ int mjhmc_energy_create_expr_coupled(mjhmc_ctx* ctx, int ndims, const char* stat
                                      const char* include_dir, mjhmc_energy** out);
 int mjhmc_expr_check_coupled(int ndims, const char* stat_exprs, const char* energy_expr, const char* energy0_expr,
                              const char* grad_expr, const char* include_dir);
+/* Linear-model energies on the ProductOfT matrix-core tile kernels (MJHMC_E_LINEAR_EXPR):
+ *     E(x) = sum_{j<K} f(u_j, j),   u = W x + b,   dE/dx = W^T f'(u)
+ * W: nexperts x ndims row-major, b: nexperts (float64 on input, stored float32 as PRODUCT_OF_T stores its parameters);
+ * energy_expr = f and grad_expr = f', C expressions evaluated in float32 of
+ *     u (float, the expert's input), j (int, the expert), p[k] (the nparams shared parameters, as float),
+ *     q[m] (per-expert parameter row m < n_expert_rows <= 4 at expert j; expert_params: n_expert_rows x nexperts row-major).
+ * Write float literals and functions (0.5f, logf) to stay in float32.  1 <= ndims, nexperts <= 512 (both padded to 128,
+ * 256 or 512); wider models return MJHMC_ERR_UNSUPPORTED.  Padded experts contribute nothing (their f and f' are masked).
+ * Examples: correlated Gaussian  f "0.5f*u*u", f' "u" with W the transposed Cholesky factor of the precision;
+ * softplus  "u > 20.f ? u : log1pf(expf(u))", "1.f/(1.f + expf(-u))"; ProductOfT  "q[0]*logf(1.f + u*u)",
+ * "2.f*q[0]*u/(1.f + u*u)" with W / nu, b / nu and q[0] = (nu + 1) / 2.
+ * dtype F64 = float64 state around the float32 force (the reference's ProductOfT arithmetic), F32 = float32 state: every
+ * path of PRODUCT_OF_T.  The kernels (14 for the model's padded size) are compiled with hipRTC at creation (include_dir as
+ * for mjhmc_energy_create_expr) and cached per process by their source.  Compile errors: MJHMC_ERR_INVALID with the log. */
+int mjhmc_energy_create_linear(mjhmc_ctx* ctx, int ndims, int nexperts, const double* W, const double* b,
+                               const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                               const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out);
+/* compile-only check of a linear-model energy's expressions (needs no device): 0, MJHMC_ERR_INVALID with the compiler's
+ * log, MJHMC_ERR_UNSUPPORTED beyond 512 */
+int mjhmc_linear_check(int ndims, int nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
 int mjhmc_energy_destroy(mjhmc_energy* e);
 
 /* One evaluation of E_val / dEdX_val (mjhmc/misc/distributions.py:66-81) on n columns.

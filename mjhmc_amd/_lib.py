@@ -14,7 +14,8 @@ KERNEL_HEADERS = os.path.join(_HERE, 'csrc')     # elementwise.hpp / philox.hpp:
 LIB_PATH = os.environ.get('MJHMC_HIP_LIB') or os.path.join(_HERE, 'lib', 'libmjhmc_hip.so')
 
 # enums of include/mjhmc_hip.h
-E_ISO_GAUSS, E_DIAG_GAUSS, E_ROUGH_WELL, E_MM_GAUSS, E_FUNNEL_NEAL, E_FUNNEL_REF, E_PRODUCT_OF_T, E_SPARSE_CODE, E_USER_EXPR, E_HOST = range(10)
+E_ISO_GAUSS, E_DIAG_GAUSS, E_ROUGH_WELL, E_MM_GAUSS, E_FUNNEL_NEAL, E_FUNNEL_REF, E_PRODUCT_OF_T, E_SPARSE_CODE, E_USER_EXPR, E_HOST, \
+    E_LINEAR_EXPR = range(11)
 F64, F32, BF16 = 0, 1, 2
 MODE_MJHMC, MODE_CONTROL, MODE_CTHMC = 0, 1, 2
 F_X, F_V, F_EX, F_EV, F_DEDX, F_HFLF, F_CACHE, F_DWELL, F_TRANS = range(9)
@@ -53,6 +54,9 @@ PROTOTYPES = {
     'mjhmc_energy_create_expr_coupled': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                                         ctypes.c_char_p, _P, ctypes.c_size_t, ctypes.c_char_p,
                                                         ctypes.POINTER(_P)]),
+    'mjhmc_energy_create_linear': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_char_p, ctypes.c_char_p, _P,
+                                                  ctypes.c_size_t, _P, ctypes.c_int, ctypes.c_char_p, _P]),
+    'mjhmc_linear_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_expr_check_coupled': (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                                 ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_energy_destroy': (ctypes.c_int, [_P]),

@@ -149,7 +149,7 @@ int pick_shape(int D, int dtype, Shape* out) {
 // the dtype the state is STORED in (float64 where float32 was asked for rows only the multi-pass path handles: sh->round32)
 static int shape_for(const mjhmc_energy* e, int* dtype, Shape* sh) {
   if (e->is_pot()) {
-    if (*dtype != MJHMC_F64 && *dtype != MJHMC_F32) return fail(MJHMC_ERR_UNSUPPORTED, "PRODUCT_OF_T runs with float32 or float64 state");
+    if (*dtype != MJHMC_F64 && *dtype != MJHMC_F32) return fail(MJHMC_ERR_UNSUPPORTED, "PRODUCT_OF_T and LINEAR_EXPR run with float32 or float64 state");
     if (*dtype == MJHMC_F64 || e->pot_big()) {
       // the reference's own arithmetic: float64 HMCState arrays around the float32 force (distributions.py:408-415,
       // hmc_state.py:29-38); ndims > 512: the blocked force evaluation exists on the multi-pass path only
@@ -784,7 +784,7 @@ static int run_eval_pot(mjhmc_sampler* s, const void* X, void* Gout, void* Eout,
   a.first_pid = s->first_pid;
   a.D = s->D;
   a.key = RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), 0u, 0u};
-  pot_launch_eval(a, s->en->pot_model(), s->stream);
+  pot_launch_eval(a, s->en->pot_model(), s->stream, s->en->pot_gen());
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1084,9 +1084,46 @@ int mjhmc_expr_check(int ndims, const char* energy_expr, const char* grad_expr, 
   return mjhmc_expr_check_coupled(ndims, nullptr, energy_expr, nullptr, grad_expr, include_dir);
 }
 
+int mjhmc_energy_create_linear(mjhmc_ctx* ctx, int ndims, int nexperts, const double* W, const double* b,
+                               const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                               const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out) {
+  if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  TRY(linear_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
+  if (nparams && !params) return fail(MJHMC_ERR_INVALID, "params is NULL");
+  if (n_expert_rows < 0 || n_expert_rows > 4 || (n_expert_rows && !expert_params))
+    return fail(MJHMC_ERR_INVALID, "LINEAR_EXPR takes 0 to 4 per-expert parameter rows");
+  HIPCHK(hipSetDevice(ctx->device));
+  mjhmc_energy* e = new mjhmc_energy();
+  e->ctx = ctx;
+  std::memset(&e->ep, 0, sizeof(e->ep));
+  e->ep.kind = MJHMC_E_LINEAR_EXPR;
+  e->ep.ndims = ndims;
+  const int rc = linear_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params, n_expert_rows,
+                                     include_dir);
+  if (rc) {
+    std::string keep = g_err;
+    mjhmc_energy_destroy(e);
+    g_err = keep;
+    return rc;
+  }
+  *out = e;
+  return 0;
+}
+
+int mjhmc_linear_check(int ndims, int nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
+  TRY(linear_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  std::string err;
+  const std::vector<char>* code = nullptr;
+  const std::vector<std::string>* lowered = nullptr;
+  const int rc = linear_compile(energy_expr, grad_expr, linear_dim(ndims, nexperts), include_dir, &err, &code, &lowered);
+  return rc ? fail(rc, err) : 0;
+}
+
 int mjhmc_energy_destroy(mjhmc_energy* e) {
   if (!e) return 0;
   user_energy_free(e);
+  linear_energy_free(e);
   if (e->dev64) (void)hipFree(e->dev64);
   if (e->dev32) (void)hipFree(e->dev32);
   for (float* q : e->pot)
@@ -1916,7 +1953,7 @@ static int iterate_t(mjhmc_sampler* s, int n_iter, const double* replay_normal, 
           PotJumpArgs h = part_args<PotJumpArgs, float>(pa, n_parts > 1 ? part_start(k) : 0, n_parts > 1 ? part_count(k) : s->N,
                                                         n_parts > 1 ? part_npad(k) : s->Npad, (size_t)s->sh.pitch, k, i, dense_counters);
           h.ntiles = h.Npad / 32;
-          pot_launch_jump(h, s->en->pot_model(), part_stream(k));
+          pot_launch_jump(h, s->en->pot_model(), part_stream(k), s->en->pot_gen());
         }
       } else {
         // the reference's arithmetic: float64 state rows streamed through the tile kernel's epilogue (dense_pot64.hip)
@@ -1967,7 +2004,7 @@ static int iterate_t(mjhmc_sampler* s, int n_iter, const double* replay_normal, 
           Pot64JumpArgs h = part_args<Pot64JumpArgs, double>(pa, n_parts > 1 ? part_start(k) : 0, n_parts > 1 ? part_count(k) : s->N,
                                                              n_parts > 1 ? part_npad(k) : s->Npad, (size_t)s->sh.pitch, k, i, dense_counters);
           h.ntiles = h.Npad / 32;
-          pot64_launch_jump(h, s->en->pot_model(), part_stream(k));
+          pot64_launch_jump(h, s->en->pot_model(), part_stream(k), s->en->pot_gen());
         }
       }
     } else if (s->en->is_sic()) {
@@ -2755,7 +2792,7 @@ int mjhmc_leapfrog(mjhmc_energy* e, int dtype, const double* X, const double* V,
       a.L = n_steps;
       a.eps = (float)eps;
       a.chalf = (float)(-eps / 2.);
-      pot_launch_leap(a, e->pot_model(), w.stream);
+      pot_launch_leap(a, e->pot_model(), w.stream, e->pot_gen());
       HIPCHK(hipGetLastError());
     } else if (e->is_sic()) {
       auto leap_sic = [&](auto tag) {

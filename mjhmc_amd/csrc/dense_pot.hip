@@ -28,41 +28,19 @@
 #include <cstdlib>
 
 #include "dense_pot.hpp"
+#include "dense_pot_kernels.hpp"
 #include "dense_pot_tile.hpp"
 
 namespace mjhmc {
 
 // ---------------------------------------------------------------------------------------------------
-// evaluation: E(X), dEdX(X), optional kinetic energy / generated momentum (HMCState.__init__)
+// evaluation: E(X), dEdX(X), optional kinetic energy / generated momentum (HMCState.__init__).  The bodies of this
+// file's tile kernels are the fragments dense_pot_*.inc, written against the experts `xp` of the force; here ProductOfT's.
 // ---------------------------------------------------------------------------------------------------
 template <int NB>
 __global__ __launch_bounds__(256, 1) void pot_eval_kernel(const PotEvalArgs a, const PotModel mdl) {
-  __shared__ Shared<NB> sh;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-  AReg<NB> ar;
-  areg_load<NB>(mdl, w, c, h, ar);
-  stage_bias<NB>(mdl, sh);
-  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-    const int64_t p = tile * kP + c;
-    Tile<NB> x, g;
-    tile_load<NB>(a.X, p, w, h, x);
-    float ex = 0.f;
-    pot_gradient<NB>(mdl, ar, sh, w, c, h, lane, x, g, true, &ex);
-    if (a.G) tile_store<NB>(a.G, p, w, h, g);
-    if (a.E && w == 0 && h == 0) a.E[p] = ex;
-    if (a.EV) {
-      Tile<NB> v;
-      if (a.V_gen) {
-        pot_normals<NB>(a.key, (uint32_t)(a.first_pid + (p < a.N ? p : 0)), w, h, a.D, v);
-        tile_store<NB>(a.V_gen, p, w, h, v);
-      } else {
-        tile_load<NB>(a.V, p, w, h, v);
-      }
-      const float ev = pot_kinetic<NB>(sh, w, c, h, v);
-      if (w == 0 && h == 0) a.EV[p] = ev;
-    }
-    __syncthreads();
-  }
+  const PotExperts xp;
+#include "dense_pot_eval.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -104,208 +82,11 @@ __global__ void pot_cold_list_kernel(const float* __restrict__ Hflf_in, const fl
   append_cold(list, count, (p < N) && !(hc == hc) && !(hs == hs), p);
 }
 
-// The successor's rows once the moves of a tile's columns stand in sh.move.  FIX = false (jump kernel): x, v, g hold the
-// end point of L.  FIX = true (pot_fix_kernel): columns that keep the end point are finished already (their rows hold
-// it); only the others are touched.
-template <int NB, bool REPLAY, int MODE, bool FIX, class SH>
-__device__ __forceinline__ void pot_finish(const PotJumpArgs& a, SH& sh, int64_t p, bool alive, int w, int c, int h,
-                                           Tile<NB>& x, Tile<NB>& v, Tile<NB>& g) {
-  const int mv = sh.move[c];
-  const int k = mv & 3;
-  bool refresh;  // this column's momentum is redrawn (HMCState.R)
-  bool touch = true;
-  if constexpr (MODE == kModeControl) {
-    if (!(k & 1)) {  // rejected: back to the pre-move state
-      tile_load<NB>(a.X_in, p, w, h, x);
-      tile_load<NB>(a.G_in, p, w, h, g);
-      tile_load<NB>(a.V_in, p, w, h, v);
-    } else {  // accepted L F: flip
-#pragma unroll
-      for (int r = 0; r < NB; ++r) v.b[r] = -v.b[r];
-    }
-    if (k & 2) {
-#pragma unroll
-      for (int r = 0; r < NB; ++r) v.b[r] = -v.b[r];
-    }
-    refresh = (mv & 4) != 0;  // batch-wide (markov_jump_hmc.py:138-141)
-  } else {
-    const bool keep_L = (k == 0);
-    if constexpr (FIX) touch = !keep_L;
-    if (!keep_L) {  // F / R keep the position (and its gradient)
-      tile_load<NB>(a.X_in, p, w, h, x);
-      tile_load<NB>(a.G_in, p, w, h, g);
-      tile_load<NB>(a.V_in, p, w, h, v);
-    }
-    if ((MODE == kModeCT && k == 0) || k == 1) {  // CT's FL move ends with a flip (:258,278); F flips
-#pragma unroll
-      for (int r = 0; r < NB; ++r) v.b[r] = -v.b[r];
-    }
-    refresh = (k == 2);
-  }
-  const bool tile_refreshes = __ballot(refresh) != 0ull;
-  if constexpr (REPLAY) {
-    if (refresh) {  // HMCState.R (hmc_state.py:121-129) with the recorded normals
-      Tile<NB> z;
-      tile_load<NB>(a.noise, alive ? p : 0, w, h, z);
-#pragma unroll
-      for (int r = 0; r < NB; ++r) v.b[r] = v.b[r] * a.r_keep + z.b[r] * a.r_mix;
-    }
-  } else {
-    // column by column (the set is the same in every wave: it comes from sh.move), the whole workgroup drawing
-    unsigned cols = (unsigned)(__ballot(refresh) & 0xFFFFFFFFull);
-    while (cols) {
-      const int c0 = __ffs((int)cols) - 1;
-      cols &= cols - 1;
-      const int64_t p0 = __shfl((long long)p, c0);
-      column_normals<NB, float>(a.key, (uint32_t)(a.first_pid + (p0 < a.N ? p0 : 0)), a.D, sh.zn);
-      __syncthreads();
-      if (c == c0) {
-        using V = typename VecN<NB>::type;
-        const float* zrow = sh.zn + 32 * NB * w;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const V z = *reinterpret_cast<const V*>(zrow + NB * acc_row(q, h));
-#pragma unroll
-          for (int r = 0; r < NB; ++r) v.b[r][q] = v.b[r][q] * a.r_keep + vget<NB>(z, r) * a.r_mix;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (tile_refreshes) {  // all waves take part in the reduction; only refreshed columns use the result
-    const float evr = pot_kinetic<NB>(sh, w, c, h, v);
-    if (refresh && w == 0 && h == 0) a.EV_out[p] = evr;
-  }
-  if (touch) {
-    tile_store<NB>(a.X_out, p, w, h, x);
-    tile_store<NB>(a.V_out, p, w, h, v);
-    tile_store<NB>(a.G_out, p, w, h, g);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// the jump kernel: one sampling_iteration attempt for a tile of 32 particles.
-// MODE = kModeMJHMC (markov_jump_hmc.py:355-415), kModeCT (ContinuousTimeHMC, :251-290) or kModeControl (HMCBase /
-// HMC / ControlHMC, :116-148 -- the comparison arm of the reference's ProductOfT experiments,
-// search/control_poe_36/mjhmc_objective.py:14).
-// ---------------------------------------------------------------------------------------------------
+// the jump kernel (dense_pot_jump.inc): one sampling_iteration attempt for a tile of 32 particles
 template <int NB, bool REPLAY, int MODE>
 __global__ __launch_bounds__(256, 1) void pot_jump_kernel(const PotJumpArgs a, const PotModel mdl) {
-  __shared__ Shared<NB> sh;
-  if (a.ctl->failed) return;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-  // MJHMC: the inverse-L tiles of this iteration's list are the first items of the launch
-  const int ncold = MODE == kModeMJHMC ? *a.cold_count : 0;
-  const int64_t nft = (ncold + kP - 1) / kP;
-  if ((int64_t)blockIdx.x >= nft + a.ntiles) return;
-  if (MODE == kModeMJHMC && blockIdx.x == 0 && threadIdx.x == 0) {
-    *a.zero_count = 0;   // the list two iterations back is consumed: its counter is free for the next iteration's appends
-    if (ncold) atomicAdd(&a.stats[3], (unsigned long long)ncold << 32);   // integrated here: the high half of the cold tally
-  }
-  unsigned n0 = 0, n1 = 0, n2 = 0, n3 = 0;  // tallies (meaning per mode: fill_iter_stats in api.hip)
-  bool any_bad = false;
-  AReg<NB> ar;
-  areg_load<NB>(mdl, w, c, h, ar);
-  stage_bias<NB>(mdl, sh);
-  for (int64_t item = blockIdx.x; item < nft + a.ntiles; item += gridDim.x) {
-    const bool inverse = item < nft;   // (uniform over the workgroup)
-    int64_t p;
-    if (inverse) {
-      const int64_t slot = item * kP + c;
-      p = a.cold_list[slot < ncold ? slot : ncold - 1];  // pad the last tile with a repeat
-    } else {
-      p = (item - nft) * kP + c;
-    }
-    const bool alive = p < a.N;
-    Tile<NB> x, v, g;
-    tile_load<NB>(a.X_in, p, w, h, x);
-    tile_load<NB>(a.V_in, p, w, h, v);
-    tile_load<NB>(a.G_in, p, w, h, g);
-    if (inverse) {
-#pragma unroll
-      for (int r = 0; r < NB; ++r) v.b[r] = -v.b[r];
-    }
-    float EXL = 0.f;
-    pot_trajectory<NB>(mdl, ar, sh, w, c, h, lane, x, v, g, a.L, a.eps, a.chalf, &EXL);
-    const float EVL = pot_kinetic<NB>(sh, w, c, h, v);
-    const float HL = EXL + EVL;
-    if (inverse) {
-      if (w == 0 && h == 0) a.Hwork[p] = HL;
-      __syncthreads();
-      continue;
-    }
-
-    // rates / acceptance, waiting times, first minimum: lanes 0..31 of wave 0, one particle each
-    if (w == 0 && h == 0) {
-      const uint32_t pid = (uint32_t)(a.first_pid + (alive ? p : 0));
-      const float EX0 = a.EX_in[p], EV0 = a.EV_in[p];
-      const float H0 = EX0 + EV0;
-      // H of the inverse-L proposal: cached; or the L proposal of the iteration in which the particle flipped; or being
-      // integrated by an inverse-L item of this very launch -- then the particle is left pending for pot_fix_kernel
-      float Hflf = MODE == kModeMJHMC ? a.Hflf_in[p] : 0.f;
-      const bool cold = !(Hflf == Hflf);
-      bool pending = false;
-      if (cold) {
-        Hflf = a.Hspec_in[p];
-        pending = !(Hflf == Hflf);
-      }
-      double best = 0.0;
-      bool bad = false, gate = false;
-      int k = 0;
-      if (!pending) {
-        if constexpr (MODE == kModeMJHMC)
-          k = dense_decide<REPLAY>(H0, HL, Hflf, a.p_r, pid, alive ? p : 0, a.N, a.rexp, a.key, best, bad);
-        else if constexpr (MODE == kModeCT)
-          k = dense_decide_ct<REPLAY>(H0, HL, a.p_r, pid, alive ? p : 0, a.N, a.rexp, a.key, best, bad);
-        else
-          k = dense_control<REPLAY>(H0, HL, a.p_r, a.p_flip, pid, alive ? p : 0, a.N, a.runif, a.key, gate);
-        any_bad |= (bad && alive);
-        // every move but L clears the cache; of those only the R-movers need their inverse-L proposal integrated
-        if constexpr (MODE == kModeMJHMC) append_cold(a.next_list, a.next_count, alive && k == 2, p);
-        a.dwell[p] = best;
-        a.dwell_ring[p] = best;
-        a.trans[p] = (uint8_t)k;
-      }
-      sh.move[c] = k | (gate ? 4 : 0);
-      if (alive) {
-        if constexpr (MODE == kModeControl) {  // l_count, f_count, R applied, fl_count (markov_jump_hmc.py:143-148)
-          n0 += (k == 3);
-          n1 += (k == 2);
-          n2 += gate ? 1u : 0u;
-          n3 += (k == 1);
-        } else if (!pending) {
-          n0 += (k == 0);
-          n1 += (k == 1);
-          n2 += (k == 2);
-        }
-        if constexpr (MODE == kModeMJHMC) n3 += cold;   // the reference integrates F L F for every one of these
-      }
-      // scalars of the successors that keep or take whole states; a refreshed kinetic energy is filled in below
-      const bool took_L = MODE == kModeControl ? (k & 1) : (k == 0);
-      a.EX_out[p] = took_L ? EXL : EX0;
-      a.EV_out[p] = took_L ? EVL : EV0;
-      if (!pending) {
-        a.Hflf_out[p] = (MODE == kModeMJHMC && k == 0) ? H0 : __builtin_nanf("");
-        if constexpr (MODE == kModeMJHMC) a.Hspec_out[p] = (k == 1) ? HL : __builtin_nanf("");
-      }
-    }
-    __syncthreads();
-    pot_finish<NB, REPLAY, MODE, false>(a, sh, p, alive, w, c, h, x, v, g);
-    __syncthreads();
-  }
-  if (any_bad) {
-    a.ctl->failed = 1;
-    a.ctl->failed_iter = a.iter;
-  }
-  __shared__ unsigned tally[4];
-  if (threadIdx.x < 4) tally[threadIdx.x] = 0;
-  __syncthreads();
-  if (n0) atomicAdd(&tally[0], n0);
-  if (n1) atomicAdd(&tally[1], n1);
-  if (n2) atomicAdd(&tally[2], n2);
-  if (n3) atomicAdd(&tally[3], n3);
-  __syncthreads();
-  if (threadIdx.x < 4 && tally[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
+  const PotExperts xp;
+#include "dense_pot_jump.inc"
 }
 
 // The particles the jump kernel left pending (this iteration's list): both trajectories are done now -- H of the
@@ -373,36 +154,11 @@ __global__ __launch_bounds__(256) void pot_fix_kernel(const PotJumpArgs a) {
   if (threadIdx.x < 3 && tally[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// HMCState.leapfrog / HMCState.L on caller-supplied states (hmc_state.py:86-100; figures/poe_fig.py:59 assigns and
-// integrates states of a ProductOfT sampler): dE/dX at the start point, L steps, energies of the end point.
-// ---------------------------------------------------------------------------------------------------
+// HMCState.leapfrog / HMCState.L on caller-supplied states (dense_pot_leap.inc)
 template <int NB>
 __global__ __launch_bounds__(256, 1) void pot_leap_kernel(const PotLeapArgs a, const PotModel mdl) {
-  __shared__ Shared<NB> sh;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-  AReg<NB> ar;
-  areg_load<NB>(mdl, w, c, h, ar);
-  stage_bias<NB>(mdl, sh);
-  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-    const int64_t p = tile * kP + c;
-    Tile<NB> x, v, g;
-    tile_load<NB>(a.X, p, w, h, x);
-    tile_load<NB>(a.V, p, w, h, v);
-    float ex = 0.f;
-    pot_gradient<NB>(mdl, ar, sh, w, c, h, lane, x, g, true, &ex);
-    __syncthreads();
-    pot_trajectory<NB>(mdl, ar, sh, w, c, h, lane, x, v, g, a.L, a.eps, a.chalf, &ex);
-    const float ev = pot_kinetic<NB>(sh, w, c, h, v);
-    tile_store<NB>(a.X_out, p, w, h, x);
-    tile_store<NB>(a.V_out, p, w, h, v);
-    if (a.G) tile_store<NB>(a.G, p, w, h, g);
-    if (w == 0 && h == 0) {
-      if (a.EX) a.EX[p] = ex;
-      if (a.EV) a.EV[p] = ev;
-    }
-    __syncthreads();
-  }
+  const PotExperts xp;
+#include "dense_pot_leap.inc"
 }
 
 #ifdef POT_STAMPS
@@ -509,14 +265,15 @@ void pot_big_eval(const PotBigModel& m, const float* X32, float* G32, float* E32
 }
 
 template <int NB, int MODE>
-static void launch_jump_mode(const PotJumpArgs& a, const PotModel& mdl, unsigned grid, hipStream_t st) {
+static void launch_jump_mode(const PotJumpArgs& a, const PotModel& mdl, unsigned grid, hipStream_t st, const PotGenerated* gen) {
   const bool replay = MODE == kModeControl ? (a.runif && a.noise) : (a.rexp && a.noise);
-  if (replay) hipLaunchKernelGGL((pot_jump_kernel<NB, true, MODE>), dim3(grid), dim3(256), 0, st, a, mdl);
+  if (gen) pot_launch_generated(gen->jump32[MODE][replay ? 1 : 0], grid, st, a, mdl, gen->lin);
+  else if (replay) hipLaunchKernelGGL((pot_jump_kernel<NB, true, MODE>), dim3(grid), dim3(256), 0, st, a, mdl);
   else hipLaunchKernelGGL((pot_jump_kernel<NB, false, MODE>), dim3(grid), dim3(256), 0, st, a, mdl);
 }
 
 template <int NB>
-static void launch_jump_nb(const PotJumpArgs& a, const PotModel& mdl, hipStream_t st) {
+static void launch_jump_nb(const PotJumpArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen) {
   const int cus = resident_cus();
   if (a.mode == kModeMJHMC) {  // only MJHMC has the inverse-L proposal and its cache
     if (a.iter == 0 || a.rescan) {  // first iteration of a call: the three counters cleared (they are adjacent), the list from a scan
@@ -526,33 +283,35 @@ static void launch_jump_nb(const PotJumpArgs& a, const PotModel& mdl, hipStream_
     }
     // forward tiles + at most as many inverse-L tiles (workgroups without an item leave at once)
     const unsigned grid = (unsigned)std::min<int64_t>(2 * a.ntiles, cus);
-    launch_jump_mode<NB, kModeMJHMC>(a, mdl, grid, st);
+    launch_jump_mode<NB, kModeMJHMC>(a, mdl, grid, st, gen);
     const unsigned fgrid = (unsigned)std::min<int64_t>(a.ntiles, 4 * cus);
     if (a.rexp && a.noise) hipLaunchKernelGGL((pot_fix_kernel<NB, true>), dim3(fgrid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((pot_fix_kernel<NB, false>), dim3(fgrid), dim3(256), 0, st, a);
   } else {
     const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, cus);
-    if (a.mode == kModeCT) launch_jump_mode<NB, kModeCT>(a, mdl, grid, st);
-    else launch_jump_mode<NB, kModeControl>(a, mdl, grid, st);
+    if (a.mode == kModeCT) launch_jump_mode<NB, kModeCT>(a, mdl, grid, st, gen);
+    else launch_jump_mode<NB, kModeControl>(a, mdl, grid, st, gen);
   }
 }
 
-void pot_launch_jump(const PotJumpArgs& a, const PotModel& mdl, hipStream_t st) {
-  if (mdl.dim == 128) launch_jump_nb<1>(a, mdl, st);
-  else if (mdl.dim == 256) launch_jump_nb<2>(a, mdl, st);
-  else launch_jump_nb<4>(a, mdl, st);
+void pot_launch_jump(const PotJumpArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen) {
+  if (mdl.dim == 128) launch_jump_nb<1>(a, mdl, st, gen);
+  else if (mdl.dim == 256) launch_jump_nb<2>(a, mdl, st, gen);
+  else launch_jump_nb<4>(a, mdl, st, gen);
 }
 
-void pot_launch_leap(const PotLeapArgs& a, const PotModel& mdl, hipStream_t st) {
+void pot_launch_leap(const PotLeapArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen) {
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
-  if (mdl.dim == 128) hipLaunchKernelGGL(pot_leap_kernel<1>, dim3(grid), dim3(256), 0, st, a, mdl);
+  if (gen) pot_launch_generated(gen->leap, grid, st, a, mdl, gen->lin);
+  else if (mdl.dim == 128) hipLaunchKernelGGL(pot_leap_kernel<1>, dim3(grid), dim3(256), 0, st, a, mdl);
   else if (mdl.dim == 256) hipLaunchKernelGGL(pot_leap_kernel<2>, dim3(grid), dim3(256), 0, st, a, mdl);
   else hipLaunchKernelGGL(pot_leap_kernel<4>, dim3(grid), dim3(256), 0, st, a, mdl);
 }
 
-void pot_launch_eval(const PotEvalArgs& a, const PotModel& mdl, hipStream_t st) {
+void pot_launch_eval(const PotEvalArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen) {
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
-  if (mdl.dim == 128) hipLaunchKernelGGL(pot_eval_kernel<1>, dim3(grid), dim3(256), 0, st, a, mdl);
+  if (gen) pot_launch_generated(gen->eval, grid, st, a, mdl, gen->lin);
+  else if (mdl.dim == 128) hipLaunchKernelGGL(pot_eval_kernel<1>, dim3(grid), dim3(256), 0, st, a, mdl);
   else if (mdl.dim == 256) hipLaunchKernelGGL(pot_eval_kernel<2>, dim3(grid), dim3(256), 0, st, a, mdl);
   else hipLaunchKernelGGL(pot_eval_kernel<4>, dim3(grid), dim3(256), 0, st, a, mdl);
 }

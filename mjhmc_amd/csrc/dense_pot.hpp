@@ -1,6 +1,8 @@
 // Argument blocks of the ProductOfT MFMA kernels (dense_pot.hip).
 #pragma once
+#ifndef __HIPCC_RTC__  // hipRTC pre-includes the device runtime (linear_energy.hip)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include "elementwise.hpp"  // Control, RngKey, philox
@@ -122,6 +124,15 @@ struct PotEvalArgs {
   int64_t N, ntiles, first_pid;
   int D;
   RngKey key;
+};
+
+// The experts of a linear-model energy (MJHMC_E_LINEAR_EXPR: E = sum_j f(u_j, j), u = W x + b; dense_pot_kernels.hpp
+// LinearExperts), the third argument of its generated kernels
+struct PotLinear {
+  const float* q;   // [4][stride] per-expert parameter rows (q[m] at expert j: q[m * stride + j])
+  const float* p;   // shared parameters
+  int K;            // experts; j >= K is padding
+  int stride;       // the padded dimension
 };
 
 // Rates, waiting times and first minimum of ONE particle, evaluated serially by one lane (the dense
@@ -251,14 +262,31 @@ struct PotBigModel {
   int dim;             // ndims rounded up to a multiple of 512
   int ndims;
 };
+#ifndef __HIPCC_RTC__  // (host entry points: not in the hipRTC translation units of linear_energy.hip)
 // E (or nullptr) and dE/dX (or nullptr) of rows X32 [rows_pad][dim] (float32, rows_pad a multiple of 32); U: scratch of
 // the same shape.  2 (dim / 512)^2 block-GEMM launches + one elementwise pass.
 void pot_big_eval(const PotBigModel& m, const float* X32, float* G32, float* E32, float* U, int64_t rows_pad, hipStream_t st);
 
-void pot_launch_jump(const PotJumpArgs& a, const PotModel& mdl, hipStream_t st);
-void pot_launch_eval(const PotEvalArgs& a, const PotModel& mdl, hipStream_t st);
-void pot_launch_leap(const PotLeapArgs& a, const PotModel& mdl, hipStream_t st);
-void pot64_launch_jump(const Pot64JumpArgs& a, const PotModel& mdl, hipStream_t st);
+// The hipRTC-built kernels of one linear-model energy (linear_energy.hip, one NB): the entry points below launch them, with
+// the same grids and the same cold-list / fix / decide kernels, in place of ProductOfT's own when `gen` is given
+struct PotGenerated {
+  hipFunction_t jump32[3][2] = {};   // dense_pot_jump.inc   [mode][replay]
+  hipFunction_t jump64[3][2] = {};   // dense_pot64_jump.inc [mode][replay]
+  hipFunction_t eval = nullptr, leap = nullptr;
+  PotLinear lin{};
+};
+
+void pot_launch_jump(const PotJumpArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen = nullptr);
+void pot_launch_eval(const PotEvalArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen = nullptr);
+void pot_launch_leap(const PotLeapArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen = nullptr);
+void pot64_launch_jump(const Pot64JumpArgs& a, const PotModel& mdl, hipStream_t st, const PotGenerated* gen = nullptr);
+// a generated kernel on (args, model, experts): the signature of linear_energy.hip's wrappers
+template <class A>
+inline void pot_launch_generated(hipFunction_t f, unsigned grid, hipStream_t st, const A& a, const PotModel& mdl, const PotLinear& lin) {
+  void* params[] = {(void*)&a, (void*)&mdl, (void*)&lin};
+  (void)hipModuleLaunchKernel(f, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
+}
 int pot64_scratch_workgroups();  // workgroups a pot64 launch may run: rows of Pot64JumpArgs::scratch to provide per launch
+#endif
 
 }  // namespace mjhmc

@@ -1,0 +1,144 @@
+// Body of the float64-state jump kernel, included INSIDE the kernel definition (dense_pot64.hip; linear_energy.hip for the
+// kernels of a linear-model energy): one sampling_iteration attempt for a tile of 32 particles (MODE as in
+// dense_pot_jump.inc).  In scope: template parameters NB, REPLAY, MODE, the arguments `a` and `mdl`, the experts `xp`.
+  __shared__ Shared64<NB> sh;
+  if (a.ctl->failed) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
+  // MJHMC: the inverse-L tiles of this iteration's list are the first items of the launch
+  const int ncold = MODE == kModeMJHMC ? *a.cold_count : 0;
+  const int64_t nft = (ncold + kP - 1) / kP;
+  if ((int64_t)blockIdx.x >= nft + a.ntiles) return;
+  if (MODE == kModeMJHMC && blockIdx.x == 0 && threadIdx.x == 0) {
+    *a.zero_count = 0;   // the list two iterations back is consumed: its counter is free for the next iteration's appends
+    if (ncold) atomicAdd(&a.stats[3], (unsigned long long)ncold << 32);   // integrated here: the high half of the cold tally
+  }
+  // tallies (meaning per mode: fill_iter_stats in api.hip) and the failure flag live in LDS, not in registers that would be
+  // live across every GEMM loop and streamed pass of the kernel: [0..3] counts, [4] some particle met a non-finite rate
+  __shared__ unsigned tally[5];
+  if (threadIdx.x < 5) tally[threadIdx.x] = 0;
+  AReg<NB> ar;
+  areg_load<NB>(mdl, w, c, h, ar);
+  stage_bias<NB>(mdl, sh.s);
+  const Work<NB> wk = work_of<NB>(a.scratch, blockIdx.x, w, lane);
+  for (int64_t item = blockIdx.x; item < nft + a.ntiles; item += gridDim.x) {
+    const bool inverse = item < nft;   // (uniform over the workgroup)
+    auto column_of = [&](int64_t it) -> int64_t {
+      if (it < nft) {
+        const int64_t slot = it * kP + c;
+        return a.cold_list[slot < ncold ? slot : ncold - 1];  // pad the last tile with a repeat
+      }
+      return (it - nft) * kP + c;
+    };
+    // (everything that is not needed during the trajectory -- the scalars of the decision, the output rows' addresses --
+    // is fetched / formed after it: the kernel sits at its 512-register budget, and what is live across the GEMM loops
+    // and the streamed passes decides whether those spill; tools/check_isa.sh gates both.  That includes the column's own
+    // index: it is looked up again behind the trajectory, through an item number the compiler cannot see through)
+    Tile<NB> g;
+    VTile<NB> v;
+    float exl = 0.f;
+    double EVL;
+    {
+      const int64_t p = column_of(item);
+      const size_t roff = (size_t)p * (128 * NB) + 32 * NB * w + 4 * NB * h;   // this lane's elements inside a [*][DIM] matrix
+      // the end point's position: into the output rows -- an inverse-L item's is wanted by nobody: into the second half of
+      // the workgroup's working rows (32 rows, the momentum's would-be working copy: unused)
+      auto xend = [&]() -> double* {
+        int64_t it = item;
+        asm volatile("" : "+s"(it));
+        const size_t lane_part = 32 * NB * w + 4 * NB * h;
+        return it < nft ? a.scratch + (size_t)blockIdx.x * (Work<NB>::kArea) + Work<NB>::kArea / 2 + (size_t)c * (128 * NB) + lane_part
+                        : a.X_out + (size_t)column_of(it) * (128 * NB) + lane_part;
+      };
+      tile_load_narrow<NB>(a.G_in + roff, g);
+      EVL = pot64_trajectory<NB, kXRows>(mdl, xp, ar, sh, w, c, h, lane, wk, a.X_in + roff, a.V_in + roff, xend, g, v, a.L, a.eps,
+                                         a.chalf, &exl, inverse);
+    }
+    int64_t item_again = item;
+    asm volatile("" : "+s"(item_again));
+    const int64_t p = column_of(item_again);
+    const bool alive = p < a.N;
+    const size_t roff = (size_t)p * (128 * NB) + 32 * NB * w + 4 * NB * h;
+    const double EXL = (double)exl;
+    const double HL = EXL + EVL;
+    if (inverse) {
+      if (w == 0 && h == 0) a.Hwork[p] = HL;
+      __syncthreads();
+      continue;
+    }
+
+    if constexpr (MODE == kModeMJHMC) {
+      // the jump process itself -- rates, clocks, first minimum, the successor of a move that is not L -- belongs to
+      // pot64_decide_kernel, which runs when this launch's inverse-L items are done too: here the end point of L is
+      // written as if taken (position: by the last drift), with its energies
+      if (w == 0 && h == 0) {
+        a.EX_out[p] = EXL;
+        a.EV_out[p] = EVL;
+      }
+      using DV = typename DVecN<NB>::type;
+      double* vo = a.V_out + roff;
+      double* go = a.G_out + roff;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        DV vv, gg;
+#pragma unroll
+        for (int r = 0; r < NB; ++r) {
+          dset<NB>(vv, r, v.b[r][q]);
+          dset<NB>(gg, r, (double)g.b[r][q]);
+        }
+        dv_store<NB>(vo, q, vv);
+        dv_store<NB>(go, q, gg);
+      }
+      __syncthreads();
+      continue;
+    }
+
+    // the discrete-time and continuous-time control samplers decide here: lanes 0..31 of wave 0, one particle each
+    if (w == 0 && h == 0) {
+      const int64_t pp = alive ? p : 0;
+      const uint32_t pid = (uint32_t)(a.first_pid + pp);
+      const double EX0 = a.EX_in[p], EV0 = a.EV_in[p];
+      const double H0 = EX0 + EV0;
+      double best = 0.0;
+      bool bad = false, gate = false;
+      const int k = pot64_decide<REPLAY, MODE>(a, H0, HL, 0.0, pp, pid, best, bad, gate);
+      if (bad && alive) tally[4] = 1;
+      a.dwell[p] = best;
+      a.dwell_ring[p] = best;
+      a.trans[p] = (uint8_t)k;
+      sh.s.move[c] = k | (gate ? 4 : 0);
+      {
+        // one LDS atomic per tally and tile (the 32 deciding lanes of wave 0)
+        unsigned long long b0, b1, b2, b3 = 0ull;
+        if constexpr (MODE == kModeControl) {  // l_count, f_count, R applied, fl_count (markov_jump_hmc.py:143-148)
+          b0 = __ballot(alive && k == 3);
+          b1 = __ballot(alive && k == 2);
+          b2 = __ballot(alive && gate);
+          b3 = __ballot(alive && k == 1);
+        } else {
+          b0 = __ballot(alive && k == 0);
+          b1 = __ballot(alive && k == 1);
+          b2 = __ballot(alive && k == 2);
+        }
+        if (c == 0) {
+          if (b0) atomicAdd(&tally[0], (unsigned)__popcll(b0));
+          if (b1) atomicAdd(&tally[1], (unsigned)__popcll(b1));
+          if (b2) atomicAdd(&tally[2], (unsigned)__popcll(b2));
+          if (b3) atomicAdd(&tally[3], (unsigned)__popcll(b3));
+        }
+      }
+      // scalars of the successors that keep or take whole states; a refreshed kinetic energy is filled in below
+      const bool took_L = MODE == kModeControl ? (k & 1) : (k == 0);
+      a.EX_out[p] = took_L ? EXL : EX0;
+      a.EV_out[p] = took_L ? EVL : EV0;
+      a.Hflf_out[p] = __builtin_nan("");
+    }
+    __syncthreads();
+    pot64_finish<NB, REPLAY, MODE, false>(a, sh, p, alive, roff, w, c, h, v, g);
+    __syncthreads();
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && tally[4]) {
+    a.ctl->failed = 1;
+    a.ctl->failed_iter = a.iter;
+  }
+  if (threadIdx.x < 4 && tally[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)tally[threadIdx.x]);

@@ -2,7 +2,9 @@
 // arithmetic, float64 state around the float32 force): the accumulator-layout tile, its LDS image, the software-pipelined
 // GEMM over the L2-resident pre-scaled matrices, the gradient evaluation built from two of them.
 #pragma once
+#ifndef __HIPCC_RTC__  // hipRTC pre-includes the device runtime (linear_energy.hip)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include "dense_pot.hpp"
@@ -333,14 +335,25 @@ __device__ __forceinline__ void stage_bias(const PotModel& mdl, Shared<NB>& sh) 
 }
 
 
+// The elementwise stage of the force, between its two GEMMs: per expert j of the padded dimension, from u_j (accumulator
+// layout) the energy term and phi_j, the factor the second GEMM multiplies into the expert's row.  An expert type XP has
+//   kProductOfT              true: the built-in ProductOfT's stage, written out in pot_gradient_published (alpha_j from
+//                            PotModel::alpha, distributions.py:430-432; padded experts have alpha = 0 and zero rows)
+//   energy_sum<NB>(u, w, h)  otherwise: the sum of this lane's energy terms (the caller adds the lanes up)
+//   phi<NB>(u, w, h)         and u <- phi(u) in place
+// LinearExperts (dense_pot_kernels.hpp) takes a caller's f / f' and masks the padded experts.
+struct PotExperts {
+  static constexpr bool kProductOfT = true;
+};
+
 // gradient of the energy at the X held in `x`; optionally the energy itself.
 // On return g holds dE/dX in the same layout as x.  Two barriers (X and H live in separate buffers:
 // a wave can only reach the next publish of a buffer after every wave has passed the barrier that
 // follows its last read of it).
 // pot_gradient_published: the same from the barrier on -- the caller has written its part of the X image
 // (sh.pub[0][w], publish()'s layout) already.
-template <int NB>
-__device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
+template <int NB, class XP>
+__device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, const XP& xp, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
                                                        int lane, Tile<NB>& g, bool want_energy, float* energy_out,
                                                        int stamp_slot = 0) {
   __syncthreads();
@@ -349,26 +362,36 @@ __device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, AReg
   rowvec_load<NB>(sh.cb, w, h, u);                     // u starts at b_j / nu_j (LDS copy, stage_bias)
   gemm_any<NB, false>(mdl, ar, sh.pub[0], w, c, h, lane, u);   // + sum_d W[d][j]/nu_j * x_d
   POT_STAMP(2);
-  if (want_energy) {                                   // E = sum_j alpha_j log(1 + u_j^2)  (distributions.py:430-432)
-    using V = typename VecN<NB>::type;
-    const float* al = mdl.alpha + 32 * NB * w;
-    float s = 0.f;
+  if constexpr (XP::kProductOfT) {
+    // ProductOfT's experts written out in place: with the stage behind the expert type's member functions hipcc scheduled
+    // the built-in kernels differently; this is their original text
+    if (want_energy) {                                   // E = sum_j alpha_j log(1 + u_j^2)  (distributions.py:430-432)
+      using V = typename VecN<NB>::type;
+      const float* al = mdl.alpha + 32 * NB * w;
+      float s = 0.f;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const V a4 = *reinterpret_cast<const V*>(al + NB * acc_row(q, h));
+      for (int q = 0; q < 16; ++q) {
+        const V a4 = *reinterpret_cast<const V*>(al + NB * acc_row(q, h));
 #pragma unroll
-      for (int r = 0; r < NB; ++r) s += vget<NB>(a4, r) * logf(1.0f + u.b[r][q] * u.b[r][q]);
+        for (int r = 0; r < NB; ++r) s += vget<NB>(a4, r) * logf(1.0f + u.b[r][q] * u.b[r][q]);
+      }
+      const float part = half_sum(s);
+      if (h == 0) sh.red[0][w][c] = part;
     }
-    const float part = half_sum(s);
-    if (h == 0) sh.red[0][w][c] = part;
+#pragma unroll
+    for (int r = 0; r < NB; ++r)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float uu = u.b[r][q];
+        u.b[r][q] = uu * __builtin_amdgcn_rcpf(1.0f + uu * uu);   // phi(u) (v_rcp_f32: 1 ulp); the factor (nu+1)/nu lives in W2T
+      }
+  } else {
+    if (want_energy) {                                 // E = sum_j f(u_j, j)
+      const float part = half_sum(xp.template energy_sum<NB>(u, w, h));
+      if (h == 0) sh.red[0][w][c] = part;
+    }
+    xp.template phi<NB>(u, w, h);
   }
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float uu = u.b[r][q];
-      u.b[r][q] = uu * __builtin_amdgcn_rcpf(1.0f + uu * uu);   // phi(u) (v_rcp_f32: 1 ulp); the factor (nu+1)/nu lives in W2T
-    }
   publish<NB>(sh.pub[1][w], lane, u);
   POT_STAMP(3);
   __syncthreads();
@@ -384,14 +407,14 @@ __device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, AReg
   }
 }
 
-template <int NB>
-__device__ __forceinline__ void pot_gradient(const PotModel& mdl, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
+template <int NB, class XP>
+__device__ __forceinline__ void pot_gradient(const PotModel& mdl, const XP& xp, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
                                              int lane, const Tile<NB>& x, Tile<NB>& g, bool want_energy,
                                              float* energy_out) {
   [[maybe_unused]] const int stamp_slot = 0;
   POT_STAMP(0);
   publish<NB>(sh.pub[0][w], lane, x);
-  pot_gradient_published<NB>(mdl, ar, sh, w, c, h, lane, g, want_energy, energy_out);
+  pot_gradient_published<NB>(mdl, xp, ar, sh, w, c, h, lane, g, want_energy, energy_out);
 }
 
 // kinetic energy sum(v^2)/2 per particle (all lanes of column c get it).  One barrier pair.
@@ -412,8 +435,8 @@ __device__ __forceinline__ float pot_kinetic(SH& sh, int w, int c, int h, const 
 
 // L leapfrog steps (hmc_state.py:86-100); g enters as dE/dX at x, leaves as dE/dX at the new x.
 // Returns E(x_new) through *ex (the last gradient evaluation already has u(x_new)).
-template <int NB>
-__device__ __forceinline__ void pot_trajectory(const PotModel& mdl, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
+template <int NB, class XP>
+__device__ __forceinline__ void pot_trajectory(const PotModel& mdl, const XP& xp, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
                                                int lane, Tile<NB>& x, Tile<NB>& v, Tile<NB>& g, int L, float eps,
                                                float chalf, float* ex) {
   // the closing half kick of a step and the opening one of the next use the same gradient: one kick of twice the size
@@ -429,7 +452,7 @@ __device__ __forceinline__ void pot_trajectory(const PotModel& mdl, AReg<NB>& ar
     for (int r = 0; r < NB; ++r)
 #pragma unroll
       for (int q = 0; q < 16; ++q) x.b[r][q] = x.b[r][q] + eps * v.b[r][q];
-    pot_gradient<NB>(mdl, ar, sh, w, c, h, lane, x, g, s == L - 1, ex);
+    pot_gradient<NB>(mdl, xp, ar, sh, w, c, h, lane, x, g, s == L - 1, ex);
     const float ck = s == L - 1 ? chalf : 2.0f * chalf;
 #pragma unroll
     for (int r = 0; r < NB; ++r)

@@ -9,6 +9,7 @@
 #include "dense_pot.hpp"
 #include "dense_sic.hpp"
 #include "elementwise.hpp"
+#include "linear_energy.hpp"
 #include "user_expr.hpp"
 
 using namespace mjhmc;
@@ -45,10 +46,15 @@ struct mjhmc_energy {
   void* dev32 = nullptr;
   float* pot[4] = {nullptr, nullptr, nullptr, nullptr};  // ProductOfT: W1, W2T, cb, alpha (float32, padded to 512)
   int pot_dim = kPotDim;  // rows padded to 128, 256 or 512 -- or, beyond the tile kernels, to a multiple of 512 (pot_big())
-  PotModel pot_model() const { return PotModel{pot[0], pot[1], pot[2], pot[3], pot_dim, ep.ndims}; }
+  int pot_rows = 0;       // LINEAR_EXPR: max(ndims, nexperts), the rows the matrices may hold (0: ndims)
+  PotModel pot_model() const { return PotModel{pot[0], pot[1], pot[2], pot[3], pot_dim, pot_rows ? pot_rows : ep.ndims}; }
   bool pot_big() const { return is_pot() && pot_dim > kPotDim; }   // matrices stored as 512 x 512 blocks, multi-pass path only
   PotBigModel pot_big_model() const { return PotBigModel{pot[0], pot[1], pot[2], pot[3], pot_dim, ep.ndims}; }
-  bool is_pot() const { return ep.kind == MJHMC_E_PRODUCT_OF_T; }
+  // the ProductOfT tile kernels' energies: ProductOfT itself and the linear-model energies, which run its kernels (and every
+  // path of it) with their own experts (linear_energy.hip; never pot_big())
+  bool is_pot() const { return ep.kind == MJHMC_E_PRODUCT_OF_T || ep.kind == MJHMC_E_LINEAR_EXPR; }
+  LinearEnergy* lin = nullptr;  // MJHMC_E_LINEAR_EXPR: its hipRTC-built kernels, launched by the pot_launch_* entry points
+  const PotGenerated* pot_gen() const { return lin ? &lin->gen : nullptr; }
   void* sic[3] = {nullptr, nullptr, nullptr};  // SparseImageCode: A1, A2 (bf16, fragment order), y (float32 [P][256])
   float sic_lambda = 0.f;
   int sic_cauchy = 1;

@@ -520,7 +520,7 @@ static void pot_force32(mjhmc_sampler* s, float* const* buf, bool want_G, bool w
   a.first_pid = 0;
   a.D = s->D;
   a.key = RngKey{0u, 0u, 0u, 0u};
-  pot_launch_eval(a, s->en->pot_model(), s->stream);
+  pot_launch_eval(a, s->en->pot_model(), s->stream, s->en->pot_gen());
 }
 
 // ProductOfT as the reference runs it (distributions.py:408-415 with hmc_state.py:29-38): float64 HMCState arrays around

@@ -1,0 +1,164 @@
+// Linear-model energies:
+//
+//     E(x) = sum_{j<K} f(u_j, j),   u = W x + b,   dE/dx = W^T f'(u)        (W: K x D, 1 <= D, K <= 512)
+//
+// with f and f' C expressions of `u` (float), `j` (int), `p[k]` (shared float parameters) and `q[m]` (per-expert parameter
+// row m at expert j, m < 4).  This is the ProductOfT tile kernel's force with its elementwise stage replaced: the first
+// GEMM forms u (W1 = W^T, cb = b), the caller's f' gives phi(u), the second GEMM applies W (W2T = W).  The model is
+// padded to P = 128, 256 or 512 rows in both dimensions like ProductOfT's; experts j >= K are masked (LinearExperts,
+// dense_pot_kernels.hpp), the state rows d >= D are zero as everywhere.  The kernels are the built-in ones' own text (the
+// fragments dense_pot_{eval,jump,leap}.inc and dense_pot64_jump.inc), compiled with hipRTC around the generated functor
+// for the one NB the model needs: float32-state jump kernels x 3 modes x replay, the float64-state ones likewise, eval
+// and leap -- 14 kernels.  The cold-list, fix and decide kernels take no model and are the library's own.  Everything
+// else (dE/dX storage, call blocks, parts, the multi-pass path at L = 0, state operations) is ProductOfT's: is_pot().
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "handles.hpp"
+#include "linear_energy.hpp"
+
+namespace {
+
+struct Compiled {
+  std::vector<char> code;
+  std::vector<std::string> lowered;
+};
+
+std::mutex g_cache_mu;
+std::map<std::string, std::unique_ptr<Compiled>> g_cache;   // generated source + NB -> code object (never evicted)
+
+std::string linear_source(const std::string& energy_expr, const std::string& grad_expr) {
+  std::string s;
+  s += "#include \"dense_pot_kernels.hpp\"\n";
+  s += "#include \"dense_pot64_kernels.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += "// E = sum_j f(u_j, j), dE/dx = W^T f'(u): the caller's expressions (u float, j int, p[k], q[m])\n";
+  s += "struct LinUserF {\n";
+  s += "  static __device__ __forceinline__ float f(float u, int j, const float* __restrict__ p, LinQ q) {\n";
+  s += "    (void)u; (void)j; (void)p; (void)q;\n";
+  s += "    return (float)(" + energy_expr + ");\n  }\n";
+  s += "  static __device__ __forceinline__ float fp(float u, int j, const float* __restrict__ p, LinQ q) {\n";
+  s += "    (void)u; (void)j; (void)p; (void)q;\n";
+  s += "    return (float)(" + grad_expr + ");\n  }\n";
+  s += "};\n";
+  s += "using LinXP = LinearExperts<LinUserF>;\n";
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_eval_kernel(const PotEvalArgs a, const PotModel mdl, const PotLinear lin) {\n";
+  s += "  const LinXP xp{lin};\n#include \"dense_pot_eval.inc\"\n}\n";
+  s += "template <int NB, bool REPLAY, int MODE>\n__global__ __launch_bounds__(256, 1) void lin_jump_kernel(const PotJumpArgs a, const PotModel mdl, const PotLinear lin) {\n";
+  s += "  const LinXP xp{lin};\n#include \"dense_pot_jump.inc\"\n}\n";
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_leap_kernel(const PotLeapArgs a, const PotModel mdl, const PotLinear lin) {\n";
+  s += "  const LinXP xp{lin};\n#include \"dense_pot_leap.inc\"\n}\n";
+  s += "template <int NB, bool REPLAY, int MODE>\n__global__ __launch_bounds__(256, 1) void lin64_jump_kernel(const Pot64JumpArgs a, const PotModel mdl, const PotLinear lin) {\n";
+  s += "  const LinXP xp{lin};\n#include \"dense_pot64_jump.inc\"\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
+// [0, 6): float32-state jump kernels (mode * 2 + replay), [6, 12): float64-state ones, 12: eval, 13: leap
+std::vector<std::string> linear_kernel_names(int NB) {
+  const std::string nb = std::to_string(NB);
+  std::vector<std::string> n;
+  for (const char* k : {"lin_jump_kernel", "lin64_jump_kernel"})
+    for (int mode = 0; mode < 3; ++mode)
+      for (int replay = 0; replay < 2; ++replay)
+        n.push_back(std::string("mjhmc::") + k + "<" + nb + ", " + (replay ? "true" : "false") + ", " + std::to_string(mode) + ">");
+  n.push_back("mjhmc::lin_eval_kernel<" + nb + ">");
+  n.push_back("mjhmc::lin_leap_kernel<" + nb + ">");
+  return n;
+}
+
+}  // namespace
+
+int linear_dim(int ndims, int nexperts) {
+  const int m = ndims > nexperts ? ndims : nexperts;
+  return m <= 128 ? 128 : (m <= 256 ? 256 : (m <= kPotDim ? kPotDim : 0));
+}
+
+int linear_check_args(int ndims, int nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
+  if (!energy_expr || !grad_expr || !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (ndims < 1 || nexperts < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "LINEAR_EXPR needs ndims >= 1 and nexperts >= 1");
+  if (!linear_dim(ndims, nexperts))
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "LINEAR_EXPR runs on the register-resident tile kernels: ndims and nexperts must "
+                                             "be at most 512 (got " + std::to_string(ndims) + " x " + std::to_string(nexperts) +
+                                             "); there is no blocked form for wider models");
+  return 0;
+}
+
+int linear_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
+                   std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered) {
+  const int NB = dim / 128;
+  const std::string src = linear_source(energy_expr, grad_expr);
+  const std::string key = src + "\n// NB = " + std::to_string(NB) + ", -I" + include_dir;
+  std::lock_guard<std::mutex> lk(g_cache_mu);   // (one compile at a time: a second thread asking for the same code waits for it)
+  auto it = g_cache.find(key);
+  if (it == g_cache.end()) {
+    std::unique_ptr<Compiled> c(new Compiled());
+    const int rc = rtc_compile(src, "mjhmc_linear_energy.hip", include_dir, linear_kernel_names(NB), &c->code, &c->lowered, err);
+    if (rc) return rc;
+    it = g_cache.emplace(key, std::move(c)).first;
+  }
+  *code = &it->second->code;
+  *lowered = &it->second->lowered;
+  return 0;
+}
+
+int linear_energy_build(mjhmc_energy* e, int nexperts, const double* W, const double* b, const char* energy_expr,
+                        const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
+                        int n_expert_rows, const char* include_dir) {
+  const int D = e->ep.ndims, K = nexperts, DIM = linear_dim(D, K);
+  LinearEnergy* l = new LinearEnergy();
+  e->lin = l;
+  const std::vector<char>* code = nullptr;
+  const std::vector<std::string>* lowered = nullptr;
+  std::string err;
+  const int rc = linear_compile(energy_expr, grad_expr, DIM, include_dir, &err, &code, &lowered);
+  if (rc) return mjhmc_fail(rc, err);
+  HIPCHK(hipModuleLoadData(&l->module, code->data()));
+  for (int k = 0; k < 12; ++k) {
+    hipFunction_t* f = k < 6 ? &l->gen.jump32[k / 2][k % 2] : &l->gen.jump64[(k - 6) / 2][k % 2];
+    HIPCHK(hipModuleGetFunction(f, l->module, (*lowered)[(size_t)k].c_str()));
+  }
+  HIPCHK(hipModuleGetFunction(&l->gen.eval, l->module, (*lowered)[12].c_str()));
+  HIPCHK(hipModuleGetFunction(&l->gen.leap, l->module, (*lowered)[13].c_str()));
+
+  // the model in ProductOfT's layout, float32 (W1 = W^T: u = W1^T x + cb; W2T = W: dE/dx = W2T^T phi(u))
+  e->pot_dim = DIM;
+  e->pot_rows = D > K ? D : K;
+  const size_t M = (size_t)DIM * DIM, nrows = (size_t)4 * DIM + (nparams ? nparams : 1);
+  std::vector<float> w1(M, 0.f), w2t(M, 0.f), cb(DIM, 0.f), rows(nrows, 0.f);
+  for (int j = 0; j < K; ++j) {
+    cb[j] = (float)b[j];
+    for (int d = 0; d < D; ++d) {
+      const float w = (float)W[(size_t)j * D + d];
+      w1[(size_t)d * DIM + j] = w;
+      w2t[(size_t)j * DIM + d] = w;
+    }
+  }
+  for (int m = 0; m < n_expert_rows; ++m)
+    for (int j = 0; j < K; ++j) rows[(size_t)m * DIM + j] = (float)expert_params[(size_t)m * K + j];
+  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * DIM + k] = (float)params[k];
+  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
+  const size_t bytes[3] = {M * 4, M * 4, (size_t)DIM * 4};
+  for (int i = 0; i < 3; ++i) {
+    HIPCHK(hipMalloc((void**)&e->pot[i], bytes[i]));
+    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
+  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
+  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * DIM, K, DIM};
+  return 0;
+}
+
+void linear_energy_free(mjhmc_energy* e) {
+  if (!e->lin) return;
+  if (e->lin->rows) (void)hipFree(e->lin->rows);
+  if (e->lin->module) (void)hipModuleUnload(e->lin->module);
+  delete e->lin;
+  e->lin = nullptr;
+}

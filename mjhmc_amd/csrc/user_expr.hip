@@ -162,19 +162,18 @@ std::vector<std::string> user_expr_kernel_names(int E) {
   return n;
 }
 
-int user_expr_compile(const std::string& src, const std::string& include_dir, int E, std::vector<char>* code,
-                      std::vector<std::string>* lowered, std::string* err) {
+int rtc_compile(const std::string& src, const char* file_name, const std::string& include_dir, const std::vector<std::string>& names,
+                std::vector<char>* code, std::vector<std::string>* lowered, std::string* err) {
   Rtc& r = rtc();
   if (!r.err.empty()) {
     *err = r.err;
     return MJHMC_ERR_HIP;
   }
   hiprtcProgram prog;
-  if (r.CreateProgram(&prog, src.c_str(), "mjhmc_user_energy.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+  if (r.CreateProgram(&prog, src.c_str(), file_name, 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
     *err = "hiprtcCreateProgram failed";
     return MJHMC_ERR_HIP;
   }
-  const std::vector<std::string> names = user_expr_kernel_names(E);
   for (const std::string& n : names) r.AddNameExpression(prog, n.c_str());
   const std::string inc = "-I" + include_dir;
   // the library's own build flags (csrc/Makefile): the leapfrog update rounds like the reference's NumPy expression
@@ -206,6 +205,11 @@ int user_expr_compile(const std::string& src, const std::string& include_dir, in
   r.GetCode(prog, code->data());
   r.DestroyProgram(&prog);
   return 0;
+}
+
+int user_expr_compile(const std::string& src, const std::string& include_dir, int E, std::vector<char>* code,
+                      std::vector<std::string>* lowered, std::string* err) {
+  return rtc_compile(src, "mjhmc_user_energy.hip", include_dir, user_expr_kernel_names(E), code, lowered, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -22,6 +22,9 @@ struct UserEnergy {
 std::string user_expr_source(const std::string& energy_expr, const std::string& grad_expr, const std::string& stats = "",
                              const std::string& energy0_expr = "");
 std::vector<std::string> user_expr_kernel_names(int E);
+// hipRTC with the library's build flags; `names`: name expressions whose lowered names are returned in *lowered
+int rtc_compile(const std::string& src, const char* file_name, const std::string& include_dir, const std::vector<std::string>& names,
+                std::vector<char>* code, std::vector<std::string>* lowered, std::string* err);
 int user_expr_compile(const std::string& src, const std::string& include_dir, int E, std::vector<char>* code,
                       std::vector<std::string>* lowered, std::string* err);
 

@@ -77,6 +77,27 @@ class Context(object):
         return which
 
 
+def linear_arrays(W, b, params=(), expert_params=None):
+    """The checked float64 arrays of a linear-model energy: W (K, D), b (K,), params (n,), expert_params (M <= 4, K).
+    Raises ValueError on a shape the device form does not take (before any device call)."""
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+        raise ValueError('W must be a (K, D) matrix, got shape %r' % (W.shape,))
+    K, D = W.shape
+    if K > 512 or D > 512:
+        raise ValueError('linear-model energies take at most 512 experts and 512 dims (W is %d x %d)' % (K, D))
+    b = np.ascontiguousarray(np.zeros(K) if b is None else b, dtype=np.float64)
+    if b.shape != (K,):
+        raise ValueError('b must have one entry per row of W (%d), got shape %r' % (K, b.shape))
+    params = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel())
+    q = np.zeros((0, K)) if expert_params is None else np.asarray(expert_params, dtype=np.float64)
+    if q.ndim == 1:
+        q = q.reshape(1, -1)
+    if q.ndim != 2 or q.shape[1] != K or q.shape[0] > 4:
+        raise ValueError('expert_params must be (M <= 4, K = %d), got shape %r' % (K, q.shape))
+    return W, b, params, np.ascontiguousarray(q)
+
+
 def context(device=0):
     """Process-wide context per device index."""
     if device not in _contexts:
@@ -115,6 +136,27 @@ class DeviceEnergy(object):
             ctx.handle, self.ndims, ';'.join(str(t) for t in stats).encode() if stats else None, str(energy_expr).encode(),
             str(energy0_expr).encode() if energy0_expr else None, str(grad_expr).encode(),
             ptr(self.params) if self.params.size else None, self.params.size, _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
+        self.handle = h
+        return self
+
+    @classmethod
+    def from_linear(cls, ctx, W, b, energy_expr, grad_expr, params=(), expert_params=None):
+        """A linear-model energy on the ProductOfT matrix-core tile kernels (mjhmc_energy_create_linear,
+        include/mjhmc_hip.h):  E(x) = sum_j f(u_j, j),  u = W x + b,  dE/dx = W^T f'(u);  W (K, D), b (K,), f / f'
+        C expressions of ``u``, ``j``, ``p[k]`` (``params``) and ``q[m]`` (row m of ``expert_params``, (M <= 4, K)),
+        evaluated in float32.  1 <= D, K <= 512."""
+        W, b, params, q = linear_arrays(W, b, params, expert_params)
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.kind = _lib.E_LINEAR_EXPR
+        self.nexperts, self.ndims = W.shape
+        self.params = params
+        self.W, self.b, self.expert_params = W, b, q
+        h = ctypes.c_void_p()
+        check(ctx.lib.mjhmc_energy_create_linear(
+            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), str(energy_expr).encode(), str(grad_expr).encode(),
+            ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
+            _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
         self.handle = h
         return self
 

@@ -47,6 +47,10 @@ class Distribution(object):
             kind, params = self.device_energy()
             if kind == _lib.E_USER_EXPR:                   # params = (energy_expr, grad_expr, float64 parameters, stats, energy0_expr)
                 self._dev = engine.DeviceEnergy.from_expr(engine.context(device), self.ndims, *params)
+            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=)
+                self._dev = engine.DeviceEnergy.from_linear(engine.context(device), params['W'], params.get('b'),
+                                                            params['energy'], params['grad'], params.get('params', ()),
+                                                            params.get('expert_params'))
             elif kind == _lib.E_HOST:                      # params = (energy_func, energy_grad_func): opaque callables
                 self._dev = engine.DeviceEnergy.host(engine.context(device), self.ndims, *params)
             else:
@@ -155,18 +159,37 @@ class LambdaDistribution(Distribution):
       Coupled coordinates: ``device_expr=dict(stats=[...], energy=..., energy0=..., grad=...)`` -- the ``stats``
       expressions are summed over a particle's coordinates into ``S[k]``, which the other expressions may use:
       ``E = energy0(S) + sum_d energy(x_d, d, S)``, ``dE/dx_d = grad(x_d, d, S)`` (mjhmc_energy_create_expr_coupled);
+    * ``device_linear=dict(W=, b=, energy=, grad=, params=(), expert_params=None)``: a linear-model energy
+      ``E(x) = sum_j energy(u_j, j)``, ``u = W x + b`` (W (K, D), K, D <= 512), ``dE/dx = W^T grad(u)``, with ``energy`` /
+      ``grad`` C expressions of ``u``, ``j``, ``p[k]`` (``params``) and ``q[m]`` (row m of ``expert_params``) evaluated in
+      float32 on the ProductOfT matrix-core tile kernels (mjhmc_energy_create_linear).  ``state_dtype``: 'float64'
+      (default: float64 state around the float32 force, as ProductOfT) or 'float32'.  Callables given as well are checked
+      against the device energy at bind time at a float32-force bar: ``|dE| <= 1e-4 (1 + |E|)`` and
+      ``max |d grad| <= 1e-4 max(1, max |grad|)`` on a few probe points;
     * ``device_energy=(kind, params)``: one of the built-in device energies by name.
     """
 
     def __init__(self, energy_func=None, energy_grad_func=None, init=None, name=None, device_energy=None,
-                 device_expr=None, device_params=()):
+                 device_expr=None, device_params=(), device_linear=None, state_dtype='float64'):
         self.energy_func = energy_func
         self.energy_grad_func = energy_grad_func
         self.init = np.array(init, dtype=np.float64)
         self.name = name or str(np.random.random())
         self._functor = device_energy
         self._checked = False
-        if device_expr is not None:
+        self._bar32 = False
+        if device_linear is not None:
+            if state_dtype not in ('float32', 'float64'):
+                raise ValueError("device_linear state_dtype must be 'float32' or 'float64'")
+            self.state_dtype = state_dtype
+            lin = dict(device_linear)
+            W, b, params, q = engine.linear_arrays(lin['W'], lin.get('b'), lin.get('params', ()), lin.get('expert_params'))
+            if W.shape[1] != self.init.shape[0]:
+                raise ValueError('W has %d columns but init has %d dims' % (W.shape[1], self.init.shape[0]))
+            self._functor = (_lib.E_LINEAR_EXPR, dict(W=W, b=b, energy=str(lin['energy']), grad=str(lin['grad']),
+                                                      params=params, expert_params=q))
+            self._bar32 = True
+        elif device_expr is not None:
             if isinstance(device_expr, dict):              # coupled through per-particle statistics S[k]
                 e_expr, g_expr = device_expr['energy'], device_expr['grad']
                 stats = device_expr.get('stats', ())
@@ -198,7 +221,12 @@ class LambdaDistribution(Distribution):
             E, G = dev.eval(P)
             e = np.asarray(self.energy_func(P), dtype=np.float64).reshape(-1)
             g = np.asarray(self.energy_grad_func(P), dtype=np.float64)
-            if not (np.allclose(E, e, rtol=1e-9, atol=1e-12) and np.allclose(G, g, rtol=1e-9, atol=1e-12)):
+            if self._bar32:      # float32 force (device_linear): the bar of the docstring
+                ok = (np.all(np.abs(E - e) <= 1e-4 * (1 + np.abs(e))) and
+                      np.abs(G - g).max() <= 1e-4 * max(1.0, np.abs(g).max()))
+            else:
+                ok = np.allclose(E, e, rtol=1e-9, atol=1e-12) and np.allclose(G, g, rtol=1e-9, atol=1e-12)
+            if not ok:
                 raise ValueError('LambdaDistribution %r: the device energy disagrees with energy_func / '
                                  'energy_grad_func (max |dE| %g, max |d grad| %g)'
                                  % (self.name, np.abs(E - e).max(), np.abs(G - g).max()))
@@ -347,6 +375,62 @@ class Funnel(Distribution):
 
     def __hash__(self):
         return hash((self.scale, self.ndims))
+
+
+class CorrelatedGaussian(Distribution):
+    """Gaussian with a dense covariance, E = 1/2 (x - mu)^T A (x - mu), A = cov^-1 the precision, on the ProductOfT
+    matrix-core tile kernels as a linear-model energy (mjhmc_energy_create_linear): W = L^T and b = -L^T mu for the
+    Cholesky factor A = L L^T, f(u) = u^2 / 2, f'(u) = u (float32 force).  Give ``cov`` or ``precision`` (D x D,
+    D <= 512); with neither, a seeded random rotation of a spectrum spanning 10^log_conditioning.
+    ``state_dtype``: 'float64' (default, float64 state around the float32 force) or 'float32'.  ``gen_init_X`` draws
+    exactly from N(mu, cov)."""
+
+    def __init__(self, cov=None, precision=None, mean=None, ndims=None, nbatch=100, state_dtype='float64',
+                 log_conditioning=2, seed=0):
+        if state_dtype not in ('float32', 'float64'):
+            raise ValueError("CorrelatedGaussian state_dtype must be 'float32' or 'float64'")
+        if cov is not None and precision is not None:
+            raise ValueError('give cov or precision, not both')
+        if cov is None and precision is None:
+            D = 2 if ndims is None else int(ndims)
+            rs = np.random.RandomState(seed)
+            Q, R = np.linalg.qr(rs.randn(D, D))
+            Q = Q * np.sign(np.diag(R))
+            spec = 10.0 ** np.linspace(-log_conditioning / 2.0, log_conditioning / 2.0, D)
+            cov = (Q * spec) @ Q.T
+        if precision is None:
+            cov = np.array(cov, dtype=np.float64)
+            precision = np.linalg.inv(cov)
+        else:
+            precision = np.array(precision, dtype=np.float64)
+            cov = np.linalg.inv(precision)
+        if precision.ndim != 2 or precision.shape[0] != precision.shape[1]:
+            raise ValueError('cov / precision must be square, got shape %r' % (precision.shape,))
+        D = precision.shape[0]
+        precision = (precision + precision.T) / 2
+        cov = (cov + cov.T) / 2
+        self.mean = np.zeros(D) if mean is None else np.array(mean, dtype=np.float64).reshape(D)
+        self.cov, self.precision = cov, precision
+        self.L = np.linalg.cholesky(precision)           # A = L L^T
+        self.state_dtype = state_dtype
+        self.backend = 'hip-mfma'
+        super(CorrelatedGaussian, self).__init__(D, nbatch)
+
+    def device_energy(self):
+        W = self.L.T
+        return (_lib.E_LINEAR_EXPR, dict(W=W, b=-W @ self.mean, energy='0.5f*u*u', grad='u', params=(),
+                                         expert_params=None))
+
+    def gen_init_X(self):
+        C = np.linalg.cholesky(self.cov)
+        self.Xinit = self.mean.reshape(-1, 1) + C @ np.random.randn(self.ndims, self.nbatch)
+
+    def __hash__(self):
+        import hashlib
+        h = hashlib.sha1()
+        for a in (self.precision, self.mean):
+            h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        return int(h.hexdigest()[:15], 16)
 
 
 class ProductOfT(Distribution):

@@ -97,6 +97,12 @@ def stable_digest(distribution):
             if isinstance(part, (list, tuple)):
                 part = ';'.join(str(t) for t in part)
             h.update(part.encode() if isinstance(part, str) else np.ascontiguousarray(part, dtype=np.float64).tobytes())
+    elif isinstance(params, dict):     # linear-model energies: matrices, expressions and parameters by name
+        for key in sorted(params):
+            v = params[key]
+            h.update(key.encode())
+            if v is not None:
+                h.update(v.encode() if isinstance(v, str) else np.ascontiguousarray(v, dtype=np.float64).tobytes())
     elif isinstance(params, (tuple, list)) and any(callable(q) for q in params):
         # opaque callables (LambdaDistribution on MJHMC_E_HOST): no bytes to hash -- the name the distribution was given
         # stands for them, as in Distribution.__hash__ of the reference (distributions.py:247-251)
