@@ -83,6 +83,12 @@ static int ab_flags() {
          (test_env("MJHMC_NO_RELAY") ? kAbNoRelay : 0) | (test_env("MJHMC_FORCE_RELAY") ? kAbForceRelay : 0);
 }
 
+// the Philox key of RNG tick `tick` (tick 0: the initial momenta of an evaluation)
+static RngKey rng_key(const mjhmc_sampler* s, uint64_t tick) {
+  return RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), (uint32_t)(tick & 0xFFFFFFFFu),
+                (uint32_t)(tick >> 32)};
+}
+
 static int ilog2(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -356,123 +362,34 @@ __global__ __launch_bounds__(1024) void compact_list_kernel(const Pred pred, int
 // ---------------------------------------------------------------------------------------------
 // dispatch over energies / dtypes
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-static int dispatch_jump(int kind, const JumpArgs<T>& a, const EnergyParams& ep, int E, hipStream_t st);
+// the launchers of one elementwise energy (elementwise.hpp: MJHMC_DEFINE_ENERGY_LAUNCHERS), overloaded on the argument block
+#define MJHMC_ENERGY_LAUNCHERS(NAME)                                               \
+  struct NAME##_launchers {                                                        \
+    template <class... A> static void jump(const A&... a) { NAME##_jump(a...); }  \
+    template <class... A> static void leap(const A&... a) { NAME##_leap(a...); }  \
+    template <class... A> static void step(const A&... a) { NAME##_step(a...); }  \
+    template <class... A> static void eval(const A&... a) { NAME##_eval(a...); }  \
+  };
+MJHMC_ENERGY_LAUNCHERS(iso)
+MJHMC_ENERGY_LAUNCHERS(diag)
+MJHMC_ENERGY_LAUNCHERS(rough)
+MJHMC_ENERGY_LAUNCHERS(mm)
+MJHMC_ENERGY_LAUNCHERS(funnel_neal)
+MJHMC_ENERGY_LAUNCHERS(funnel_ref)
+#undef MJHMC_ENERGY_LAUNCHERS
 
-template <>
-int dispatch_jump<double>(int kind, const JumpArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {
+// launch(en) with the launchers of energy `kind`, e.g. with_elementwise_energy(kind, [&](auto en) { en.jump(a, ep, E, st); })
+template <class F>
+static int with_elementwise_energy(int kind, F&& launch) {
   switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_jump_f64(a, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_jump_f64(a, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_jump_f64(a, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_jump_f64(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_jump_f64(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_jump_f64(a, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no fused jump kernel yet");
+    case MJHMC_E_ISO_GAUSS: launch(iso_launchers{}); return 0;
+    case MJHMC_E_DIAG_GAUSS: launch(diag_launchers{}); return 0;
+    case MJHMC_E_ROUGH_WELL: launch(rough_launchers{}); return 0;
+    case MJHMC_E_MM_GAUSS: launch(mm_launchers{}); return 0;
+    case MJHMC_E_FUNNEL_NEAL: launch(funnel_neal_launchers{}); return 0;
+    case MJHMC_E_FUNNEL_REF: launch(funnel_ref_launchers{}); return 0;
+    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no elementwise kernels");
   }
-  return 0;
-}
-template <>
-int dispatch_jump<float>(int kind, const JumpArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_jump_f32(a, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_jump_f32(a, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_jump_f32(a, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_jump_f32(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_jump_f32(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_jump_f32(a, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no fused jump kernel yet");
-  }
-  return 0;
-}
-
-template <typename T>
-static int dispatch_leap(int kind, const LeapArgs<T>& a, const EnergyParams& ep, int E, hipStream_t st);
-template <>
-int dispatch_leap<double>(int kind, const LeapArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_leap_f64(a, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_leap_f64(a, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_leap_f64(a, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_leap_f64(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_leap_f64(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_leap_f64(a, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "the stand-alone leapfrog operator exists for the elementwise energies");
-  }
-  return 0;
-}
-template <>
-int dispatch_leap<float>(int kind, const LeapArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_leap_f32(a, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_leap_f32(a, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_leap_f32(a, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_leap_f32(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_leap_f32(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_leap_f32(a, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "the stand-alone leapfrog operator exists for the elementwise energies");
-  }
-  return 0;
-}
-
-template <typename T>
-static int dispatch_step(int kind, const TrajArgs<T>* ta, const JumpDecideArgs<T>* da, const EnergyParams& ep, int E, hipStream_t st);
-template <>
-int dispatch_step<double>(int kind, const TrajArgs<double>* ta, const JumpDecideArgs<double>* da, const EnergyParams& ep, int E,
-                          hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_step_f64(ta, da, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_step_f64(ta, da, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_step_f64(ta, da, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_step_f64(ta, da, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_step_f64(ta, da, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_step_f64(ta, da, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no trajectory / jump-process kernel");
-  }
-  return 0;
-}
-template <>
-int dispatch_step<float>(int kind, const TrajArgs<float>* ta, const JumpDecideArgs<float>* da, const EnergyParams& ep, int E,
-                         hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_step_f32(ta, da, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_step_f32(ta, da, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_step_f32(ta, da, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_step_f32(ta, da, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_step_f32(ta, da, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_step_f32(ta, da, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no trajectory / jump-process kernel");
-  }
-  return 0;
-}
-
-template <typename T>
-static int dispatch_eval(int kind, const EvalArgs<T>& a, const EnergyParams& ep, int E, hipStream_t st);
-template <>
-int dispatch_eval<double>(int kind, const EvalArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_eval_f64(a, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_eval_f64(a, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_eval_f64(a, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_eval_f64(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_eval_f64(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_eval_f64(a, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no evaluation kernel yet");
-  }
-  return 0;
-}
-template <>
-int dispatch_eval<float>(int kind, const EvalArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {
-  switch (kind) {
-    case MJHMC_E_ISO_GAUSS: iso_eval_f32(a, ep, E, st); break;
-    case MJHMC_E_DIAG_GAUSS: diag_eval_f32(a, ep, E, st); break;
-    case MJHMC_E_ROUGH_WELL: rough_eval_f32(a, ep, E, st); break;
-    case MJHMC_E_MM_GAUSS: mm_eval_f32(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_NEAL: funnel_neal_eval_f32(a, ep, E, st); break;
-    case MJHMC_E_FUNNEL_REF: funnel_ref_eval_f32(a, ep, E, st); break;
-    default: return fail(MJHMC_ERR_UNSUPPORTED, "energy kind has no evaluation kernel yet");
-  }
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -761,63 +678,61 @@ static int run_eval_t(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, c
   a.pitch = s->sh.pitch;
   a.CH = s->sh.CH;
   a.logG = s->sh.logG;
-  a.key = RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), 0u, 0u};
+  a.key = rng_key(s, 0);
   if constexpr (sizeof(T) == 8) {
     if (s->en->is_user()) return user_launch_eval(s->en, a, s->stream);
   }
-  TRY(dispatch_eval<T>(s->en->ep.kind, a, s->en->ep, s->sh.E, s->stream));
+  TRY(with_elementwise_energy(s->en->ep.kind, [&](auto en) { en.eval(a, s->en->ep, s->sh.E, s->stream); }));
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-static int run_eval_pot(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen,
-                        void* EVout) {
-  PotEvalArgs a;
-  a.X = (const float*)X;
-  a.G = (float*)Gout;
-  a.E = (float*)Eout;
-  a.EV = (float*)EVout;
-  a.V = (const float*)V;
-  a.V_gen = (float*)Vgen;
-  a.N = s->N;
-  a.ntiles = s->Npad / 32;
-  a.first_pid = s->first_pid;
-  a.D = s->D;
-  a.key = RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), 0u, 0u};
-  pot_launch_eval(a, s->en->pot_model(), s->stream, s->en->pot_gen());
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <typename ST>
-static int run_eval_sic_t(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen,
-                          void* EVout) {
-  SicEvalArgsT<ST> a;
-  a.X = (const ST*)X;
-  a.G = (float*)Gout;  // float32 [Npad][1024]
-  a.E = (float*)Eout;
-  a.EV = (float*)EVout;
-  a.V = (const ST*)V;
-  a.V_gen = (ST*)Vgen;
-  a.N = s->N;
+// tiles of a dense launch over particles [0, N) of rows [0, Npad): 32 rows a tile (ProductOfT), whole particles of P
+// rows each (SparseImageCode)
+static int64_t dense_ntiles(const mjhmc_sampler* s, int64_t N, int64_t Npad) {
+  if (!s->en->is_sic()) return Npad / 32;
   const int ppt = sic_particles_per_tile(s->en->sic_P);
-  a.ntiles = (s->N + ppt - 1) / ppt;
+  return (N + ppt - 1) / ppt;
+}
+
+// one part of an iteration of a dense batch: the tile kernel of the energy and the state's type
+template <typename S, typename H, bool POT>
+static void launch_dense_jump(const mjhmc_sampler* s, const DenseJumpArgs<S, H, POT>& a, hipStream_t st) {
+  if constexpr (!POT) sic_launch_jump(a, s->en->sic_model(), st);
+  else if constexpr (sizeof(S) == 8) pot64_launch_jump(a, s->en->pot_model(), st, s->en->pot_gen());
+  else pot_launch_jump(a, s->en->pot_model(), st, s->en->pot_gen());
+}
+
+template <typename S, bool POT>
+static int run_eval_dense(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen, void* EVout) {
+  DenseEvalArgs<S, POT> a{};
+  a.X = (const S*)X;
+  a.G = (float*)Gout;  // (SparseImageCode: float32 [Npad][1024])
+  a.E = (float*)Eout;
+  a.EV = (float*)EVout;
+  a.V = (const S*)V;
+  a.V_gen = (S*)Vgen;
+  a.N = s->N;
+  a.ntiles = dense_ntiles(s, s->N, s->Npad);
   a.first_pid = s->first_pid;
-  a.key = RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), 0u, 0u};
-  sic_launch_eval(a, s->en->sic_model(), s->stream);
+  a.key = rng_key(s, 0);
+  if constexpr (POT) {
+    a.D = s->D;
+    pot_launch_eval(a, s->en->pot_model(), s->stream, s->en->pot_gen());
+  } else {
+    sic_launch_eval(a, s->en->sic_model(), s->stream);
+  }
   HIPCHK(hipGetLastError());
   return 0;
-}
-static int run_eval_sic(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen, void* EVout) {
-  return s->dtype == MJHMC_BF16 ? run_eval_sic_t<__bf16>(s, X, Gout, Eout, V, Vgen, EVout)
-                                : run_eval_sic_t<float>(s, X, Gout, Eout, V, Vgen, EVout);
 }
 
 static int run_eval(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen, void* EVout) {
   // host energies (E and dE/dX are the caller's, mjhmc_host_set_energy) and wide rows (multi-pass device kernels)
   if (s->en->is_host() || s->sh.wide) return wide_run_eval(s, X, Gout, Eout, V, Vgen, EVout);
-  if (s->en->is_pot()) return run_eval_pot(s, X, Gout, Eout, V, Vgen, EVout);
-  if (s->en->is_sic()) return run_eval_sic(s, X, Gout, Eout, V, Vgen, EVout);
+  if (s->en->is_pot()) return run_eval_dense<float, true>(s, X, Gout, Eout, V, Vgen, EVout);
+  // (the state's type of SparseImageCode: bfloat16, BASELINE.json configs[4], or float32, the reference's TensorFlow float32)
+  if (s->en->is_sic()) return s->dtype == MJHMC_BF16 ? run_eval_dense<__bf16, false>(s, X, Gout, Eout, V, Vgen, EVout)
+                                                    : run_eval_dense<float, false>(s, X, Gout, Eout, V, Vgen, EVout);
   return s->dtype == MJHMC_F64 ? run_eval_t<double>(s, X, Gout, Eout, V, Vgen, EVout)
                                : run_eval_t<float>(s, X, Gout, Eout, V, Vgen, EVout);
 }
@@ -1407,6 +1322,12 @@ static void fill_iter_stats(const mjhmc_sampler* s, const std::vector<long long>
   }
 }
 
+// the tile kernels' argument blocks (elementwise.hpp), apart from the elementwise energies' JumpArgs<T>
+template <class A>
+struct IsDenseJump : std::false_type {};
+template <typename S, typename H, bool POT>
+struct IsDenseJump<DenseJumpArgs<S, H, POT>> : std::true_type {};
+
 // Elementwise energies, counter RNG, n_iter >= 2: launches of up to kMaxFuse FUSED iterations.  A launch reads
 // the state buffers of one parity and writes the other, so its input survives it: when some particle meets a
 // non-finite rate at iteration f (the reference aborts the WHOLE batch there, markov_jump_hmc.py:376-389) the
@@ -1427,10 +1348,11 @@ static void fill_iter_stats(const mjhmc_sampler* s, const std::vector<long long>
 // every iteration boundary (the first form of this) kept 1.5 % / 4 %: the dispatcher hands free CUs to the pending
 // workgroups of the OLDEST dispatch first, a persistent grid of one workgroup per CU shuts out even a one-block memset
 // until a workgroup exits, and a boundary at which both halves wait for each other is a drain again.
-// part `which` of a dense batch: particles [start, start + n), their rows of every per-particle array, their stretch of the
-// lists, their own three rotating counters (iteration i reads slot i % 3, appends to (i + 1) % 3, clears (i + 2) % 3)
-template <class A, typename S>
-static A part_args(const A& a, int64_t start, int64_t n, int64_t npad, size_t pitch, int which, int iter, int* counters) {
+// part `which` of a split batch: particles [start, start + n), their rows of every per-particle array; of a dense batch
+// also their stretch of the lists and their own three rotating counters (iteration i reads slot i % 3, appends to
+// (i + 1) % 3, clears (i + 2) % 3)
+template <class A>
+static A part_args(const A& a, int64_t start, int64_t n, int64_t npad, size_t pitch, int which, int* counters) {
   A h = a;
   h.X_in = a.X_in + (size_t)start * pitch;
   h.V_in = a.V_in + (size_t)start * pitch;
@@ -1439,26 +1361,28 @@ static A part_args(const A& a, int64_t start, int64_t n, int64_t npad, size_t pi
   h.EX_in = a.EX_in + start;
   h.EV_in = a.EV_in + start;
   h.Hflf_in = a.Hflf_in + start;
-  h.Hspec_in = a.Hspec_in + start;
-  h.Hwork = a.Hwork + start;
   h.EX_out = a.EX_out + start;
   h.EV_out = a.EV_out + start;
   h.Hflf_out = a.Hflf_out + start;
-  h.Hspec_out = a.Hspec_out + start;
   h.dwell = a.dwell + start;
   h.dwell_ring = a.dwell_ring + start;
   h.trans = a.trans + start;
-  h.cold_list = a.cold_list + start;
-  h.next_list = a.next_list + start;
-  h.cold_count = counters + 3 * which + iter % 3;
-  h.next_count = counters + 3 * which + (iter + 1) % 3;
-  h.zero_count = counters + 3 * which + (iter + 2) % 3;
-  if constexpr (std::is_same<A, Pot64JumpArgs>::value || std::is_same<A, PotJumpArgs>::value) {
-    h.G_in = a.G_in + (size_t)start * pitch;
-    h.G_out = a.G_out + (size_t)start * pitch;
+  if constexpr (IsDenseJump<A>::value) {
+    h.Hspec_in = a.Hspec_in + start;
+    h.Hwork = a.Hwork + start;
+    h.Hspec_out = a.Hspec_out + start;
+    h.cold_list = a.cold_list + start;
+    h.next_list = a.next_list + start;
+    h.cold_count = counters + 3 * which + a.iter % 3;
+    h.next_count = counters + 3 * which + (a.iter + 1) % 3;
+    h.zero_count = counters + 3 * which + (a.iter + 2) % 3;
+    if constexpr (A::kPot) {
+      h.G_in = a.G_in + (size_t)start * pitch;
+      h.G_out = a.G_out + (size_t)start * pitch;
+    }
+    if constexpr (A::kScratch)  // the float64 tile kernel's working rows: one set per concurrent launch
+      h.scratch = a.scratch + (size_t)which * pot64_scratch_workgroups() * 2 * 32 * (size_t)pitch;
   }
-  if constexpr (std::is_same<A, Pot64JumpArgs>::value)   // the tile kernel's working rows: one set per concurrent launch
-    h.scratch = a.scratch + (size_t)which * pot64_scratch_workgroups() * 2 * 32 * (size_t)pitch;
   h.N = n;
   h.Npad = npad;
   h.first_pid = a.first_pid + start;
@@ -1520,22 +1444,93 @@ static int read_back_call(mjhmc_sampler* s, size_t stats_rows, Control* hc, long
   return 0;
 }
 
+// The fields every jump block of an iteration shares (JumpArgs<T>, DenseJumpArgs<S, H>): iteration `iter` of the call reads
+// X from xin, V of parity vi and the scalars of parity si, writes X to xout and the other parities, records its dwelling
+// times in ring slot ring_slot0 + iter (or a scratch vector when nothing is recorded) and its tallies in `stats`.  The
+// replay streams, the dense lists and the fused launches' fields are the caller's; the rest is left zero.
+template <class A>
+static A jump_args(const mjhmc_sampler* s, int iter, int vi, int si, const void* xin, void* xout, int ring_slot0,
+                   long long* stats) {
+  using S = std::remove_pointer_t<decltype(A::X_out)>;   // the state rows
+  using H = std::remove_pointer_t<decltype(A::EX_out)>;  // the per-particle scalars and step parameters
+  A a{};
+  a.X_in = (const S*)xin;
+  a.V_in = (const S*)s->Vbuf[vi];
+  a.X_out = (S*)xout;
+  a.V_out = (S*)s->Vbuf[vi ^ 1];
+  a.EX_in = (const H*)s->EX[si];
+  a.EV_in = (const H*)s->EV[si];
+  a.Hflf_in = (const H*)s->Hflf[si];
+  a.EX_out = (H*)s->EX[si ^ 1];
+  a.EV_out = (H*)s->EV[si ^ 1];
+  a.Hflf_out = (H*)s->Hflf[si ^ 1];
+  a.dwell = s->dwell;
+  a.dwell_ring = ring_slot0 >= 0 ? s->dwell_ring + (size_t)(ring_slot0 + iter) * s->Npad : s->dwell_scratch;
+  a.trans = s->trans;
+  a.ctl = s->ctl;
+  a.stats = (unsigned long long*)stats;
+  a.N = s->N;
+  a.Npad = s->Npad;
+  a.first_pid = s->first_pid;
+  a.L = s->L;
+  a.iter = iter;
+  a.mode = s->mode;
+  a.eps = (H)s->eps;  // (rounded once from the double expressions)
+  a.chalf = (H)(-s->eps / 2.);
+  a.r_keep = (H)std::sqrt(1. - s->beta);
+  a.r_mix = (H)std::sqrt(s->beta);
+  a.p_r = s->p_r;
+  a.p_flip = s->p_flip;
+  a.key = rng_key(s, s->tick + (uint64_t)iter);
+  if constexpr (!IsDenseJump<A>::value) {
+    a.D = s->D;
+    a.pitch = s->sh.pitch;
+    a.CH = s->sh.CH;
+    a.logG = s->sh.logG;
+    a.ab = ab_flags();
+  } else if constexpr (A::kPot) {
+    a.D = s->D;
+  }
+  return a;
+}
+
+// the live state sits in one of the ring slots [slot0, slot0 + n) about to be overwritten: move it out first
+static int move_out_of_ring(mjhmc_sampler* s, int slot0, int n) {
+  const size_t mb = mat_bytes(s);
+  const char* lo = (const char*)s->ring + (size_t)slot0 * mb;
+  if ((const char*)s->Xcur >= lo && (const char*)s->Xcur < lo + (size_t)n * mb) {
+    HIPCHK(hipMemcpyAsync(s->Xbuf[0], s->Xcur, mb, hipMemcpyDeviceToDevice, s->stream));
+    s->Xcur = s->Xbuf[0];
+  }
+  return 0;
+}
+
+// test hook MJHMC_DEBUG_POISON="iteration:particle": that particle's kinetic energy (parity si) reads NaN in that iteration
+// of the call -> its rates are not finite -> the whole-batch abort of markov_jump_hmc.py:376-389, at a chosen point of a
+// multi-iteration call.  stream_of(particle): the stream that runs the particle's part.
+template <typename T, class StreamOf>
+static int debug_poison(mjhmc_sampler* s, int iter, int si, StreamOf stream_of) {
+  const char* poison = test_env("MJHMC_DEBUG_POISON");
+  int pit = -1;
+  long long pp = -1;
+  if (!poison || std::sscanf(poison, "%d:%lld", &pit, &pp) != 2 || pit != iter || pp < 0 || pp >= s->N) return 0;
+  static const double nan64 = __builtin_nan("");
+  static const float nan32 = __builtin_nanf("");
+  const hipStream_t pst = stream_of(pp);
+  if (pst != s->stream && iter == 0) HIPCHK(hipStreamSynchronize(s->stream));  // (the fork to the parts' streams comes later)
+  HIPCHK(hipMemcpyAsync((char*)s->EV[si] + (size_t)pp * ssize(s), sizeof(T) == 8 ? (const void*)&nan64 : (const void*)&nan32,
+                        ssize(s), hipMemcpyHostToDevice, pst));
+  return 0;
+}
+
 template <typename T>
 static int iterate_fused_t(mjhmc_sampler* s, int n_iter, int ring_slot0, mjhmc_iter_stats* per_iter, int* n_done) {
   const size_t mb = mat_bytes(s);
   const int need = n_iter + kMaxFuse;  // + scratch tallies for the recovery launch
   TRY(zero_call(s, need));
 
+  if (ring_slot0 >= 0) TRY(move_out_of_ring(s, ring_slot0, n_iter));   // (a launch writes several slots while it reads xin)
   void* xin = s->Xcur;
-  if (ring_slot0 >= 0) {  // the live state sits in a slot about to be overwritten: move it out first
-    const char* lo = (const char*)s->ring + (size_t)ring_slot0 * mb;
-    const char* hi = lo + (size_t)n_iter * mb;
-    if ((const char*)xin >= lo && (const char*)xin < hi) {
-      void* spare = s->Xbuf[0];
-      HIPCHK(hipMemcpyAsync(spare, xin, mb, hipMemcpyDeviceToDevice, s->stream));
-      xin = s->Xcur = spare;
-    }
-  }
   struct Launch {
     int i0, K, vi, si;
     void* xin;
@@ -1552,55 +1547,12 @@ static int iterate_fused_t(mjhmc_sampler* s, int n_iter, int ring_slot0, mjhmc_i
     if (split_at) TRY(ensure_part_streams(s, n_parts));
   }
   auto launch = [&](const Launch& l, long long* stats) -> int {
-    JumpArgs<T> a;
-    a.X_in = (const T*)l.xin;
-    a.V_in = (const T*)s->Vbuf[l.vi];
-    a.X_out = (T*)l.xout;
-    a.V_out = (T*)s->Vbuf[l.vi ^ 1];
-    a.EX_in = (const T*)s->EX[l.si];
-    a.EV_in = (const T*)s->EV[l.si];
-    a.EX_out = (T*)s->EX[l.si ^ 1];
-    a.EV_out = (T*)s->EV[l.si ^ 1];
-    a.Hflf_in = (const T*)s->Hflf[l.si];
-    a.Hflf_out = (T*)s->Hflf[l.si ^ 1];
-    a.dwell = s->dwell;
-    a.trans = s->trans;
-    a.noise = nullptr;
-    a.rexp = nullptr;
-    a.runif = nullptr;
-    a.mode = s->mode;
-    a.ctl = s->ctl;
-    a.stats = (unsigned long long*)stats;
-    a.N = s->N;
-    a.Npad = s->Npad;
-    a.first_pid = s->first_pid;
-    a.D = s->D;
-    a.pitch = s->sh.pitch;
-    a.CH = s->sh.CH;
-    a.logG = s->sh.logG;
-    a.L = s->L;
-    a.iter = l.i0;
-    a.defer_r = 0;
+    JumpArgs<T> a = jump_args<JumpArgs<T>>(s, l.i0, l.vi, l.si, l.xin, l.xout, ring_slot0, stats);
     a.n_fuse = l.K;
-    a.ab = ab_flags();
     if (ring_slot0 >= 0) {
       a.xiter = (T*)((char*)s->ring + (size_t)(ring_slot0 + l.i0) * mb);
       a.xiter_stride = mb / sizeof(T);
-      a.dwell_ring = s->dwell_ring + (size_t)(ring_slot0 + l.i0) * s->Npad;
-    } else {
-      a.xiter = nullptr;
-      a.xiter_stride = 0;
-      a.dwell_ring = s->dwell_scratch;
     }
-    a.eps = (T)s->eps;
-    a.chalf = (T)(-s->eps / 2.);
-    a.r_keep = (T)std::sqrt(1. - s->beta);
-    a.r_mix = (T)std::sqrt(s->beta);
-    a.p_r = s->p_r;
-    a.p_flip = s->p_flip;
-    const uint64_t tick = s->tick + (uint64_t)l.i0;
-    a.key = RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), (uint32_t)(tick & 0xFFFFFFFFu),
-                   (uint32_t)(tick >> 32)};
     if (split_at > 0 && allow_split_now) {
       // several parts on as many streams: a launch is a persistent grid of one slot (here: up to 64 iterations of a
       // particle) per wave and pass, so it ends with a partial pass (C2: 100 000 slots on 4096 resident waves = 24.4
@@ -1611,34 +1563,17 @@ static int iterate_fused_t(mjhmc_sampler* s, int n_iter, int ring_slot0, mjhmc_i
       HIPCHK(hipEventRecord(s->ev_fork, s->stream));
       for (int k = 0; k < n_parts; ++k) {
         const int64_t start = (int64_t)k * split_at, stop = (k + 1 == n_parts) ? a.N : start + split_at;
-        JumpArgs<T> h = a;
-        const size_t po = (size_t)start * a.pitch;
-        h.X_in = a.X_in + po;
-        h.V_in = a.V_in + po;
-        h.X_out = a.X_out + po;
-        h.V_out = a.V_out + po;
-        h.EX_in = a.EX_in + start;
-        h.EV_in = a.EV_in + start;
-        h.EX_out = a.EX_out + start;
-        h.EV_out = a.EV_out + start;
-        h.Hflf_in = a.Hflf_in + start;
-        h.Hflf_out = a.Hflf_out + start;
-        h.dwell = a.dwell + start;
-        h.dwell_ring = a.dwell_ring + start;
-        h.trans = a.trans + start;
-        h.first_pid = a.first_pid + start;
-        h.N = stop - start;
-        h.Npad = (k + 1 == n_parts) ? a.Npad - start : split_at;
+        const JumpArgs<T> h = part_args(a, start, stop - start, (k + 1 == n_parts) ? a.Npad - start : split_at, (size_t)a.pitch, k, nullptr);
         hipStream_t q = k == 0 ? s->stream : s->part_streams[(size_t)k - 1];
         if (k > 0) HIPCHK(hipStreamWaitEvent(q, s->ev_fork, 0));
-        TRY(dispatch_jump<T>(s->en->ep.kind, h, s->en->ep, s->sh.E, q));
+        TRY(with_elementwise_energy(s->en->ep.kind, [&](auto en) { en.jump(h, s->en->ep, s->sh.E, q); }));
         if (k > 0) {
           HIPCHK(hipEventRecord(s->part_events[(size_t)k - 1], q));
           HIPCHK(hipStreamWaitEvent(s->stream, s->part_events[(size_t)k - 1], 0));
         }
       }
     } else {
-      TRY(dispatch_jump<T>(s->en->ep.kind, a, s->en->ep, s->sh.E, s->stream));
+      TRY(with_elementwise_energy(s->en->ep.kind, [&](auto en) { en.jump(a, s->en->ep, s->sh.E, s->stream); }));
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1648,18 +1583,7 @@ static int iterate_fused_t(mjhmc_sampler* s, int n_iter, int ring_slot0, mjhmc_i
     return (in != s->Xbuf[0]) ? s->Xbuf[0] : s->Xbuf[1];
   };
 
-#ifdef MJHMC_TEST_HOOKS
-  if (const char* poison = test_env("MJHMC_DEBUG_POISON")) {  // test hook, see iterate_t (fused launches: iteration 0 only)
-    int pit = -1;
-    long long pp = -1;
-    if (std::sscanf(poison, "%d:%lld", &pit, &pp) == 2 && pit == 0 && pp >= 0 && pp < s->N) {
-      static const double nan64 = __builtin_nan("");
-      static const float nan32 = __builtin_nanf("");
-      HIPCHK(hipMemcpyAsync((char*)s->EV[s->scur] + (size_t)pp * ssize(s), sizeof(T) == 8 ? (const void*)&nan64 : (const void*)&nan32,
-                            ssize(s), hipMemcpyHostToDevice, s->stream));
-    }
-  }
-#endif  // MJHMC_TEST_HOOKS
+  TRY(debug_poison<T>(s, 0, s->scur, [&](long long) { return s->stream; }));   // (fused launches: iteration 0 only)
   std::vector<Launch> launches;
   if (s->timing_on) HIPCHK(hipEventRecord(s->ev_total[0], s->stream));
   for (int i0 = 0; i0 < n_iter; i0 += kMaxFuse) {
@@ -1815,23 +1739,15 @@ static int iterate_t(mjhmc_sampler* s, int n_iter, const double* replay_normal, 
   int* const dense_counters = s->cold_list ? s->cold_list + 2 * s->Npad : nullptr;
 
   std::vector<void*> xout(n_iter);
-  void* xin = s->Xcur;
   if (s->timing_on) HIPCHK(hipEventRecord(s->ev_total[0], s->stream));
+  if (ring_slot0 >= 0) TRY(move_out_of_ring(s, ring_slot0, 1));   // (iteration i reads slot i - 1 and writes slot i)
+  void* xin = s->Xcur;
+  const void* noise = replay_normal ? s->noise : nullptr;
+  const double* rexp = replay_exp ? s->rexp : nullptr;
+  const double* runif = replay_unif ? s->runif : nullptr;
   for (int i = 0; i < n_iter; ++i) {
-    void* xo;
-    double* dring = s->dwell_scratch;
-    if (ring_slot0 >= 0) {
-      xo = (char*)s->ring + (size_t)(ring_slot0 + i) * mb;
-      dring = s->dwell_ring + (size_t)(ring_slot0 + i) * s->Npad;
-      if (xo == xin) {  // the live state sits in the slot about to be overwritten: move it out first
-        void* spare = s->Xbuf[0];
-        HIPCHK(hipMemcpyAsync(spare, xin, mb, hipMemcpyDeviceToDevice, s->stream));
-        xin = spare;
-        if (i == 0) s->Xcur = spare;
-      }
-    } else {
-      xo = (xin != s->Xbuf[0]) ? s->Xbuf[0] : s->Xbuf[1];
-    }
+    void* const xo = ring_slot0 >= 0 ? (void*)((char*)s->ring + (size_t)(ring_slot0 + i) * mb)
+                                     : (xin != s->Xbuf[0] ? s->Xbuf[0] : s->Xbuf[1]);
     xout[i] = xo;
     const int vi = (s->vcur + i) & 1, si = (s->scur + i) & 1;
     if (replay_normal) TRY(upload_matrix(s, replay_normal + (size_t)i * s->D * s->N, s->noise));
@@ -1841,229 +1757,51 @@ static int iterate_t(mjhmc_sampler* s, int n_iter, const double* replay_normal, 
     if (replay_unif)
       HIPCHK(hipMemcpyAsync(s->runif, replay_unif + (size_t)i * (2 * s->N + 1), (2 * s->N + 1) * sizeof(double),
                             hipMemcpyHostToDevice, s->stream));
-#ifdef MJHMC_TEST_HOOKS
-    if (const char* poison = test_env("MJHMC_DEBUG_POISON")) {
-      // test hook "iteration:particle": that particle's kinetic energy reads NaN in that iteration of the call -> its rates
-      // are not finite -> the whole-batch abort of markov_jump_hmc.py:376-389, at a chosen point of a multi-iteration call
-      int pit = -1;
-      long long pp = -1;
-      if (std::sscanf(poison, "%d:%lld", &pit, &pp) == 2 && pit == i && pp >= 0 && pp < s->N) {
-        static const double nan64 = __builtin_nan("");
-        static const float nan32 = __builtin_nanf("");
-        const int pk = n_parts > 1 ? (int)std::min<int64_t>(pp / part_len, n_parts - 1) : 0;
-        hipStream_t pst = part_stream(pk);
-        if (pk > 0 && i == 0) HIPCHK(hipStreamSynchronize(s->stream));  // (the fork below comes later)
-        HIPCHK(hipMemcpyAsync((char*)s->EV[si] + (size_t)pp * ssize(s), sizeof(T) == 8 ? (const void*)&nan64 : (const void*)&nan32,
-                              ssize(s), hipMemcpyHostToDevice, pst));
-      }
-    }
-#endif  // MJHMC_TEST_HOOKS
+    TRY(debug_poison<T>(s, i, si, [&](long long pp) {
+      return part_stream(n_parts > 1 ? (int)std::min<int64_t>(pp / part_len, n_parts - 1) : 0);
+    }));
     if (n_parts > 1 && i == 0) {  // the other parts' streams start from everything the first has been given so far
       HIPCHK(hipEventRecord(s->ev_fork, s->stream));
       for (int k = 1; k < n_parts; ++k) HIPCHK(hipStreamWaitEvent(part_stream(k), s->ev_fork, 0));
     }
-    JumpArgs<T> a;
-    a.X_in = (const T*)xin;
-    a.V_in = (const T*)s->Vbuf[vi];
-    a.X_out = (T*)xo;
-    a.V_out = (T*)s->Vbuf[vi ^ 1];
-    a.EX_in = (const T*)s->EX[si];
-    a.EV_in = (const T*)s->EV[si];
-    a.EX_out = (T*)s->EX[si ^ 1];
-    a.EV_out = (T*)s->EV[si ^ 1];
-    a.Hflf_in = (const T*)s->Hflf[si];
-    a.Hflf_out = (T*)s->Hflf[si ^ 1];
-    a.dwell = s->dwell;
-    a.dwell_ring = dring;
-    a.trans = s->trans;
-    a.noise = replay_normal ? (const T*)s->noise : nullptr;
-    a.rexp = replay_exp ? s->rexp : nullptr;
-    a.runif = replay_unif ? s->runif : nullptr;
-    a.mode = s->mode;
-    a.ctl = s->ctl;
-    a.stats = (unsigned long long*)(s->stats + 4 * i);
-    a.N = s->N;
-    a.Npad = s->Npad;
-    a.first_pid = s->first_pid;
-    a.D = s->D;
-    a.pitch = s->sh.pitch;
-    a.CH = s->sh.CH;
-    a.logG = s->sh.logG;
-    a.L = s->L;
-    a.iter = i;
-    a.n_fuse = 0;
-    a.defer_r = 0;
-    a.ab = ab_flags();
-    a.xiter = nullptr;
-    a.xiter_stride = 0;
-    a.eps = (T)s->eps;
-    a.chalf = (T)(-s->eps / 2.);
-    a.r_keep = (T)std::sqrt(1. - s->beta);
-    a.r_mix = (T)std::sqrt(s->beta);
-    a.p_r = s->p_r;
-    a.p_flip = s->p_flip;
-    const uint64_t tick = s->tick + (uint64_t)i;
-    a.key = RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), (uint32_t)(tick & 0xFFFFFFFFu),
-                   (uint32_t)(tick >> 32)};
-    if (s->en->is_pot()) {
-      if constexpr (sizeof(T) == 4) {
-        PotJumpArgs pa;
-        pa.X_in = a.X_in;
-        pa.V_in = a.V_in;
-        pa.G_in = (const float*)s->Gbuf[vi];
-        pa.X_out = a.X_out;
-        pa.V_out = a.V_out;
-        pa.G_out = (float*)s->Gbuf[vi ^ 1];
-        pa.EX_in = a.EX_in;
-        pa.EV_in = a.EV_in;
-        pa.Hflf_in = a.Hflf_in;
-        pa.Hwork = s->Hwork;
-        pa.cold_list = s->cold_list + (size_t)(i & 1) * s->Npad;          // iteration i reads list i & 1 ...
-        pa.next_list = s->cold_list + (size_t)((i + 1) & 1) * s->Npad;    // ... and writes the next iteration's
-        pa.Hspec_in = (const float*)s->Hspec[si];
-        pa.Hspec_out = (float*)(spec_out_override ? spec_out_override : s->Hspec[si ^ 1]);
-        pa.rescan = spec_out_override ? 1 : 0;
-        pa.EX_out = a.EX_out;
-        pa.EV_out = a.EV_out;
-        pa.Hflf_out = a.Hflf_out;
-        pa.dwell = a.dwell;
-        pa.dwell_ring = a.dwell_ring;
-        pa.trans = a.trans;
-        pa.noise = a.noise;
-        pa.rexp = a.rexp;
-        pa.runif = a.runif;
-        pa.mode = a.mode;
-        pa.p_flip = a.p_flip;
-        pa.ctl = a.ctl;
-        pa.stats = a.stats;
-        pa.N = a.N;
-        pa.Npad = a.Npad;
-        pa.ntiles = a.Npad / 32;
-        pa.first_pid = a.first_pid;
-        pa.D = a.D;
-        pa.L = a.L;
-        pa.iter = a.iter;
-        pa.eps = a.eps;
-        pa.chalf = a.chalf;
-        pa.r_keep = a.r_keep;
-        pa.r_mix = a.r_mix;
-        pa.p_r = a.p_r;
-        pa.key = a.key;
-        for (int k = 0; k < n_parts; ++k) {
-          PotJumpArgs h = part_args<PotJumpArgs, float>(pa, n_parts > 1 ? part_start(k) : 0, n_parts > 1 ? part_count(k) : s->N,
-                                                        n_parts > 1 ? part_npad(k) : s->Npad, (size_t)s->sh.pitch, k, i, dense_counters);
-          h.ntiles = h.Npad / 32;
-          pot_launch_jump(h, s->en->pot_model(), part_stream(k), s->en->pot_gen());
+    if (s->en->is_dense()) {
+      // one block of the tile kernels' arguments per part: S the state rows, H the per-particle scalars, pot: ProductOfT
+      auto launch_dense = [&](auto s_tag, auto h_tag, auto pot) {
+        using S = decltype(s_tag);
+        using H = decltype(h_tag);
+        using A = DenseJumpArgs<S, H, decltype(pot)::value>;
+        A d = jump_args<A>(s, i, vi, si, xin, xo, ring_slot0, s->stats + 4 * i);
+        d.noise = (const S*)noise;
+        d.rexp = rexp;
+        d.runif = runif;
+        if constexpr (A::kPot) {
+          d.G_in = (const S*)s->Gbuf[vi];
+          d.G_out = (S*)s->Gbuf[vi ^ 1];
         }
-      } else {
-        // the reference's arithmetic: float64 state rows streamed through the tile kernel's epilogue (dense_pot64.hip)
-        Pot64JumpArgs pa;
-        pa.X_in = (const double*)a.X_in;
-        pa.V_in = (const double*)a.V_in;
-        pa.G_in = (const double*)s->Gbuf[vi];
-        pa.X_out = (double*)a.X_out;
-        pa.V_out = (double*)a.V_out;
-        pa.G_out = (double*)s->Gbuf[vi ^ 1];
-        pa.EX_in = (const double*)a.EX_in;
-        pa.EV_in = (const double*)a.EV_in;
-        pa.Hflf_in = (const double*)a.Hflf_in;
-        pa.Hwork = (double*)s->Hwork;
-        pa.cold_list = s->cold_list + (size_t)(i & 1) * s->Npad;          // iteration i reads list i & 1 ...
-        pa.next_list = s->cold_list + (size_t)((i + 1) & 1) * s->Npad;    // ... and writes the next iteration's
-        pa.Hspec_in = (const double*)s->Hspec[si];
-        pa.Hspec_out = (double*)(spec_out_override ? spec_out_override : s->Hspec[si ^ 1]);
-        pa.rescan = spec_out_override ? 1 : 0;
-        pa.EX_out = (double*)a.EX_out;
-        pa.EV_out = (double*)a.EV_out;
-        pa.Hflf_out = (double*)a.Hflf_out;
-        pa.dwell = a.dwell;
-        pa.dwell_ring = a.dwell_ring;
-        pa.trans = a.trans;
-        pa.noise = (const double*)a.noise;
-        pa.rexp = a.rexp;
-        pa.runif = a.runif;
-        pa.scratch = s->pot64_scratch;
-        pa.mode = a.mode;
-        pa.p_flip = a.p_flip;
-        pa.ctl = a.ctl;
-        pa.stats = a.stats;
-        pa.N = a.N;
-        pa.Npad = a.Npad;
-        pa.ntiles = a.Npad / 32;
-        pa.first_pid = a.first_pid;
-        pa.D = a.D;
-        pa.L = a.L;
-        pa.iter = a.iter;
-        pa.eps = s->eps;
-        pa.chalf = -s->eps / 2.;
-        pa.r_keep = std::sqrt(1. - s->beta);
-        pa.r_mix = std::sqrt(s->beta);
-        pa.p_r = a.p_r;
-        pa.key = a.key;
+        d.Hwork = (H*)s->Hwork;
+        d.cold_list = s->cold_list + (size_t)(i & 1) * s->Npad;          // iteration i reads list i & 1 ...
+        d.next_list = s->cold_list + (size_t)((i + 1) & 1) * s->Npad;    // ... and writes the next iteration's
+        d.Hspec_in = (const H*)s->Hspec[si];
+        d.Hspec_out = (H*)(spec_out_override ? spec_out_override : s->Hspec[si ^ 1]);
+        d.rescan = spec_out_override ? 1 : 0;
+        if constexpr (A::kScratch) d.scratch = s->pot64_scratch;
         for (int k = 0; k < n_parts; ++k) {
-          Pot64JumpArgs h = part_args<Pot64JumpArgs, double>(pa, n_parts > 1 ? part_start(k) : 0, n_parts > 1 ? part_count(k) : s->N,
-                                                             n_parts > 1 ? part_npad(k) : s->Npad, (size_t)s->sh.pitch, k, i, dense_counters);
-          h.ntiles = h.Npad / 32;
-          pot64_launch_jump(h, s->en->pot_model(), part_stream(k), s->en->pot_gen());
+          A h = part_args(d, part_start(k), part_count(k), part_npad(k), (size_t)s->sh.pitch, k, dense_counters);
+          h.ntiles = dense_ntiles(s, h.N, h.Npad);
+          launch_dense_jump(s, h, part_stream(k));
         }
-      }
-    } else if (s->en->is_sic()) {
-      if constexpr (sizeof(T) == 4) {
-        auto launch_sic = [&](auto tag) {
-          using ST = decltype(tag);
-          SicJumpArgsT<ST> sa;
-          sa.X_in = (const ST*)xin;
-          sa.V_in = (const ST*)s->Vbuf[vi];
-          sa.X_out = (ST*)xo;
-          sa.V_out = (ST*)s->Vbuf[vi ^ 1];
-          sa.EX_in = a.EX_in;
-          sa.EV_in = a.EV_in;
-          sa.Hflf_in = a.Hflf_in;
-          sa.Hwork = s->Hwork;
-          sa.cold_list = s->cold_list + (size_t)(i & 1) * s->Npad;
-          sa.next_list = s->cold_list + (size_t)((i + 1) & 1) * s->Npad;
-          sa.Hspec_in = (const float*)s->Hspec[si];
-          sa.Hspec_out = (float*)(spec_out_override ? spec_out_override : s->Hspec[si ^ 1]);
-          sa.rescan = spec_out_override ? 1 : 0;
-          sa.EX_out = a.EX_out;
-          sa.EV_out = a.EV_out;
-          sa.Hflf_out = a.Hflf_out;
-          sa.dwell = a.dwell;
-          sa.dwell_ring = a.dwell_ring;
-          sa.trans = a.trans;
-          sa.noise = (const ST*)a.noise;
-          sa.rexp = a.rexp;
-          sa.runif = a.runif;
-          sa.mode = a.mode;
-          sa.p_flip = a.p_flip;
-          sa.ctl = a.ctl;
-          sa.stats = a.stats;
-          sa.N = a.N;
-          sa.Npad = a.Npad;
-          const int ppt = sic_particles_per_tile(s->en->sic_P);
-          sa.ntiles = (a.N + ppt - 1) / ppt;
-          sa.first_pid = a.first_pid;
-          sa.L = a.L;
-          sa.iter = a.iter;
-          sa.eps = a.eps;
-          sa.chalf = a.chalf;
-          sa.r_keep = a.r_keep;
-          sa.r_mix = a.r_mix;
-          sa.p_r = a.p_r;
-          sa.key = a.key;
-          for (int k = 0; k < n_parts; ++k) {
-            SicJumpArgsT<ST> h = part_args<SicJumpArgsT<ST>, ST>(sa, n_parts > 1 ? part_start(k) : 0, n_parts > 1 ? part_count(k) : s->N,
-                                                                 n_parts > 1 ? part_npad(k) : s->Npad, (size_t)s->sh.pitch, k, i,
-                                                                 dense_counters);
-            h.ntiles = (h.N + ppt - 1) / ppt;
-            sic_launch_jump(h, s->en->sic_model(), part_stream(k));
-          }
-        };
-        // the state's type: bfloat16 (BASELINE.json configs[4]) or float32 (the reference's TensorFlow float32)
-        if (s->dtype == MJHMC_BF16) launch_sic(__bf16{});
-        else launch_sic(float{});
-      }
+      };
+      // float64 state: the reference's arithmetic, float64 rows streamed through the tile kernel's epilogue (dense_pot64.hip);
+      // SparseImageCode's state: bfloat16 (BASELINE.json configs[4]) or float32 (the reference's TensorFlow float32)
+      if constexpr (sizeof(T) == 8) launch_dense(double{}, double{}, std::true_type{});
+      else if (s->en->is_pot()) launch_dense(float{}, float{}, std::true_type{});
+      else if (s->dtype == MJHMC_BF16) launch_dense(__bf16{}, float{}, std::false_type{});
+      else launch_dense(float{}, float{}, std::false_type{});
     } else {
+      JumpArgs<T> a = jump_args<JumpArgs<T>>(s, i, vi, si, xin, xo, ring_slot0, s->stats + 4 * i);
+      a.noise = (const T*)noise;
+      a.rexp = rexp;
+      a.runif = runif;
       if (compact) {
         // elementwise.hpp (mjhmc_step_kernel): the iteration's trajectories -- the L proposals and, beside them, the
         // inverse-L proposals of the listed cold caches --, then its jump process with a lane per particle, which finishes
@@ -2134,12 +1872,14 @@ static int iterate_t(mjhmc_sampler* s, int n_iter, const double* replay_normal, 
           hipLaunchKernelGGL(compact_list_kernel<ColdCache<T>>, list_grid, dim3(1024), 0, s->stream,
                              ColdCache<T>{a.Hflf_in, (T*)s->Hpre + s->Npad}, s->N, s->ctl, s->flf_list, s->flf_counts);
         }
-        TRY(dispatch_step<T>(s->en->ep.kind, &ta, nullptr, s->en->ep, s->sh.E, s->stream));
-        TRY(dispatch_step<T>(s->en->ep.kind, nullptr, &da, s->en->ep, s->sh.E, s->stream));
+        TRY(with_elementwise_energy(s->en->ep.kind, [&](auto en) {
+          en.step(&ta, nullptr, s->en->ep, s->sh.E, s->stream);
+          en.step(nullptr, &da, s->en->ep, s->sh.E, s->stream);
+        }));
       } else if (s->en->is_user()) {
         if constexpr (sizeof(T) == 8) TRY(user_launch_jump(s->en, a, s->stream));
       } else {
-        TRY(dispatch_jump<T>(s->en->ep.kind, a, s->en->ep, s->sh.E, s->stream));
+        TRY(with_elementwise_energy(s->en->ep.kind, [&](auto en) { en.jump(a, s->en->ep, s->sh.E, s->stream); }));
       }
     }
     if (n_parts > 1 && i + 1 == n_iter) {  // the read-back follows every part
@@ -2161,8 +1901,7 @@ static int iterate_t(mjhmc_sampler* s, int n_iter, const double* replay_normal, 
       const bool room = s->dl_stage_elems >= (size_t)s->dl->n_iter * elems;
       for (int k = 0; k < n_parts; ++k) {
         sts[k] = part_stream(k);
-        if (room) TRY(dl_retile(s, xj, n_parts > 1 ? part_start(k) : 0, n_parts > 1 ? part_count(k) : s->N,
-                                s->dl_stage + (size_t)j * elems, sts[k]));
+        if (room) TRY(dl_retile(s, xj, part_start(k), part_count(k), s->dl_stage + (size_t)j * elems, sts[k]));
       }
       s->dl->retiled[(size_t)j] = room ? 1 : 0;
       return dl_mark(s, j, 1, sts, n_parts);
@@ -2238,7 +1977,33 @@ static int leap_t(mjhmc_sampler& w, void* Xd, void* Vd, void* Xo, void* Vo, void
   if constexpr (sizeof(T) == 8) {
     if (w.en->is_user()) return user_launch_leap(w.en, a, w.stream);
   }
-  TRY(dispatch_leap<T>(w.en->ep.kind, a, w.en->ep, w.sh.E, w.stream));
+  TRY(with_elementwise_energy(w.en->ep.kind, [&](auto en) { en.leap(a, w.en->ep, w.sh.E, w.stream); }));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the dense energies' leapfrog operator on rows buf[0] (X), buf[1] (V) -> buf[2], buf[3], dE/dX buf[4], EX buf[5], EV buf[6]
+template <typename S, bool POT>
+static int leap_dense(mjhmc_sampler& w, void* const* buf, double eps, int L) {
+  DenseLeapArgs<S, POT> a{};
+  a.X = (const S*)buf[0];
+  a.V = (const S*)buf[1];
+  a.X_out = (S*)buf[2];
+  a.V_out = (S*)buf[3];
+  a.G = (float*)buf[4];
+  a.EX = (float*)buf[5];
+  a.EV = (float*)buf[6];
+  a.N = w.N;
+  a.ntiles = dense_ntiles(&w, w.N, w.Npad);
+  a.L = L;
+  a.eps = (float)eps;
+  a.chalf = (float)(-eps / 2.);
+  if constexpr (POT) {
+    a.D = w.D;
+    pot_launch_leap(a, w.en->pot_model(), w.stream, w.en->pot_gen());
+  } else {
+    sic_launch_leap(a, w.en->sic_model(), w.stream);
+  }
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2778,44 +2543,10 @@ int mjhmc_leapfrog(mjhmc_energy* e, int dtype, const double* X, const double* V,
       TRY(round_rows32(&w, buf[1]));
     }
     if (e->is_pot() && !w.sh.wide) {
-      PotLeapArgs a;
-      a.X = (const float*)buf[0];
-      a.V = (const float*)buf[1];
-      a.X_out = (float*)buf[2];
-      a.V_out = (float*)buf[3];
-      a.G = (float*)buf[4];
-      a.EX = (float*)buf[5];
-      a.EV = (float*)buf[6];
-      a.N = n;
-      a.ntiles = w.Npad / 32;
-      a.D = w.D;
-      a.L = n_steps;
-      a.eps = (float)eps;
-      a.chalf = (float)(-eps / 2.);
-      pot_launch_leap(a, e->pot_model(), w.stream, e->pot_gen());
-      HIPCHK(hipGetLastError());
+      TRY((leap_dense<float, true>(w, buf, eps, n_steps)));
     } else if (e->is_sic()) {
-      auto leap_sic = [&](auto tag) {
-        using ST = decltype(tag);
-        SicLeapArgsT<ST> a;
-        a.X = (const ST*)buf[0];
-        a.V = (const ST*)buf[1];
-        a.X_out = (ST*)buf[2];
-        a.V_out = (ST*)buf[3];
-        a.G = (float*)buf[4];
-        a.EX = (float*)buf[5];
-        a.EV = (float*)buf[6];
-        a.N = n;
-        const int ppt = sic_particles_per_tile(e->sic_P);
-        a.ntiles = (n + ppt - 1) / ppt;
-        a.L = n_steps;
-        a.eps = (float)eps;
-        a.chalf = (float)(-eps / 2.);
-        sic_launch_leap(a, e->sic_model(), w.stream);
-      };
-      if (dtype == MJHMC_BF16) leap_sic(__bf16{});
-      else leap_sic(float{});
-      HIPCHK(hipGetLastError());
+      if (dtype == MJHMC_BF16) TRY((leap_dense<__bf16, false>(w, buf, eps, n_steps)));
+      else TRY((leap_dense<float, false>(w, buf, eps, n_steps)));
     } else if (w.sh.wide) {
       TRY(wide_leapfrog(&w, (const double*)buf[0], (const double*)buf[1], (double*)buf[2], (double*)buf[3], (double*)buf[4],
                         (double*)buf[5], (double*)buf[6], eps, n_steps));

@@ -22,109 +22,12 @@ struct PotModel {
   int ndims;           // true ndims == nbasis (rows at or beyond it are zero padding)
 };
 
-struct PotJumpArgs {
-  const float* X_in;
-  const float* V_in;
-  const float* G_in;   // dE/dX at X_in (HMCState.dEdX, hmc_state.py:36-39)
-  float* X_out;
-  float* V_out;
-  float* G_out;
-  const float* EX_in;
-  const float* EV_in;
-  const float* Hflf_in;
-  float* Hwork;        // [Npad] H of the inverse-L proposal, where this iteration integrates it (the listed particles)
-  int* cold_list;      // [Npad] compacted indices of the particles whose inverse-L proposal must be integrated
-  int* cold_count;
-  int* next_list;       // the NEXT iteration's list and counter, filled by this iteration's jump and fix kernels
-  int* next_count;
-  int* zero_count;      // the counter of the list two iterations back (consumed): cleared by the jump kernel for its next use
-  int rescan;           // host side: build this iteration's list by a scan even if it is not the call's first (test build, MJHMC_NO_FSPEC)
-  const float* Hspec_in;   // H of the L proposal of a particle that then moved by F, NaN otherwise (see dense_pot.hip: F-movers)
-  float* Hspec_out;
-  float* EX_out;
-  float* EV_out;
-  float* Hflf_out;
-  double* dwell;
-  double* dwell_ring;
-  uint8_t* trans;
-  const float* noise;   // replay normals [N][512] or nullptr
-  const double* rexp;   // replay unit exponentials [3][N] or nullptr
-  const double* runif;  // replay uniforms of the discrete-time samplers [2N+1] (accept, flip, R gate) or nullptr
-  Control* ctl;
-  unsigned long long* stats;
-  int64_t N, Npad, ntiles, first_pid;
-  int D, L, iter;
-  int mode;             // kModeMJHMC / kModeControl / kModeCT
-  float eps, chalf, r_keep, r_mix;
-  double p_r, p_flip;
-  RngKey key;
-};
-
-// The same iteration in the reference's arithmetic (dense_pot64.hip): float64 state rows around the float32 force
-struct Pot64JumpArgs {
-  const double* X_in;
-  const double* V_in;
-  const double* G_in;   // dE/dX at X_in: float32 values widened (hmc_state.py:52-53)
-  double* X_out;        // also the working rows of the trajectory
-  double* V_out;
-  double* G_out;
-  const double* EX_in;
-  const double* EV_in;
-  const double* Hflf_in;
-  double* Hwork;
-  int* cold_list;
-  int* cold_count;
-  int* next_list;       // the NEXT iteration's list and counter, filled by this iteration's jump and fix kernels
-  int* next_count;
-  int* zero_count;
-  int rescan;
-  const double* Hspec_in;
-  double* Hspec_out;
-  double* EX_out;
-  double* EV_out;
-  double* Hflf_out;
-  double* dwell;
-  double* dwell_ring;
-  uint8_t* trans;
-  const double* noise;
-  const double* rexp;
-  const double* runif;
-  double* scratch;      // [workgroups][2][32][dim] working rows of the inverse-L pass (pot64_scratch_workgroups())
-  Control* ctl;
-  unsigned long long* stats;
-  int64_t N, Npad, ntiles, first_pid;
-  int D, L, iter;       // L >= 1
-  int mode;
-  double eps, chalf, r_keep, r_mix;
-  double p_r, p_flip;
-  RngKey key;
-};
-
-// stand-alone leapfrog operator on caller-supplied states (HMCState.leapfrog / L, hmc_state.py:86-100)
-struct PotLeapArgs {
-  const float* X;
-  const float* V;
-  float* X_out;
-  float* V_out;
-  float* G;        // dE/dX at the end point, or nullptr
-  float* EX;       // [n] or nullptr
-  float* EV;
-  int64_t N, ntiles;
-  int D, L;
-  float eps, chalf;
-};
-
-struct PotEvalArgs {
-  const float* X;
-  float* G;
-  float* E;
-  float* EV;
-  const float* V;
-  float* V_gen;
-  int64_t N, ntiles, first_pid;
-  int D;
-  RngKey key;
-};
+// the tile kernels' argument blocks (elementwise.hpp: DenseJumpArgs): float32 state rows, and the reference's
+// arithmetic (dense_pot64.hip) with float64 state rows around the float32 force
+using PotJumpArgs = DenseJumpArgs<float, float, true>;
+using Pot64JumpArgs = DenseJumpArgs<double, double, true>;
+using PotLeapArgs = DenseLeapArgs<float, true>;
+using PotEvalArgs = DenseEvalArgs<float, true>;
 
 // The experts of a linear-model energy (MJHMC_E_LINEAR_EXPR: E = sum_j f(u_j, j), u = W x + b; dense_pot_kernels.hpp
 // LinearExperts), the third argument of its generated kernels

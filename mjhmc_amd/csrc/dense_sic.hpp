@@ -27,68 +27,11 @@ constexpr int kSicCopies = 1;
 // ST = the type the state rows are STORED in: __bf16 (BASELINE.json configs[4]: "bf16 state / fp32 accumulate") or float
 // (the reference's own: TensorFlow float32 placeholders, tf_distributions.py:89).  The matrix-core operands are bf16 either way.
 template <typename ST>
-struct SicJumpArgsT {
-  const ST* X_in;
-  const ST* V_in;
-  ST* X_out;
-  ST* V_out;
-  const float* EX_in;
-  const float* EV_in;
-  const float* Hflf_in;
-  float* Hwork;
-  int* cold_list;
-  int* cold_count;
-  int* next_list;       // the NEXT iteration's list and counter, filled by this iteration's jump and fix kernels
-  int* next_count;
-  int* zero_count;      // (as PotJumpArgs)
-  int rescan;
-  const float* Hspec_in;
-  float* Hspec_out;
-  float* EX_out;
-  float* EV_out;
-  float* Hflf_out;
-  double* dwell;
-  double* dwell_ring;
-  uint8_t* trans;
-  const ST* noise;
-  const double* rexp;
-  const double* runif;  // replay uniforms of the discrete-time samplers [2N+1] or nullptr
-  Control* ctl;
-  unsigned long long* stats;
-  int64_t N, Npad, ntiles, first_pid;
-  int L, iter;
-  int mode;             // kModeMJHMC / kModeControl / kModeCT
-  float eps, chalf, r_keep, r_mix;
-  double p_r, p_flip;
-  RngKey key;
-};
-
-// stand-alone leapfrog operator on caller-supplied states (HMCState.leapfrog / L, hmc_state.py:86-100)
+using SicJumpArgsT = DenseJumpArgs<ST, float, false>;
 template <typename ST>
-struct SicLeapArgsT {
-  const ST* X;
-  const ST* V;
-  ST* X_out;
-  ST* V_out;
-  float* G;        // float32 dE/dX at the end point [n][P * 1024], or nullptr
-  float* EX;
-  float* EV;
-  int64_t N, ntiles;
-  int L;
-  float eps, chalf;
-};
-
+using SicLeapArgsT = DenseLeapArgs<ST, false>;
 template <typename ST>
-struct SicEvalArgsT {
-  const ST* X;
-  float* G;         // float32 [Npad][1024] or nullptr
-  float* E;
-  float* EV;
-  const ST* V;
-  ST* V_gen;
-  int64_t N, ntiles, first_pid;
-  RngKey key;
-};
+using SicEvalArgsT = DenseEvalArgs<ST, false>;
 
 using SicJumpArgs = SicJumpArgsT<__bf16>;
 using SicLeapArgs = SicLeapArgsT<__bf16>;

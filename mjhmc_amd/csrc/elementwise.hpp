@@ -796,6 +796,94 @@ struct JumpDecideArgs {
   RngKey key;
 };
 
+// The argument blocks of the dense tile kernels: ProductOfT (POT; dense_pot.hip, float32 rows; dense_pot64.hip, the
+// reference's float64 rows around the float32 force) and SparseImageCode (dense_sic.hip, bfloat16 or float32 rows).  S: the
+// type of the stored state rows (and of `noise`, G_in / G_out); H: the per-particle scalars and the step parameters.
+// A field a family does not have (G_in / G_out and D: ProductOfT only; scratch: float64 ProductOfT only) is a NoField that
+// takes no room, so that every family's block keeps its own layout (the kernels' scalar loads and registers follow it).
+struct NoField {};
+template <bool HAS, typename F>
+struct FieldIfT {
+  using type = F;
+};
+template <typename F>
+struct FieldIfT<false, F> {
+  using type = NoField;
+};
+template <bool HAS, typename F>
+using FieldIf = typename FieldIfT<HAS, F>::type;
+
+template <typename S, typename H, bool POT>
+struct DenseJumpArgs {
+  static constexpr bool kPot = POT, kScratch = POT && sizeof(S) == 8;
+  const S* X_in;
+  const S* V_in;
+  [[no_unique_address]] FieldIf<POT, const S*> G_in;  // dE/dX at X_in (HMCState.dEdX, hmc_state.py:36-39); float64 rows: float32 values widened (:52-53)
+  S* X_out;            // (float64 ProductOfT: also the working rows of the trajectory)
+  S* V_out;
+  [[no_unique_address]] FieldIf<POT, S*> G_out;
+  const H* EX_in;
+  const H* EV_in;
+  const H* Hflf_in;
+  H* Hwork;            // [Npad] H of the inverse-L proposal, where this iteration integrates it (the listed particles)
+  int* cold_list;      // [Npad] compacted indices of the particles whose inverse-L proposal must be integrated
+  int* cold_count;
+  int* next_list;      // the NEXT iteration's list and counter, filled by this iteration's jump and fix kernels
+  int* next_count;
+  int* zero_count;     // the counter of the list two iterations back (consumed): cleared by the jump kernel for its next use
+  int rescan;          // host side: build this iteration's list by a scan even if it is not the call's first (test build, MJHMC_NO_FSPEC)
+  const H* Hspec_in;   // H of the L proposal of a particle that then moved by F, NaN otherwise (see dense_pot.hip: F-movers)
+  H* Hspec_out;
+  H* EX_out;
+  H* EV_out;
+  H* Hflf_out;
+  double* dwell;
+  double* dwell_ring;
+  uint8_t* trans;
+  const S* noise;      // replay normals [N][pitch] or nullptr
+  const double* rexp;  // replay unit exponentials [3][N] or nullptr
+  const double* runif; // replay uniforms of the discrete-time samplers [2N+1] (accept, flip, R gate) or nullptr
+  [[no_unique_address]] FieldIf<kScratch, double*> scratch;  // [workgroups][2][32][dim] working rows of the inverse-L pass (pot64_scratch_workgroups())
+  Control* ctl;
+  unsigned long long* stats;
+  int64_t N, Npad, ntiles, first_pid;
+  [[no_unique_address]] FieldIf<POT, int> D;
+  int L, iter;         // L >= 1
+  int mode;            // kModeMJHMC / kModeControl / kModeCT
+  H eps, chalf, r_keep, r_mix;
+  double p_r, p_flip;
+  RngKey key;
+};
+
+// stand-alone leapfrog operator on caller-supplied states (HMCState.leapfrog / L, hmc_state.py:86-100)
+template <typename S, bool POT>
+struct DenseLeapArgs {
+  const S* X;
+  const S* V;
+  S* X_out;
+  S* V_out;
+  float* G;        // float32 dE/dX at the end point, or nullptr (SparseImageCode: [n][P * 1024])
+  float* EX;       // [n] or nullptr
+  float* EV;
+  int64_t N, ntiles;
+  [[no_unique_address]] FieldIf<POT, int> D;
+  int L;
+  float eps, chalf;
+};
+
+template <typename S, bool POT>
+struct DenseEvalArgs {
+  const S* X;
+  float* G;        // float32 dE/dX or nullptr (SparseImageCode: [Npad][1024])
+  float* E;
+  float* EV;
+  const S* V;
+  S* V_gen;
+  int64_t N, ntiles, first_pid;
+  [[no_unique_address]] FieldIf<POT, int> D;
+  RngKey key;
+};
+
 // ------------------------------------------------------------------------------------------
 // building blocks
 // ------------------------------------------------------------------------------------------
@@ -3314,49 +3402,49 @@ inline void launch_eval_t(const EvalArgs<T>& a, const En& en, hipStream_t st) {
 
 // E choices: f64 {2, 8, 16}, f32 {4, 16, 32}  (1, 4, 8 chunks per lane)
 #define MJHMC_DEFINE_ENERGY_LAUNCHERS(NAME, MAKE64, MAKE32)                                               \
-  void NAME##_jump_f64(const JumpArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {        \
+  void NAME##_jump(const JumpArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {            \
     const auto en = MAKE64(ep);                                                                           \
     if (E == 2) launch_jump_t<decltype(en), double, 2>(a, en, st);                                        \
     else if (E == 8) launch_jump_t<decltype(en), double, 8>(a, en, st);                                   \
     else launch_jump_t<decltype(en), double, 16>(a, en, st);                                              \
   }                                                                                                       \
-  void NAME##_jump_f32(const JumpArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {         \
+  void NAME##_jump(const JumpArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {             \
     const auto en = MAKE32(ep);                                                                           \
     if (E == 4) launch_jump_t<decltype(en), float, 4>(a, en, st);                                         \
     else if (E == 16) launch_jump_t<decltype(en), float, 16>(a, en, st);                                  \
     else launch_jump_t<decltype(en), float, 32>(a, en, st);                                               \
   }                                                                                                       \
-  void NAME##_leap_f64(const LeapArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {        \
+  void NAME##_leap(const LeapArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {            \
     const auto en = MAKE64(ep);                                                                           \
     if (E == 2) launch_leap_t<decltype(en), double, 2>(a, en, st);                                        \
     else if (E == 8) launch_leap_t<decltype(en), double, 8>(a, en, st);                                   \
     else launch_leap_t<decltype(en), double, 16>(a, en, st);                                              \
   }                                                                                                       \
-  void NAME##_leap_f32(const LeapArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {         \
+  void NAME##_leap(const LeapArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {             \
     const auto en = MAKE32(ep);                                                                           \
     if (E == 4) launch_leap_t<decltype(en), float, 4>(a, en, st);                                         \
     else if (E == 16) launch_leap_t<decltype(en), float, 16>(a, en, st);                                  \
     else launch_leap_t<decltype(en), float, 32>(a, en, st);                                               \
   }                                                                                                       \
-  void NAME##_step_f64(const TrajArgs<double>* ta, const JumpDecideArgs<double>* da, const EnergyParams& ep, int E, hipStream_t st) { \
+  void NAME##_step(const TrajArgs<double>* ta, const JumpDecideArgs<double>* da, const EnergyParams& ep, int E, hipStream_t st) { \
     const auto en = MAKE64(ep);                                                                           \
     if (E == 2) launch_step_t<decltype(en), double, 2>(ta, da, en, st);                                   \
     else if (E == 8) launch_step_t<decltype(en), double, 8>(ta, da, en, st);                              \
     else launch_step_t<decltype(en), double, 16>(ta, da, en, st);                                         \
   }                                                                                                       \
-  void NAME##_step_f32(const TrajArgs<float>* ta, const JumpDecideArgs<float>* da, const EnergyParams& ep, int E, hipStream_t st) { \
+  void NAME##_step(const TrajArgs<float>* ta, const JumpDecideArgs<float>* da, const EnergyParams& ep, int E, hipStream_t st) { \
     const auto en = MAKE32(ep);                                                                           \
     if (E == 4) launch_step_t<decltype(en), float, 4>(ta, da, en, st);                                    \
     else if (E == 16) launch_step_t<decltype(en), float, 16>(ta, da, en, st);                             \
     else launch_step_t<decltype(en), float, 32>(ta, da, en, st);                                          \
   }                                                                                                       \
-  void NAME##_eval_f64(const EvalArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {        \
+  void NAME##_eval(const EvalArgs<double>& a, const EnergyParams& ep, int E, hipStream_t st) {            \
     const auto en = MAKE64(ep);                                                                           \
     if (E == 2) launch_eval_t<decltype(en), double, 2>(a, en, st);                                        \
     else if (E == 8) launch_eval_t<decltype(en), double, 8>(a, en, st);                                   \
     else launch_eval_t<decltype(en), double, 16>(a, en, st);                                              \
   }                                                                                                       \
-  void NAME##_eval_f32(const EvalArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {         \
+  void NAME##_eval(const EvalArgs<float>& a, const EnergyParams& ep, int E, hipStream_t st) {             \
     const auto en = MAKE32(ep);                                                                           \
     if (E == 4) launch_eval_t<decltype(en), float, 4>(a, en, st);                                         \
     else if (E == 16) launch_eval_t<decltype(en), float, 16>(a, en, st);                                  \
@@ -3364,14 +3452,14 @@ inline void launch_eval_t(const EvalArgs<T>& a, const En& en, hipStream_t st) {
   }
 
 #define MJHMC_DECLARE_ENERGY_LAUNCHERS(NAME)                                                       \
-  void NAME##_jump_f64(const JumpArgs<double>&, const EnergyParams&, int, hipStream_t);           \
-  void NAME##_jump_f32(const JumpArgs<float>&, const EnergyParams&, int, hipStream_t);            \
-  void NAME##_leap_f64(const LeapArgs<double>&, const EnergyParams&, int, hipStream_t);           \
-  void NAME##_leap_f32(const LeapArgs<float>&, const EnergyParams&, int, hipStream_t);            \
-  void NAME##_step_f64(const TrajArgs<double>*, const JumpDecideArgs<double>*, const EnergyParams&, int, hipStream_t); \
-  void NAME##_step_f32(const TrajArgs<float>*, const JumpDecideArgs<float>*, const EnergyParams&, int, hipStream_t);  \
-  void NAME##_eval_f64(const EvalArgs<double>&, const EnergyParams&, int, hipStream_t);           \
-  void NAME##_eval_f32(const EvalArgs<float>&, const EnergyParams&, int, hipStream_t);
+  void NAME##_jump(const JumpArgs<double>&, const EnergyParams&, int, hipStream_t);           \
+  void NAME##_jump(const JumpArgs<float>&, const EnergyParams&, int, hipStream_t);            \
+  void NAME##_leap(const LeapArgs<double>&, const EnergyParams&, int, hipStream_t);           \
+  void NAME##_leap(const LeapArgs<float>&, const EnergyParams&, int, hipStream_t);            \
+  void NAME##_step(const TrajArgs<double>*, const JumpDecideArgs<double>*, const EnergyParams&, int, hipStream_t); \
+  void NAME##_step(const TrajArgs<float>*, const JumpDecideArgs<float>*, const EnergyParams&, int, hipStream_t);  \
+  void NAME##_eval(const EvalArgs<double>&, const EnergyParams&, int, hipStream_t);           \
+  void NAME##_eval(const EvalArgs<float>&, const EnergyParams&, int, hipStream_t);
 
 MJHMC_DECLARE_ENERGY_LAUNCHERS(iso)
 MJHMC_DECLARE_ENERGY_LAUNCHERS(diag)

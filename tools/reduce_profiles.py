@@ -30,7 +30,7 @@ def counters(path):
 
 
 def launches_per_iteration(path, kernel):
-    """Big dense batches run as two halves on two streams (api.hip: half_args): the main kernel is then dispatched once per
+    """Big dense batches run as two halves on two streams (api.hip: part_args): the main kernel is then dispatched once per
     half and iteration, from two queues."""
     queues = set()
     with open(path) as f:
