@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: particle-steps/s (ndims x nparticles x L per sampling_iteration) of the MJHMC hot path on
-MI355X, each workload with the roofline that bounds its kernel and the NumPy CPU baseline timed beside it.
+MI355X, each workload with the roofline that bounds its kernel and, under --full, the NumPy CPU baseline timed beside it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--head c3|c2|c4|c5] [--workload c2|c3|c4|c5|c1|all]
-                    [--scaling weak|strong] [--dump-outputs DIR]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
-The ONE JSON line rank 0 prints has the workload BASELINE.json's numeric target is stated on (C3, ProductOfT
+A plain run measures the headline only: it sets up the head workload, warms it up, times its K steps, writes
+--dump-outputs and prints the line (value, ms_per_step and the head's own roofline and device fields).  --full adds
+everything else described below: the other workloads, the N/G shards, the CPU baseline and the `target` it
+feeds, the boundary / autocorrelation / one-iteration-per-call figures, the multi-rank sample gather check, the
+strong-scaled C4 / C5 and the --detail file.  Both time the head workload the same way.
+
+The ONE JSON line rank 0 prints under --full has the workload BASELINE.json's numeric target is stated on (C3, ProductOfT
 512 x 100 000: ">= 50x the NumPy reference at 1 GPU"; in the reference's arithmetic: c3f64) as its top-level workload
 (--head) and every GPU workload (C2..C5 = configs[1..4]; c5 = SparseImageCode with the reference's float32 state rows,
 c5bf16 = BASELINE's wording, which runs hot under MarkovJumpHMC) as flat scalars of `config`: cK_ms, cK_frac (the flops
@@ -28,7 +34,7 @@ anything touches a GPU or loads the library; never exec), gives them RANK / LOCA
 in a fresh directory (MJHMC_COMM_ID_FILE), relays rank 0's line and exits non-zero if any rank does.  Particle columns are
 independent chains: each rank owns a block of columns (global particle ids keep the RNG streams those of an unsharded
 run), nothing is exchanged inside the timed region.  --scaling weak (default): every rank runs the full single-GPU
-workload (that is `value`); at N > 1 the line also carries, under "strong", C4 and C5 with the workload's particle
+workload (that is `value`); at N > 1 a --full line also carries, under "strong", C4 and C5 with the workload's particle
 count as the TOTAL (BASELINE.json words them that way: "1 000 000 sharded across 8", "200 000 ... on 8xMI355X").
 """
 import argparse
@@ -394,10 +400,11 @@ def dump_outputs(smp, key, last, out_dir):
         np.save(os.path.join(out_dir, '%s_%s.npy' % (key, name)), np.ascontiguousarray(a, dtype=np.float64))
 
 
-def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=1, dump_dir=None):
+def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=1, dump_dir=None, extras=False):
     """shard_of = G > 1: the workload at N/G particles on this one GPU -- what each rank of a G-GPU strong-scaled run
     executes (no timed region holds a collective, so t(G GPUs, N) = t(1 GPU, N/G)); same kernels, same flags.
-    dump_dir: write the timed call's outputs there (dump_outputs)."""
+    dump_dir: write the timed call's outputs there (dump_outputs).  extras (--full): after the timed call, also the
+    one-iteration-per-call, boundary and on-device autocorrelation figures."""
     from mjhmc_amd import engine, _lib
     rank, world = rig.rank, rig.world
     w = dict(WORKLOADS[key])
@@ -469,7 +476,7 @@ def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=
     # the same workload with one sampling iteration per launch (the HBM-bound form of the kernel: what every
     # sampling_iteration() caller gets -- a call of ONE iteration is never fused), after the timed region
     unfused_ms = unfused_call_ms = None
-    if fused and shard_of == 1:
+    if extras and fused and shard_of == 1:
         for _ in range(8):
             smp.iterate(1)
         t_sum = 0.0
@@ -490,7 +497,7 @@ def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=
     # every slot crosses PCIe while the following iterations run, mjhmc_iterate_download).  n = 10 where ten float64 host
     # copies of the state stay under ~4.4 GB, fewer for the bigger states (C5: 1.6 GB per sample).
     boundary = None
-    want_boundary = world == 1 and scaling == 'weak' and shard_of == 1 and key in (rig.head, 'c2', 'c4', 'c5')
+    want_boundary = extras and world == 1 and scaling == 'weak' and shard_of == 1 and key in (rig.head, 'c2', 'c4', 'c5')
     if want_boundary:
         esz = {'float64': 8, 'float32': 4, 'bfloat16': 2}[w['dtype']]
         host_bytes = 8 * int(w['D']) * n_rank
@@ -530,7 +537,7 @@ def run_workload(rig, key, steps, warmup, cpu_seconds, scaling='weak', shard_of=
     # (sample(n, preserve_order=True)'s form) + the lag sums over the ring on the device (mjhmc_ring_autocor): the samples
     # never leave HBM; particle-steps/s over BOTH.
     acor = None
-    if world == 1 and scaling == 'weak' and shard_of == 1 and key in ('c2', 'c4'):
+    if extras and world == 1 and scaling == 'weak' and shard_of == 1 and key in ('c2', 'c4'):
         T_ac = 16
         smp.ring_alloc(T_ac)
         smp.iterate(T_ac, ring_slot0=0)
@@ -1014,14 +1021,19 @@ def main(argv=None):
                     help='top-level workload of the line (default: C3 in the reference\'s arithmetic -- float64 state around '
                          'the float32 force --, the workload of BASELINE.json\'s numeric target; c3: its float32-state form)')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='measure and check everything beyond the headline figure: the other workloads, --shard-of, the CPU '
+                         'baseline, the boundary / autocorrelation / one-iteration-per-call figures, the multi-rank sample '
+                         'gather check, the strong-scaled C4 / C5 and --detail (a plain run times the head workload only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the NumPy CPU baseline')
     ap.add_argument('--shard-of', default='auto',
                     help='comma list of G: after every workload, the same workload at N/G particles on this ONE GPU (what a rank '
                          'of a G-GPU strong-scaled run executes); shard_efficiency = t(N) / (G t(N/G)).  Default "auto": 2,4,8 '
                          'for the head, C4 and C5 (BASELINE.json words those as sharded; north_star: "fraction reported at '
-                         '1/2/4/8"), 8 for the others; "1" = none.  Ignored at --gpus > 1')
-    ap.add_argument('--detail', default=os.path.join(ROOT, 'gpurun_out', 'bench_detail.json'),
-                    help='file that receives the complete per-workload records (the printed line carries numbers only)')
+                         '1/2/4/8"), 8 for the others; "1" = none.  Only with --full; ignored at --gpus > 1')
+    ap.add_argument('--detail', default=None,
+                    help='file that receives the complete per-workload records (the printed line carries numbers only); '
+                         'default: bench_detail.json in the repository root with --full, none without')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the head workload computed in its last step (float64 .npy, '
                          'a fixed sample of particle columns, < 64 MB) into DIR')
@@ -1036,17 +1048,17 @@ def main(argv=None):
         return fake_rank(args)
     rig = Rig(args)
     progress('comm_up' if rig.world > 1 else 'single')
-    # the one collective of the path FIRST: a broken or hanging all-gather is found in the run's first seconds (the
-    # spawning parent watches for the marker below), not after five workloads
-    gather_info = sample_gather_check(rig) if rig.comm is not None else None
+    # --full: the one collective of the path FIRST: a broken or hanging all-gather is found in the run's first seconds
+    # (the spawning parent watches for the marker below), not after five workloads
+    gather_info = sample_gather_check(rig) if rig.comm is not None and args.full else None
     progress('gather_done')
     keys = ['c2', 'c3', 'c3f64', 'c4', 'c5', 'c5bf16'] if args.workload == 'all' else [args.workload]
     head = args.head if args.head in keys else keys[0]
-    keys = [head] + [k for k in keys if k != head]
+    keys = [head] + [k for k in keys if k != head] if args.full else [head]
     rig.head = head
     results, strong, shards = {}, {}, {}
     def shard_gs(key):
-        if rig.world != 1 or key == 'c1':
+        if not args.full or rig.world != 1 or key == 'c1':
             return []
         if args.shard_of == 'auto':
             return [2, 4, 8] if key in (head, 'c4', 'c5') else [8]
@@ -1067,9 +1079,9 @@ def main(argv=None):
     # C2 right after the ProductOfT run reads 7 % slower than on a chip that has not just run 20 s of dense MFMA work.)
     for key in [k for k in ('c1', 'c2', 'c4', 'c3', 'c3f64', 'c5', 'c5bf16') if k in keys]:
         steps, warm = budget(key)
-        cpu_s = 0 if (args.no_cpu_baseline or cpu_key.get(key, key) != key) else (12.0 if key == head else 6.0)
+        cpu_s = 0 if (not args.full or args.no_cpu_baseline or cpu_key.get(key, key) != key) else (12.0 if key == head else 6.0)
         results[key] = run_workload(rig, key, steps, warm, cpu_s, args.scaling,
-                                    dump_dir=args.dump_outputs if key == head else None)
+                                    dump_dir=args.dump_outputs if key == head else None, extras=args.full)
         progress('workload_done ' + key)
         if results[key] is not None:
             results[key]['steps'] = steps
@@ -1083,7 +1095,7 @@ def main(argv=None):
                 rec.update(steps=steps, warmup=warm)
                 rec['shard_efficiency'] = results[key]['ms_per_step'] / (g * rec['ms_per_step'])
                 shards.setdefault(key, {})[g] = rec
-    if rig.world > 1 and args.scaling == 'weak':
+    if args.full and rig.world > 1 and args.scaling == 'weak':
         # BASELINE.json words C4 and C5 as totals sharded over the GPUs: the same line carries them strong-scaled
         for key in [k for k in ('c4', 'c5') if k in keys]:
             steps, warm = budget(key)
@@ -1190,15 +1202,16 @@ def main(argv=None):
         line = json.dumps(rnd(out))
         print(line)
         sys.stdout.flush()
-        if args.detail:
+        detail = args.detail or (os.path.join(ROOT, 'bench_detail.json') if args.full else None)
+        if detail:
             try:
-                os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-                with open(args.detail, 'w') as f:
+                os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
+                with open(detail, 'w') as f:
                     json.dump({'line_bytes': len(line), 'workloads': results,
                                'shards': {k: {str(g): r for g, r in v.items()} for k, v in shards.items()},
                                'strong': strong, 'sample_gather': gather_info}, f, indent=1, default=float)
             except OSError as exc:
-                sys.stderr.write('bench.py: --detail %s not written (%s)\n' % (args.detail, exc))
+                sys.stderr.write('bench.py: --detail %s not written (%s)\n' % (detail, exc))
     if rig.comm is not None:
         rig.comm.barrier()
         if hasattr(rig.comm, 'close'):

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" "SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" "SQ_INST_CYCLES_VMEM SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/g$i" -o c4 -- python3 "$ROOT/bench.py" --workload c4 --steps 1 --no-cpu-baseline --shard-of 1 > /dev/null 2> "$OUT/g$i.err"
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/g$i" -o c4 -- python3 "$ROOT/bench.py" --full --workload c4 --steps 1 --no-cpu-baseline --shard-of 1 > /dev/null 2> "$OUT/g$i.err"
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "$@"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/g$i" -o $W -- python3 "$ROOT/bench.py" --workload $W --no-cpu-baseline > /dev/null 2> "$OUT/g$i.err"
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/g$i" -o $W -- python3 "$ROOT/bench.py" --full --workload $W --no-cpu-baseline > /dev/null 2> "$OUT/g$i.err"
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

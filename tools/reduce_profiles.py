@@ -137,7 +137,7 @@ def main():
                                                                      100.0 * sq['SQ_INSTS_VALU'][0] * 4 / 1024.0 / cyc))
             notes.append('%s: %s' % (w, {k: '%.4g' % v[0] for k, v in sq.items()}))
     traffic['_provenance'] = {'calibration_known_read_over_FETCH_SIZE': 1.9996481868971179,
-                              'note': 'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --workload X '
+                              'note': 'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --full --workload X '
                                       '--no-cpu-baseline` (tools/profile_round.sh); bytes = FETCH_SIZE*1024*2 + WRITE_SIZE*1024 (gfx950 FETCH_SIZE '
                                       'reports half of wide streaming reads; calibrated in round 1 on to_particle_major reading a known 409.6 MB, '
                                       'profiles/r01/c2_pmc_fetch_size.csv); reduced by tools/reduce_profiles.py'}
