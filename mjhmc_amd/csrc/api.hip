@@ -1487,7 +1487,9 @@ static A jump_args(const mjhmc_sampler* s, int iter, int vi, int si, const void*
     a.pitch = s->sh.pitch;
     a.CH = s->sh.CH;
     a.logG = s->sh.logG;
-    a.ab = ab_flags();
+    // the fused launch takes the row form exactly where fused_rows() says so: launch_jump_t's fused_rows_shape() sees the
+    // lane mapping only, and without kAbNoRows the mixture below its kRelayMinL ran the one-wave row kernel
+    a.ab = ab_flags() | (fused_rows(s) ? 0 : kAbNoRows);
   } else if constexpr (A::kPot) {
     a.D = s->D;
   }

@@ -45,14 +45,16 @@ def _stats_tuple(st):
     ('E_ISO_GAUSS', 2, 100, 'MODE_MJHMC', 9),
     ('E_DIAG_GAUSS', 32, 300, 'MODE_MJHMC', 6),
     ('E_FUNNEL_NEAL', 32, 300, 'MODE_MJHMC', 6),      # the funnels fuse in row form (a lane per particle, mjhmc_fused_rows_kernel):
-    ('E_FUNNEL_NEAL', 31, 20011, 'MODE_MJHMC', 5),    #   full rows of four-lane groups, a persistent grid with a ragged last tile
+    ('E_FUNNEL_NEAL', 31, 20011, 'MODE_MJHMC', 5),    #   full rows of four-lane groups, a ragged last tile (one tile per wave: the grid holds 65 536 particles)
+    ('E_FUNNEL_NEAL', 31, 200003, 'MODE_MJHMC', 5),   #   the same with a persistent grid: every wave walks several tiles
     ('E_FUNNEL_NEAL', 21, 131, 'MODE_MJHMC', 70),     #   short rows; across the 64-iteration launch boundary
     ('E_FUNNEL_NEAL', 16, 700, 'MODE_MJHMC', 9),      #   two-lane groups, full rows
     ('E_FUNNEL_NEAL', 11, 65, 'MODE_MJHMC', 7),       #   two-lane groups, short rows
     ('E_ROUGH_WELL', 4, 48, 'MODE_MJHMC', 8),
     ('E_MM_GAUSS', 3, 40, 'MODE_MJHMC', 8),
     ('E_MM_GAUSS', 32, 300, 'MODE_MJHMC', 6),         # the mixture in row form too (round 6): full rows of four-lane groups,
-    ('E_MM_GAUSS', 27, 20011, 'MODE_MJHMC', 5),       #   short rows + a persistent grid (trajectory launch in row form on the single-iteration side),
+    ('E_MM_GAUSS', 27, 20011, 'MODE_MJHMC', 5),       #   short rows, a ragged last tile (trajectory launch in row form on the single-iteration side),
+    ('E_MM_GAUSS', 27, 200003, 'MODE_MJHMC', 5),      #   the same with a persistent grid walking several tiles,
     ('E_MM_GAUSS', 12, 700, 'MODE_MJHMC', 9),         #   two-lane groups
     ('E_ROUGH_WELL', 40, 200, 'MODE_CONTROL', 6),
     ('E_ISO_GAUSS', 16, 200, 'MODE_CONTROL', 12),
@@ -396,7 +398,8 @@ def test_split_fused_launch_other_sampler_families(mode_name, monkeypatch):
 @pytest.mark.parametrize('kind,D,N,n_iter,p_r,ring', [
     ('E_FUNNEL_NEAL', 32, 1000, 9, 0.05, False),      # four-wave workgroup tiles, the last one with three live waves and a ragged row count
     ('E_FUNNEL_NEAL', 32, 255, 6, 0.05, True),        # one workgroup tile, ragged; ring snapshots
-    ('E_FUNNEL_NEAL', 32, 20011, 5, 0.05, False),     # a persistent grid walking several workgroup tiles
+    ('E_FUNNEL_NEAL', 32, 20011, 5, 0.05, False),     # a grid of 79 workgroup tiles (below the 256 resident: one tile each)
+    ('E_FUNNEL_NEAL', 32, 200003, 5, 0.05, False),    # a persistent grid walking several workgroup tiles (above 65 536 particles)
     ('E_FUNNEL_NEAL', 32, 700, 8, 2.0, False),        # refresh rate 2: more than 32 cold caches per workgroup -- the pool overflows
     ('E_FUNNEL_NEAL', 31, 513, 7, 0.3, True),         #   every iteration, the lanes beyond it integrate in their own wave
     ('E_FUNNEL_NEAL', 21, 300, 70, 0.05, False),      # short rows; across the 64-iteration launch boundary

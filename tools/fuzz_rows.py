@@ -1,6 +1,8 @@
 """Random shapes through the row-form kernels of the funnels: a fused call (mjhmc_fused_rows_relay_kernel, ring snapshots included)
-against the same iterations one call at a time (below 16 384 particles: the jump kernel, a group of lanes per particle;
-above: the trajectory launch in row form + the jump-process launch) -- state, scalars, ring and counters bit for bit.
+against the same iterations one call at a time (below 16 384 particles: the group form's jump kernel, a group of lanes per
+particle; above: the trajectory launch in row form + the jump-process launch) -- state, scalars, ring and counters bit for
+bit.  Kernel against kernel only: tests/test_gpu_rows_oracle.py pins every one of these paths, the group form included,
+to the NumPy oracle.
 With the test build (MJHMC_HIP_LIB=.../libmjhmc_hip_test.so) and MJHMC_FORCE_RELAY=1 the relay kernel takes the short
 trajectories too (parts of one leapfrog step, empty parts).
 usage: python tools/fuzz_rows.py [seconds, default 60] [seed]"""
