@@ -14,8 +14,8 @@
 //
 // Working copy: between the passes of a trajectory the wave's X and V elements live in a per-workgroup scratch (2 x 32
 // rows = 256 KB per workgroup, 64 MB per launch: MALL-resident) in LANE-LINEAR 16-byte pieces, so the per-step passes are
-// fully coalesced (see Work<NB>); the particle rows are read by the first pass and written by the last drift (X) and
-// the closing kick (V) only.  A particle that takes the L move is finished when the trajectory is; one that does not
+// fully coalesced (see Work<NB>); the particle rows are read at the start of a trajectory and written at its end only,
+// staged through the idle B-operand images in LDS so that those accesses are coalesced too (staged_start, staged_end_*).  A particle that takes the L move is finished when the trajectory is; one that does not
 // gets its pre-move rows copied over at the end.
 // Traffic: 32 particles x 512 dims x 8 B x (X, V) x (read + write) = 512 KB per tile and leapfrog step = 3.5 B/clk/CU
 // beside ~146 000 cycles of gradient; at the CU's 64 B/clk vector-memory port that is 8 192 cycles per step.
@@ -179,6 +179,9 @@ void pot64_launch_jump(const Pot64JumpArgs& a, const PotModel& mdl, hipStream_t 
 }  // namespace mjhmc
 extern "C" int mjhmc_pot64_stamps(unsigned long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mjhmc::g_pot_stamp), sizeof(mjhmc::g_pot_stamp));
+}
+extern "C" int mjhmc_pot64_item_stamps(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mjhmc::g_pot_istamp), sizeof(mjhmc::g_pot_istamp));
 }
 namespace mjhmc {
 #endif

@@ -22,6 +22,7 @@
   const Work<NB> wk = work_of<NB>(a.scratch, blockIdx.x, w, lane);
   for (int64_t item = blockIdx.x; item < nft + a.ntiles; item += gridDim.x) {
     const bool inverse = item < nft;   // (uniform over the workgroup)
+    [[maybe_unused]] const int istamp_item = (int)(item / gridDim.x) & 15;   // (the timing build's POT_ISTAMP)
     auto column_of = [&](int64_t it) -> int64_t {
       if (it < nft) {
         const int64_t slot = it * kP + c;
@@ -39,30 +40,27 @@
     double EVL;
     {
       const int64_t p = column_of(item);
-      const size_t roff = (size_t)p * (128 * NB) + 32 * NB * w + 4 * NB * h;   // this lane's elements inside a [*][DIM] matrix
-      // the end point's position: into the output rows -- an inverse-L item's is wanted by nobody: into the second half of
-      // the workgroup's working rows (32 rows, the momentum's would-be working copy: unused)
-      auto xend = [&]() -> double* {
-        int64_t it = item;
-        asm volatile("" : "+s"(it));
-        const size_t lane_part = 32 * NB * w + 4 * NB * h;
-        return it < nft ? a.scratch + (size_t)blockIdx.x * (Work<NB>::kArea) + Work<NB>::kArea / 2 + (size_t)c * (128 * NB) + lane_part
-                        : a.X_out + (size_t)column_of(it) * (128 * NB) + lane_part;
-      };
-      tile_load_narrow<NB>(a.G_in + roff, g);
-      EVL = pot64_trajectory<NB, kXRows>(mdl, xp, ar, sh, w, c, h, lane, wk, a.X_in + roff, a.V_in + roff, xend, g, v, a.L, a.eps,
-                                         a.chalf, &exl, inverse);
+      POT_ISTAMP(0);
+      staged_start<NB>(sh.s, wk, a.X_in, a.V_in, a.G_in, p, w, c, h, g, v, inverse);
+      POT_ISTAMP(1);
+      EVL = pot64_trajectory<NB>(mdl, xp, ar, sh, w, c, h, lane, wk, g, v, a.L, a.eps, a.chalf, &exl);
+      POT_ISTAMP(2);
     }
     int64_t item_again = item;
     asm volatile("" : "+s"(item_again));
     const int64_t p = column_of(item_again);
     const bool alive = p < a.N;
     const size_t roff = (size_t)p * (128 * NB) + 32 * NB * w + 4 * NB * h;
+    // the end point's position: into the output rows -- an inverse-L item's is wanted by nobody and stays in the working
+    // copy (its last list tile is padded with a repeated column: two lanes' rows would be the same row)
+    if (!inverse) staged_end_x<NB>(sh.s, wk, a.X_out, p, w, c, h);
+    POT_ISTAMP(3);
     const double EXL = (double)exl;
     const double HL = EXL + EVL;
     if (inverse) {
       if (w == 0 && h == 0) a.Hwork[p] = HL;
       __syncthreads();
+      POT_ISTAMP(4);
       continue;
     }
 
@@ -74,21 +72,8 @@
         a.EX_out[p] = EXL;
         a.EV_out[p] = EVL;
       }
-      using DV = typename DVecN<NB>::type;
-      double* vo = a.V_out + roff;
-      double* go = a.G_out + roff;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        DV vv, gg;
-#pragma unroll
-        for (int r = 0; r < NB; ++r) {
-          dset<NB>(vv, r, v.b[r][q]);
-          dset<NB>(gg, r, (double)g.b[r][q]);
-        }
-        dv_store<NB>(vo, q, vv);
-        dv_store<NB>(go, q, gg);
-      }
-      __syncthreads();
+      staged_end_vg<NB>(sh.s, a.V_out, a.G_out, p, w, c, h, v, g);
+      POT_ISTAMP(4);
       continue;
     }
 
@@ -135,6 +120,7 @@
     __syncthreads();
     pot64_finish<NB, REPLAY, MODE, false>(a, sh, p, alive, roff, w, c, h, v, g);
     __syncthreads();
+    POT_ISTAMP(4);
   }
   __syncthreads();
   if (threadIdx.x == 0 && tally[4]) {

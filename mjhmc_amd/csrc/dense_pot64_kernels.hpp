@@ -60,17 +60,6 @@ __device__ __forceinline__ void dv_store(double* lrow, int q, const typename DVe
   *reinterpret_cast<typename DVecN<NB>::type*>(lrow + q_off<NB>(q)) = v;
 }
 
-// stored dE/dX (float64 rows holding float32 values) -> accumulator tile
-template <int NB>
-__device__ __forceinline__ void tile_load_narrow(const double* lrow, Tile<NB>& t) {
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const typename DVecN<NB>::type v = dv_load<NB>(lrow, q);
-#pragma unroll
-    for (int r = 0; r < NB; ++r) t.b[r][q] = (float)dget<NB>(v, r);
-  }
-}
-
 constexpr int kPark = 8;   // momentum elements per lane that sit out the GEMM loops in LDS (see pot64_trajectory)
 template <int NB>
 struct Shared64 {
@@ -85,8 +74,8 @@ struct Shared64 {
 // per-step passes is 64 lanes x 16 B = 1 KB contiguous.  In the particle-major rows themselves a wave instruction
 // touches 64 different 128-byte lines (lane = particle, 4 KB apart): the address pipe takes ~64 cycles per instruction
 // and, with 128 of them per wave and step, a first form that integrated in the rows spent 40 000 cycles per step there
-// (C3 21.3 ms instead of 16.6).  Rows are touched once per trajectory: read by the first pass, written by the last drift
-// (X) and the closing kick (V).
+// (C3 21.3 ms instead of 16.6).  Rows are touched once per trajectory, read and written through LDS (staged_start,
+// staged_end_x, staged_end_vg).
 // Accesses go through a buffer resource: scalar base + the lane's constant offset + a scalar piece offset.
 template <int NB>
 struct Work {
@@ -145,7 +134,110 @@ __device__ __forceinline__ void wk_store(const Work<NB>& k, unsigned area, int q
   }
 }
 
-constexpr int kXWork = 0, kXRows = 1;  // where a drift's X goes: the working copy, the rows xout
+// The particle rows at the two ends of a trajectory, staged through the B-operand images (Shared<NB>::pub: 32 KB x NB,
+// exactly the tile's 32 rows of DIM float64), which are idle there.  Read in the lanes' own accumulator layout a wave
+// instruction touches 64 rows 4 KB apart (64 cache lines: ~64 cycles of the address pipe); staged, every wave
+// instruction moves a contiguous 1 KB (512 B at NB = 1) of ONE row, and the lanes take or leave their elements in LDS.
+// LDS image: row-major, piece (16 B; 8 at NB = 1) k of row c at c * 1024 NB + (k ^ (c & 15)) * PB -- the XOR spreads the
+// 32 rows' elements of one register index over the banks (row starts are bank-aligned).
+template <int NB>
+struct PieceOf {
+  using type = uvec4;
+};
+template <>
+struct PieceOf<1> {
+  using type = unsigned long long;
+};
+template <int NB>
+struct Stage {
+  using P = typename PieceOf<NB>::type;
+  static constexpr int PB = sizeof(P);               // piece bytes
+  static constexpr int RB = 1024 * NB;               // row bytes
+  static constexpr int RP = RB / PB;                 // pieces per row: a multiple of 64 (a wave instruction: one row)
+  static constexpr int K = 32 * RP / 256;            // pieces per thread and array: 16 (NB = 1, 2), 32 (NB = 4)
+  static constexpr int KB = K < 16 ? K : 16;         // requests in flight per thread
+};
+__device__ __forceinline__ unsigned stage_addr(int row, int piece, int pb, int rb) {
+  return (unsigned)(row * rb + ((piece ^ (row & 15)) * pb));
+}
+// rows [p(c)] of `rows` ([*][DIM] float64; p: this lane's column's particle, columns = lanes 0..31) -> LDS image
+template <int NB>
+__device__ __forceinline__ void stage_rows_in(const double* rows, int64_t p, char* img) {
+  using S = Stage<NB>;
+  using P = typename S::P;
+  const int t = threadIdx.x;
+#pragma unroll 1
+  for (int i0 = 0; i0 < S::K; i0 += S::KB) {
+    P buf[S::KB];
+#pragma unroll
+    for (int i = 0; i < S::KB; ++i) {
+      const int k = (i0 + i) * 256 + t, row = k / S::RP, piece = k % S::RP;   // (row: uniform over the wave)
+      const int64_t pr = __shfl((long long)p, row);
+      buf[i] = *reinterpret_cast<const P*>(reinterpret_cast<const char*>(rows) + (size_t)pr * S::RB + (size_t)piece * S::PB);
+    }
+#pragma unroll
+    for (int i = 0; i < S::KB; ++i) {
+      const int k = (i0 + i) * 256 + t, row = k / S::RP, piece = k % S::RP;
+      *reinterpret_cast<P*>(img + stage_addr(row, piece, S::PB, S::RB)) = buf[i];
+    }
+  }
+}
+// LDS image -> rows [p(c)] of `rows`
+template <int NB>
+__device__ __forceinline__ void stage_rows_out(double* rows, int64_t p, const char* img) {
+  using S = Stage<NB>;
+  using P = typename S::P;
+  const int t = threadIdx.x;
+#pragma unroll 1
+  for (int i0 = 0; i0 < S::K; i0 += S::KB) {
+#pragma unroll
+    for (int i = 0; i < S::KB; ++i) {
+      const int k = (i0 + i) * 256 + t, row = k / S::RP, piece = k % S::RP;
+      const int64_t pr = __shfl((long long)p, row);
+      *reinterpret_cast<P*>(reinterpret_cast<char*>(rows) + (size_t)pr * S::RB + (size_t)piece * S::PB) =
+          *reinterpret_cast<const P*>(img + stage_addr(row, piece, S::PB, S::RB));
+    }
+  }
+}
+// this lane's NB doubles of register index q in the LDS image (its column's row, the accumulator layout's elements)
+template <int NB>
+__device__ __forceinline__ typename DVecN<NB>::type stage_get(const char* img, int w, int c, int h, int q) {
+  using S = Stage<NB>;
+  const int first = (8 * NB * (32 * w + acc_row(q, h))) / S::PB;
+  if constexpr (NB == 4) {
+    const f64x2 lo = *reinterpret_cast<const f64x2*>(img + stage_addr(c, first, S::PB, S::RB));
+    const f64x2 hi = *reinterpret_cast<const f64x2*>(img + stage_addr(c, first + 1, S::PB, S::RB));
+    typename DVecN<4>::type v;
+    v[0] = lo[0];
+    v[1] = lo[1];
+    v[2] = hi[0];
+    v[3] = hi[1];
+    return v;
+  } else {
+    return *reinterpret_cast<const typename DVecN<NB>::type*>(img + stage_addr(c, first, S::PB, S::RB));
+  }
+}
+template <int NB>
+__device__ __forceinline__ void stage_put(char* img, int w, int c, int h, int q, const typename DVecN<NB>::type& v) {
+  using S = Stage<NB>;
+  const int first = (8 * NB * (32 * w + acc_row(q, h))) / S::PB;
+  if constexpr (NB == 4) {
+    f64x2 lo, hi;
+    lo[0] = v[0];
+    lo[1] = v[1];
+    hi[0] = v[2];
+    hi[1] = v[3];
+    *reinterpret_cast<f64x2*>(img + stage_addr(c, first, S::PB, S::RB)) = lo;
+    *reinterpret_cast<f64x2*>(img + stage_addr(c, first + 1, S::PB, S::RB)) = hi;
+  } else {
+    *reinterpret_cast<typename DVecN<NB>::type*>(img + stage_addr(c, first, S::PB, S::RB)) = v;
+  }
+}
+template <int NB>
+__device__ __forceinline__ char* stage_image(Shared<NB>& s) {
+  static_assert(sizeof(s.pub) == 32 * Stage<NB>::RB, "the staging image is the two B-operand images");
+  return reinterpret_cast<char*>(&s.pub[0][0]);
+}
 
 // the wave's momentum elements, float64, in registers for the whole trajectory (accumulator layout: 2 x 16 NB registers)
 template <int NB>
@@ -154,46 +246,31 @@ struct VTile {
 };
 
 // One kick / drift pass over this wave's elements of the tile.  The momentum stays in registers; the position is
-// streamed through registers in four chunks of four register indices (double buffered: chunk n + 1 is in flight while
-// chunk n is worked on).
-//   NKICK = 1: v = [-]V_in + c g                    (the first step of a trajectory; neg: the F of F L F)
+// streamed through registers from the working copy in four chunks of four register indices (double buffered: chunk
+// n + 1 is in flight while chunk n is worked on).
+//   NKICK = 1: v = v + c g                          (the first step of a trajectory: v holds [-]V_in, staged_start)
 //   NKICK = 2: v = (v + c g) + c g                  (closing half kick of a step, opening one of the next)
-//   x = X + eps v ;  store x ;  float32(x) -> the X image of GEMM 1
-// FIRST: X, V come from the particle rows (the trajectory's first pass), else X from the working copy.  X goes to XDST
-// (the last drift's X is the end point: nothing reads it again but the caller).
+//   x = X + eps v ;  store x to the working copy ;  float32(x) -> the X image of GEMM 1
+// (the last drift's X is the end point: the caller takes it from the working copy, staged_end_x)
 // Every product is rounded before its sum (the library is built with -ffp-contract=off): NumPy's V += c * g.
-template <int NB, int NKICK, bool FIRST, int XDST>
-__device__ __forceinline__ void kick_drift_pass(const Work<NB>& wk, const double* xin, const double* vin, double* xout,
-                                                const Tile<NB>& g, VTile<NB>& v, double c, double eps, PubWave<NB>* pub0,
-                                                int w, int lane, bool neg = false) {
+template <int NB, int NKICK>
+__device__ __forceinline__ void kick_drift_pass(const Work<NB>& wk, const Tile<NB>& g, VTile<NB>& v, double c, double eps,
+                                                PubWave<NB>* pub0, int w, int lane) {
   using DV = typename DVecN<NB>::type;
-  DV xa[4], xb[4], va[4], vb[4];   // (va, vb: the first pass only)
-  auto load4 = [&](int q4, DV(&x)[4], DV(&vv)[4]) {
+  DV xa[4], xb[4];
+  auto load4 = [&](int q4, DV(&x)[4]) {
 #pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      if constexpr (FIRST) {
-        vv[qq] = dv_load<NB>(vin, 4 * q4 + qq);
-        x[qq] = dv_load<NB>(xin, 4 * q4 + qq);
-      } else {
-        x[qq] = wk_load<NB>(wk, wk.xb, 4 * q4 + qq);
-      }
-    }
+    for (int qq = 0; qq < 4; ++qq) x[qq] = wk_load<NB>(wk, wk.xb, 4 * q4 + qq);
   };
-  // the momentum first: it needs no memory (the first pass: only its own rows), so it runs while the X loads are in flight
-  auto kick4 = [&](int q4, DV(&vin4)[4]) {
+  // the momentum first: it needs no memory, so it runs while the X loads are in flight
+  auto kick4 = [&](int q4) {
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq) {
       const int q = 4 * q4 + qq;
 #pragma unroll
       for (int r = 0; r < NB; ++r) {
         const double t = c * (double)g.b[r][q];
-        double vv;
-        if constexpr (FIRST) {
-          vv = dget<NB>(vin4[qq], r);
-          vv = neg ? -vv : vv;   // (uniform over the workgroup: an inverse-L item of the jump launch)
-        } else {
-          vv = v.b[r][q];
-        }
+        double vv = v.b[r][q];
         vv = vv + t;
         if constexpr (NKICK == 2) vv = vv + t;
         v.b[r][q] = vv;
@@ -211,8 +288,7 @@ __device__ __forceinline__ void kick_drift_pass(const Work<NB>& wk, const double
         dset<NB>(x[qq], r, xx);
         px[r][qq] = (float)xx;
       }
-      if constexpr (XDST == kXWork) wk_store<NB>(wk, wk.xb, q, x[qq]);
-      else if constexpr (XDST == kXRows) dv_store<NB>(xout, q, x[qq]);
+      wk_store<NB>(wk, wk.xb, q, x[qq]);
     }
     if constexpr (NB == 4) {
       // this lane's slot of the X image, formed from the working copy's lane offset (which every load and store of the
@@ -231,23 +307,23 @@ __device__ __forceinline__ void kick_drift_pass(const Work<NB>& wk, const double
   };
   // (Measured: all four kick4 first, in the shadow of the first X loads, then the drifts -- more registers live across
   // the pass, 119 -> 283 spilled, C3 in this arithmetic 17.6 -> 18.7 ms.)
-  load4(0, xa, va);
-  load4(1, xb, vb);
+  load4(0, xa);
+  load4(1, xb);
   __builtin_amdgcn_sched_barrier(0);
-  kick4(0, va);
+  kick4(0);
   drift4(0, xa);
   __builtin_amdgcn_sched_barrier(0);
-  load4(2, xa, va);
+  load4(2, xa);
   __builtin_amdgcn_sched_barrier(0);
-  kick4(1, vb);
+  kick4(1);
   drift4(1, xb);
   __builtin_amdgcn_sched_barrier(0);
-  load4(3, xb, vb);
+  load4(3, xb);
   __builtin_amdgcn_sched_barrier(0);
-  kick4(2, va);
+  kick4(2);
   drift4(2, xa);
   __builtin_amdgcn_sched_barrier(0);
-  kick4(3, vb);
+  kick4(3);
   drift4(3, xb);
 }
 
@@ -278,20 +354,87 @@ __device__ __forceinline__ double column_sum(SH& sh, int w, int c, int h, double
   return tot;
 }
 
-// L >= 1 leapfrog steps (hmc_state.py:86-100) from the rows (xin, vin) and the stored dE/dX in g.  On return the end
-// point's position is in the rows xout (XLAST = kXRows; kXNone: not wanted; neg: start from -V, the F of F L F), its momentum in v, g holds its dE/dX (float32), *ex its
-// energy (float32, from the last gradient's u), and the return value is its kinetic energy sum(V^2) / 2 (all lanes of
-// column c).
-template <int NB, int XLAST, class XOut, class XP>
+// The start of a trajectory: the tile's rows (p: this lane's column's particle) through the staging image -- X into the
+// working copy, the stored dE/dX (float64 rows holding float32 values) into g, [-]V into v (neg: the F of F L F).
+// Barriers: the image is free on entry (the caller's last read of it stands behind a barrier) and on return.
+template <int NB>
+__device__ __forceinline__ void staged_start(Shared<NB>& s, const Work<NB>& wk, const double* xin, const double* vin,
+                                             const double* gin, int64_t p, int w, int c, int h, Tile<NB>& g, VTile<NB>& v,
+                                             bool neg) {
+  char* img = stage_image<NB>(s);
+  stage_rows_in<NB>(xin, p, img);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) wk_store<NB>(wk, wk.xb, q, stage_get<NB>(img, w, c, h, q));
+  __syncthreads();
+  stage_rows_in<NB>(gin, p, img);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const typename DVecN<NB>::type gg = stage_get<NB>(img, w, c, h, q);
+#pragma unroll
+    for (int r = 0; r < NB; ++r) g.b[r][q] = (float)dget<NB>(gg, r);
+  }
+  __syncthreads();
+  stage_rows_in<NB>(vin, p, img);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const typename DVecN<NB>::type vv = stage_get<NB>(img, w, c, h, q);
+#pragma unroll
+    for (int r = 0; r < NB; ++r) v.b[r][q] = neg ? -dget<NB>(vv, r) : dget<NB>(vv, r);   // (uniform: an inverse-L item)
+  }
+  __syncthreads();
+}
+
+// Rows out through the staging image: the end point's position (from the working copy, where the last drift left it),
+// its momentum, its dE/dX.  Barriers as staged_start's.
+template <int NB>
+__device__ __forceinline__ void staged_end_x(Shared<NB>& s, const Work<NB>& wk, double* xout, int64_t p, int w, int c, int h) {
+  char* img = stage_image<NB>(s);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) stage_put<NB>(img, w, c, h, q, wk_load<NB>(wk, wk.xb, q));
+  __syncthreads();
+  stage_rows_out<NB>(xout, p, img);
+  __syncthreads();
+}
+template <int NB>
+__device__ __forceinline__ void staged_end_vg(Shared<NB>& s, double* vout, double* gout, int64_t p, int w, int c, int h,
+                                              const VTile<NB>& v, const Tile<NB>& g) {
+  using DV = typename DVecN<NB>::type;
+  char* img = stage_image<NB>(s);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    DV vv;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) dset<NB>(vv, r, v.b[r][q]);
+    stage_put<NB>(img, w, c, h, q, vv);
+  }
+  __syncthreads();
+  stage_rows_out<NB>(vout, p, img);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    DV gg;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) dset<NB>(gg, r, (double)g.b[r][q]);
+    stage_put<NB>(img, w, c, h, q, gg);
+  }
+  __syncthreads();
+  stage_rows_out<NB>(gout, p, img);
+  __syncthreads();
+}
+
+// L >= 1 leapfrog steps (hmc_state.py:86-100) from the position in the working copy, the momentum in v and the stored
+// dE/dX in g (staged_start).  On return the end point's position is in the working copy (staged_end_x takes it to the
+// rows), its momentum in v, g holds its dE/dX (float32), *ex its energy (float32, from the last gradient's u), and the
+// return value is its kinetic energy sum(V^2) / 2 (all lanes of column c).
+template <int NB, class XP>
 __device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP& xp, AReg<NB>& ar, Shared64<NB>& sh, int w, int c, int h,
-                                                   int lane, const Work<NB>& wk, const double* xin, const double* vin,
-                                                   const XOut& xout_of, Tile<NB>& g, VTile<NB>& v, int L, double eps, double chalf,
-                                                   float* ex, bool neg) {
-  // xout_of(): the rows that take the end point's position, formed only where the last drift needs them (an address
-  // held across the GEMM loops and the streamed passes is two registers the kernel does not have)
+                                                   int lane, const Work<NB>& wk, Tile<NB>& g, VTile<NB>& v, int L, double eps,
+                                                   double chalf, float* ex) {
   PubWave<NB>* pub0 = sh.s.pub[0];   // the X images of the four waves (this wave's: pub0[w])
-  if (L == 1) kick_drift_pass<NB, 1, true, XLAST>(wk, xin, vin, xout_of(), g, v, chalf, eps, pub0, w, lane, neg);
-  else kick_drift_pass<NB, 1, true, kXWork>(wk, xin, vin, nullptr, g, v, chalf, eps, pub0, w, lane, neg);
+  kick_drift_pass<NB, 1>(wk, g, v, chalf, eps, pub0, w, lane);
   for (int s = 0; s < L; ++s) {
     [[maybe_unused]] const int stamp_slot = s;
     POT_STAMP(0);
@@ -324,8 +467,7 @@ __device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP
         for (int q = 0; q < 16; ++q) use_here(v.b[r][q]);
     }
     POT_STAMP(6);
-    if (s < L - 2) kick_drift_pass<NB, 2, false, kXWork>(wk, nullptr, nullptr, nullptr, g, v, chalf, eps, pub0, w, lane);
-    else if (s == L - 2) kick_drift_pass<NB, 2, false, XLAST>(wk, nullptr, nullptr, xout_of(), g, v, chalf, eps, pub0, w, lane);
+    if (s < L - 1) kick_drift_pass<NB, 2>(wk, g, v, chalf, eps, pub0, w, lane);
     POT_STAMP(7);
   }
   const double part = closing_kick<NB>(g, v, chalf);

@@ -13,8 +13,23 @@ static __device__ unsigned long long g_pot_stamp[4][8][8];
   do {                                                                                                        \
     if (blockIdx.x == 0 && lane == 0) g_pot_stamp[w][stamp_slot & 7][I] = __builtin_readcyclecounter();      \
   } while (0)
+// POT_ISTAMP(I): the float64-state kernel's item boundaries (dense_pot64_jump.inc), workgroup 0 of the launch whose
+// particles start at id 0, [wave][istamp_item: its item & 15][point]: the core clock at [I], the 100 MHz constant clock at [8 + I]
+// (the core clock's rate during the launch).  Points: 0 item start, 1 rows staged in, 2 trajectory done, 3 end point's
+// X stored, 4 the item's epilogue done.
+namespace mjhmc {
+static __device__ unsigned long long g_pot_istamp[4][16][16];
+}
+#define POT_ISTAMP(I)                                                                                         \
+  do {                                                                                                        \
+    if (blockIdx.x == 0 && lane == 0 && a.first_pid == 0) {                                                   \
+      g_pot_istamp[w][istamp_item][I] = __builtin_readcyclecounter();                                              \
+      g_pot_istamp[w][istamp_item][8 + (I)] = __builtin_amdgcn_s_memrealtime();                            \
+    }                                                                                                         \
+  } while (0)
 #else
 #define POT_STAMP(I) do { } while (0)
+#define POT_ISTAMP(I) do { } while (0)
 #endif
 
 // -DSIC_STAMPS=<k> (tools/sic_variants.sh <k>): cycle stamps (s_memtime = core clock) of four of workgroup 0's waves at
