@@ -304,6 +304,42 @@ int mjhmc_ring_read(mjhmc_sampler* s, int slot0, int n, int stacked, double* hos
  * (mjhmc/misc/gen_mj_init.py:76-98), which walks sampler.sample(1).ravel() value by value. */
 int mjhmc_ring_moments(mjhmc_sampler* s, int slot0, int n, double shift, double* sum, double* sumsq);
 
+/* Weighted sufficient statistics of ring blocks, kept on the device (csrc/estimators.hip): what a caller of
+ * sampler.sample() computes next in the reference -- online_variance (mjhmc/misc/gen_mj_init.py:76-98), posterior
+ * means and variances -- without the (ndims, n_samples * nbatch) download.  For states x[k][p][:] (ring slot
+ * x_slot0 + k, particle p < N), weights w[k][p] and a shift vector c of ndims doubles:
+ *   W = sum w,  S1_d = sum w (x_d - c_d),  S2_d = sum w (x_d - c_d)^2,  C_de = sum w (x_d - c_d)(x_e - c_e),
+ * all in float64, every state dtype widened exactly; the order of addition is fixed, so the result is bit-identical
+ * from run to run on one device.
+ * An estimator belongs to the sampler it was created on: mjhmc_sampler_destroy frees every estimator still alive on
+ * it, and the handle is INVALID from then on -- mjhmc_estimator_destroy (or any other call) on it after the sampler is
+ * gone is a use after free.  Destroy estimators first, or not at all.
+ * The sampler must have its ring (mjhmc_ring_alloc); want_cov != 0 also keeps the ndims x ndims matrix C and needs
+ * ndims <= 512 (MJHMC_ERR_INVALID beyond: first and second moments work for every ndims). */
+typedef struct mjhmc_estimator mjhmc_estimator;
+int mjhmc_estimator_create(mjhmc_sampler* s, int want_cov, mjhmc_estimator** out);
+int mjhmc_estimator_destroy(mjhmc_estimator* est);
+/* c: ndims finite doubles, NULL = zero (the state at create).  Only while the estimator is empty: sums about
+ * different shifts do not add (MJHMC_ERR_INVALID after an accumulate; mjhmc_estimator_reset first). */
+int mjhmc_estimator_set_shift(mjhmc_estimator* est, const double* c);
+/* Adds the n states of ring slots [x_slot0, x_slot0 + n) with the weights of dwell-ring slots [w_slot0, w_slot0 + n),
+ * or unit weights for w_slot0 == -1 (the discrete-time samplers).  The iteration that fills ring slot s writes the
+ * holding time of the state it LEFT (slot s - 1) to dwell slot s (mjhmc/samplers/markov_jump_hmc.py:262-277,
+ * 366-395: the rates are those of self.state before the update), so the holding time of the state in slot s is in
+ * dwell slot s + 1: a jump sampler's time average takes w_slot0 = x_slot0 + 1.
+ * MJHMC_ERR_INVALID: slots outside the ring, n < 1, or a ring re-allocated since mjhmc_estimator_create.
+ * MJHMC_ERR_NONFINITE: one of the weights is not finite (a zero total rate gives an infinite dwell); nothing of the
+ * block has been added. */
+int mjhmc_estimator_accumulate(mjhmc_estimator* est, int x_slot0, int w_slot0, int n);
+/* The only download: W, S1[ndims], S2[ndims], C[ndims * ndims] (row-major, symmetric bit for bit; NULL to skip, must
+ * be NULL for an estimator without covariance) and the number of (slot, particle) states added so far. */
+int mjhmc_estimator_read(mjhmc_estimator* est, double* W, double* S1, double* S2, double* C, int64_t* n_states);
+/* zero sums and count; the shift stays */
+int mjhmc_estimator_reset(mjhmc_estimator* est);
+/* Ring slot src_slot (state and dwelling times) copied to dst_slot on the device, on the sampler's stream: carries the
+ * last state of one block to the front of the next.  MJHMC_ERR_INVALID if dst_slot holds the live state. */
+int mjhmc_ring_copy(mjhmc_sampler* s, int src_slot, int dst_slot);
+
 /* The leapfrog operator on caller-supplied states: HMCState.leapfrog (n_steps = 1) and HMCState.L
  * (n_steps = num_leapfrog_steps) of mjhmc/samplers/hmc_state.py:86-100, in the reference's literal operation order
  * (half kicks not merged, every product rounded before its sum).  X, V and the outputs are (ndims, n) float64 C order

@@ -90,6 +90,13 @@ PROTOTYPES = {
     'mjhmc_ring_gather': (ctypes.c_int, [_P, _P, ctypes.c_int64, _P]),
     'mjhmc_ring_read': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_ring_moments': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _dp]),
+    'mjhmc_estimator_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
+    'mjhmc_estimator_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_estimator_set_shift': (ctypes.c_int, [_P, _P]),
+    'mjhmc_estimator_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_estimator_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_estimator_reset': (ctypes.c_int, [_P]),
+    'mjhmc_ring_copy': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
     'mjhmc_leapfrog': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _P, _P, _P, _P, _P]),
     'mjhmc_ring_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_autocor': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),
@@ -117,6 +124,7 @@ TEST_HOOKS_PATH = os.path.join(_HERE, 'lib', 'libmjhmc_hip_test.so')
 TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_gather_ring_local': (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_test_gather_columns_local': (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P]),
+    'mjhmc_test_ring_write_dwell': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, ctypes.c_double]),
 }
 
 _lib = None

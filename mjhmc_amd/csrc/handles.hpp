@@ -86,6 +86,7 @@ struct Shape {
 
 constexpr int kMaxDenseParts = 4;   // free-running parts of a dense batch (iterate_t)
 
+struct mjhmc_estimator;  // weighted-moment accumulator over ring blocks (estimators.hip)
 struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (api.hip)
 struct HostTraj;  // proposal workspace of a host-energy sampler (host_energy.hip)
 
@@ -148,6 +149,8 @@ struct mjhmc_sampler {
   void* ring = nullptr;
   double* dwell_ring = nullptr;
   int ring_slots = 0;
+  uint64_t ring_gen = 0;                      // counts the (re-)allocations of the ring: what an estimator was sized for
+  std::vector<mjhmc_estimator*> estimators;   // accumulators created on this sampler (estimators.hip); freed with it
   double* stage = nullptr;  // device staging, float64 host layout
   size_t stage_elems = 0;
   void* noise = nullptr;    // replay normals, particle-major
@@ -183,6 +186,9 @@ inline size_t row_bytes(const mjhmc_sampler* s) { return (size_t)s->sh.pitch * s
 inline size_t ssize(const mjhmc_sampler* s) { return s->dtype == MJHMC_F64 ? 8 : 4; }
 inline size_t mat_bytes(const mjhmc_sampler* s) { return (size_t)s->Npad * row_bytes(s); }
 
+
+// estimators.hip
+void estimator_free_all(mjhmc_sampler* s);
 
 // host_energy.hip
 void host_traj_free(mjhmc_sampler* s);

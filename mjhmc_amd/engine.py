@@ -369,6 +369,15 @@ class DeviceSampler(object):
         check(self.lib.mjhmc_ring_autocor(self.handle, int(slot0), int(n), 1 if linear else 0, ptr(out)), self.lib)
         return out
 
+    def ring_copy(self, src_slot, dst_slot):
+        """Ring slot ``src_slot`` (state and dwelling times) copied to ``dst_slot`` on the device."""
+        check(self.lib.mjhmc_ring_copy(self.handle, int(src_slot), int(dst_slot)), self.lib)
+
+    def estimator(self, want_cov=False):
+        """A weighted-moment accumulator over blocks of this sampler's ring (mjhmc_estimator_*): the sums stay on the
+        device between ``accumulate`` calls, ``read`` is the only download.  The ring must exist (ring_alloc)."""
+        return DeviceEstimator(self, want_cov)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -385,6 +394,50 @@ class DeviceSampler(object):
         if getattr(self, 'handle', None):
             self.lib.mjhmc_sampler_destroy(self.handle)
             self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceEstimator(object):
+    """W = sum w, S1 = sum w (x - c), S2 = sum w (x - c)^2 and, with ``want_cov``, C = sum w (x - c)(x - c)^T over the
+    (slot, particle) states of the ring blocks given to ``accumulate``; float64 throughout, bit-identical from run to run."""
+
+    def __init__(self, dev, want_cov=False):
+        self.dev, self.lib, self.want_cov = dev, dev.lib, bool(want_cov)
+        self.ndims = dev.ndims
+        h = ctypes.c_void_p()
+        check(self.lib.mjhmc_estimator_create(dev.handle, 1 if want_cov else 0, ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def set_shift(self, c=None):
+        c = None if c is None else as_f64(np.asarray(c, dtype=np.float64).reshape(-1), (self.ndims,))
+        check(self.lib.mjhmc_estimator_set_shift(self.handle, ptr(c)), self.lib)
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1)."""
+        check(self.lib.mjhmc_estimator_accumulate(self.handle, int(x_slot0), int(w_slot0), int(n)), self.lib)
+
+    def read(self):
+        """(W, S1 (D,), S2 (D,), C (D, D) or None, n_states)"""
+        D = self.ndims
+        W, n = ctypes.c_double(), ctypes.c_int64()
+        S1, S2 = np.empty(D), np.empty(D)
+        C = np.empty((D, D)) if self.want_cov else None
+        check(self.lib.mjhmc_estimator_read(self.handle, ctypes.byref(W), ptr(S1), ptr(S2), ptr(C), ctypes.byref(n)), self.lib)
+        return W.value, S1, S2, C, int(n.value)
+
+    def reset(self):
+        check(self.lib.mjhmc_estimator_reset(self.handle), self.lib)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+            self.lib.mjhmc_estimator_destroy(self.handle)
+        self.handle = None
 
     def __del__(self):
         try:

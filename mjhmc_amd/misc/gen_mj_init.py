@@ -52,6 +52,22 @@ def online_variance(sampler, distribution, var_steps=VAR_STEPS, block=256):
     return m2 / float(var_steps * distribution.nbatch * distribution.ndims - 1), sampler
 
 
+def weighted_variance(sampler, distribution, var_steps=VAR_STEPS):
+    """Pooled variance of every value of ``var_steps`` consecutive states, each state weighted by the time the process
+    stayed in it (``sampler.expectations``: per-dimension sums on the device, pooled here over the dimensions).
+    Returns (variance estimate, sampler), like ``online_variance``.
+
+    How the two differ for a jump sampler: ``online_variance`` mirrors the reference (gen_mj_init.py:76-98) and counts
+    every recorded state once, which for MarkovJumpHMC / ContinuousTimeHMC is the variance of the EMBEDDED chain -- its
+    states over-represent the places the process leaves quickly.  This one weights the state of ring slot s with the
+    holding time drawn for it (dwell slot s + 1) and so estimates the variance of the target itself.  For a
+    discrete-time sampler the weights are 1 and the two agree up to online_variance's n - 1 denominator (this one
+    divides by the total weight)."""
+    ex = sampler.expectations(var_steps)
+    grand = ex.mean.mean()
+    return float(np.mean(ex.var + ex.mean ** 2) - grand * grand), sampler
+
+
 def generate_initialization(distribution, burn_in_steps=BURN_IN_STEPS, var_steps=VAR_STEPS, seed=None):
     """gen_mj_init.py:14-52.  Returns (mjhmc_endpt, emc_var_estimate, true_var_estimate, control_endpt)."""
     assert burn_in_steps > var_steps

@@ -303,6 +303,18 @@ def gather_vector(comm, plan, local):
     return gather_state_columns(comm, plan, np.asarray(local, dtype=np.float64).reshape(1, -1))[0]
 
 
+def reduce_moment_sums(comm, sums):
+    """(W, S1, S2, C or None, n_states) of DeviceEstimator.read() summed over the shards: the weighted sums are additive
+    as long as every rank took them about the same shift (HMCBase.expectations broadcasts rank 0's)."""
+    W, S1, S2, C, n_states = sums
+    D = S1.size
+    flat = np.concatenate([[W], S1, S2] + ([] if C is None else [C.ravel()]))
+    flat = np.asarray(comm.allreduce_f64(flat, 'sum'), dtype=np.float64)
+    n_states = int(comm.allreduce_ints([n_states], 'sum')[0])
+    return (float(flat[0]), flat[1:1 + D].copy(), flat[1 + D:1 + 2 * D].copy(),
+            None if C is None else flat[1 + 2 * D:].reshape(D, D).copy(), n_states)
+
+
 def assemble_stacked(comm, plan, local, n, preserve_order):
     """HMCBase.sample / resample=False (markov_jump_hmc.py:166-173,331-338) from per-rank host blocks (the
     host-staged path of the torch shim; RcclComm gathers the device rings instead, see allgather_ring).

@@ -18,6 +18,21 @@ from .hmc_state import DeviceHMCState, HMCState
 MAX_RETRY_DEPTH = 60
 
 
+class Expectations(object):
+    """What ``expectations()`` returns: ``mean`` (D,), ``var`` (D,) and ``cov`` (D, D) or None -- weighted moments about
+    the true mean, normalised by ``total_weight`` (no n - 1 correction) -- the number of (slot, particle) states
+    ``n_states``, and the raw device sums ``W, S1, S2, C`` about ``shift`` they were computed from
+    (include/mjhmc_hip.h: mjhmc_estimator_read)."""
+
+    def __init__(self, W, S1, S2, C, n_states, shift):
+        self.W, self.S1, self.S2, self.C, self.shift = W, S1, S2, C, shift
+        self.total_weight, self.n_states = W, n_states
+        m1 = S1 / W
+        self.mean = shift + m1
+        self.var = S2 / W - m1 * m1
+        self.cov = None if C is None else C / W - np.outer(m1, m1)
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -332,6 +347,76 @@ class HMCBase(object):
         self._publish()
         return out
 
+    # the jump processes weight every state by its holding time (ContinuousTimeHMC); a discrete-time chain's states count once
+    _dwell_weighted = False
+
+    def expectations(self, n_iter, cov=False, block=None, shift=None):
+        """Mean, variance and (``cov=True``, ndims <= 512) covariance of ``n_iter`` consecutive states of every particle,
+        accumulated on the device: the host receives O(D) or O(D^2) numbers whatever the length of the run
+        (csrc/estimators.hip).  Returns an ``Expectations``.
+
+        Discrete-time samplers run ``n_iter`` iterations and count every state once.  The jump samplers weight the
+        state of ring slot s by the holding time the NEXT iteration draws for it (dwell slot s + 1), so they run
+        ``n_iter + 1`` iterations: the last one supplies the last holding time and its state is not counted.  Counters,
+        ``dwelling_times`` and the final state are what that many iterations of ``sample(resample=False)`` leave.
+
+        The run goes through the ring in blocks of ``block`` states (default: what the device holds).  ``shift``: the
+        vector the device sums are taken about (cancellation); None takes the first block's own mean, at the price of
+        reading that block twice.  The returned moments are about the true mean whatever the shift.  Sharded samplers
+        sum over ranks, use rank 0's shift and the smallest ``block`` of all ranks."""
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        lead = 1 if self._dwell_weighted else 0
+        if block is None:
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False) - lead
+        block = max(1, min(int(block), n_iter))
+        if self._comm is not None:
+            # _run is collective for the jump samplers: every rank must walk the run in the same blocks, whatever its own
+            # free memory or the caller's argument on that rank say
+            block = int(self._comm.allreduce_ints([block], 'min')[0])
+        self._dev.ring_alloc(block + lead)
+        est = self._dev.estimator(cov)
+        try:
+            if shift is not None:
+                shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
+                if shift.shape != (self.ndims,):
+                    raise ValueError('shift must have ndims = %d entries' % self.ndims)
+                if self._comm is not None:
+                    shift = self._comm.bcast(shift.copy(), 0)
+                est.set_shift(shift)
+            done = last = 0
+            while done < n_iter:
+                k = min(block, n_iter - done)
+                if not lead:
+                    self._run(k, ring_slot0=0, keep_trace=done > 0)
+                elif done == 0:
+                    self._run(k + 1, ring_slot0=0)         # states in slots 0 .. k, their holding times in 1 .. k (+ the next block's)
+                else:
+                    self._dev.ring_copy(last, 0)           # the state whose holding time the first iteration of this block draws
+                    self._run(k, ring_slot0=1, keep_trace=True)
+                est.accumulate(0, k, w_slot0=1 if lead else -1)
+                if shift is None:                          # the first block's own mean, then the same block again about it
+                    W, S1 = self._reduce_sums(est.read())[:2]
+                    shift = S1 / W
+                    est.reset()
+                    est.set_shift(shift)
+                    est.accumulate(0, k, w_slot0=1 if lead else -1)
+                last, done = k, done + k
+            self._publish()
+            if lead:
+                self._read_dwell()
+            W, S1, S2, C, n_states = self._reduce_sums(est.read())
+        finally:
+            est.close()
+        return Expectations(W, S1, S2, C, n_states, shift)
+
+    def _reduce_sums(self, sums):
+        if self._comm is None:
+            return sums
+        from ..parallel import reduce_moment_sums
+        return reduce_moment_sums(self._comm, sums)
+
     def _record(self, n_samples, replay=None):
         """Run n_samples iterations, snapshotting X after each into device ring slots [0, n_samples)."""
         self._dev.ring_alloc(n_samples)
@@ -379,6 +464,8 @@ class ContinuousTimeHMC(HMCBase):
                 'mjhmc_amd.misc.distributions.Distribution (same rule as the reference, '
                 'markov_jump_hmc.py:235-242).')
         self.dwelling_times = np.zeros(self.nbatch)
+
+    _dwell_weighted = True     # expectations(): time averages of the jump process, not of its embedded chain
 
     def transition_rates(self, Z1, Z2):
         Ediff = Z1.H() - Z2.H()
