@@ -340,6 +340,51 @@ int mjhmc_estimator_reset(mjhmc_estimator* est);
  * last state of one block to the front of the next.  MJHMC_ERR_INVALID if dst_slot holds the live state. */
 int mjhmc_ring_copy(mjhmc_sampler* s, int src_slot, int dst_slot);
 
+/* Per-chain weighted sums of ring blocks, kept on the device (csrc/chainstats.hip): what R-hat (plain and split) and
+ * the multi-chain effective sample size are made of.  The reference reaches them only through
+ * sample(preserve_order=True) (mjhmc/samplers/markov_jump_hmc.py:150-173, 293-338): the (ndims, nbatch, n) array on the
+ * host, reduced there.  For states x[k][p][:] (ring slot x_slot0 + k, chain = particle p < N), weights w[k][p] and a
+ * shift vector c of ndims doubles, per part h < n_parts (part = which half of the run, so that split R-hat sees the two
+ * halves of a chain as two chains) and per chain:
+ *   a0_p = sum_k w,  a1_pd = sum_k w (x_d - c_d),  a2_pd = sum_k w (x_d - c_d)^2
+ * in float64 (every state dtype widened exactly), in the fixed order
+ *   t = x - c;  u = w * t;  a1 = a1 + u;  a2 = a2 + u * t;  a0 = a0 + w          k ascending, from the stored sums,
+ * every product rounded before its sum: the sums are bit-identical to that sequence of IEEE float64 operations and do
+ * not depend on how a run is cut into accumulate calls.
+ * Ownership as for mjhmc_estimator: a chainstats belongs to the sampler it was created on, mjhmc_sampler_destroy frees
+ * it, and the handle is invalid from then on.  Device memory: n_parts * (2 * row pitch + 1) * Npad doubles.
+ * Replaces sample(preserve_order=True) + a host reduction (markov_jump_hmc.py:150-173, 293-338); n_parts is 1 or 2 and
+ * the sampler must have its ring. */
+typedef struct mjhmc_chainstats mjhmc_chainstats;
+int mjhmc_chainstats_create(mjhmc_sampler* s, int n_parts, mjhmc_chainstats** out);
+int mjhmc_chainstats_destroy(mjhmc_chainstats* cs);
+/* c: ndims finite doubles, NULL = zero (the state at create).  Only while every part is empty (MJHMC_ERR_INVALID after
+ * an accumulate; mjhmc_chainstats_reset first).  The reference has no counterpart: its host reduction of
+ * sample(preserve_order=True) (markov_jump_hmc.py:150-173, 293-338) is free to centre as it likes. */
+int mjhmc_chainstats_set_shift(mjhmc_chainstats* cs, const double* c);
+/* Adds the n states of ring slots [x_slot0, x_slot0 + n) to the chains' sums of `part`, with the weights of dwell-ring
+ * slots [w_slot0, w_slot0 + n) or unit weights for w_slot0 == -1: the pairing of mjhmc_estimator_accumulate (a jump
+ * sampler takes w_slot0 = x_slot0 + 1).  What appending the block to the array of sample(preserve_order=True)
+ * (markov_jump_hmc.py:150-173, 293-338) is on the host.
+ * MJHMC_ERR_INVALID: slots outside the ring, n < 1, part outside [0, n_parts), or a ring re-allocated since create.
+ * MJHMC_ERR_NONFINITE: a weight of a chain p < N is not finite; the sums are as before the call. */
+int mjhmc_chainstats_accumulate(mjhmc_chainstats* cs, int part, int x_slot0, int w_slot0, int n);
+/* The fold of one part, in a fixed order (bit-identical from run to run on one device), O(ndims) download.  With
+ * m_pd = a1_pd / a0_p and v_pd = a2_pd / a0_p - m_pd * m_pd over the chains p < N:
+ *   *n_chains = N, *n_states_per_chain = slots accumulated, *Sw = sum_p a0_p,
+ *   Sm[d] = sum_p m_pd, Sq[d] = sum_p m_pd^2, Sv[d] = sum_p v_pd          (ndims doubles each).
+ * All of them add over parts and over ranks.  MJHMC_ERR_INVALID for a part nothing was added to.  The host reduction
+ * of sample(preserve_order=True) (markov_jump_hmc.py:150-173, 293-338) over its last axis, then over chains. */
+int mjhmc_chainstats_read(mjhmc_chainstats* cs, int part, int64_t* n_chains, int64_t* n_states_per_chain, double* Sw,
+                          double* Sm, double* Sq, double* Sv);
+/* The per-chain sums themselves, O(N * ndims): a0 (N), a1 and a2 (ndims, N) float64 C order, the layout of every host
+ * array of the reference (a slice of sample(preserve_order=True), markov_jump_hmc.py:150-173, 293-338, reduced over
+ * its last axis).  Any of the three may be NULL. */
+int mjhmc_chainstats_read_chains(mjhmc_chainstats* cs, int part, double* a0, double* a1, double* a2);
+/* zero sums and counts of every part; the shift stays (a fresh sample(preserve_order=True),
+ * markov_jump_hmc.py:150-173, 293-338) */
+int mjhmc_chainstats_reset(mjhmc_chainstats* cs);
+
 /* The leapfrog operator on caller-supplied states: HMCState.leapfrog (n_steps = 1) and HMCState.L
  * (n_steps = num_leapfrog_steps) of mjhmc/samplers/hmc_state.py:86-100, in the reference's literal operation order
  * (half kicks not merged, every product rounded before its sum).  X, V and the outputs are (ndims, n) float64 C order

@@ -97,6 +97,13 @@ PROTOTYPES = {
     'mjhmc_estimator_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
     'mjhmc_estimator_reset': (ctypes.c_int, [_P]),
     'mjhmc_ring_copy': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_chainstats_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
+    'mjhmc_chainstats_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_chainstats_set_shift': (ctypes.c_int, [_P, _P]),
+    'mjhmc_chainstats_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_chainstats_read': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _dp, _P, _P, _P]),
+    'mjhmc_chainstats_read_chains': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _P]),
+    'mjhmc_chainstats_reset': (ctypes.c_int, [_P]),
     'mjhmc_leapfrog': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _P, _P, _P, _P, _P]),
     'mjhmc_ring_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_autocor': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),
@@ -125,6 +132,7 @@ TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_gather_ring_local': (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_test_gather_columns_local': (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P]),
     'mjhmc_test_ring_write_dwell': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, ctypes.c_double]),
+    'mjhmc_test_ring_write': (ctypes.c_int, [_P, ctypes.c_int, _P]),
 }
 
 _lib = None

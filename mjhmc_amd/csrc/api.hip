@@ -1054,6 +1054,7 @@ int mjhmc_sampler_destroy(mjhmc_sampler* s) {
   (void)hipSetDevice(s->ctx->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   estimator_free_all(s);
+  chainstats_free_all(s);
   void* ptrs[] = {s->flf_list, s->call_block, s->Hpre, s->Hwork, s->cold_list, s->pot64_scratch, s->Hspec[0], s->Hspec[1], s->Hspec_dump, s->Gbuf[0], s->Gbuf[1], s->Xbuf[0], s->Xbuf[1], s->Vbuf[0],  s->Vbuf[1], s->EX[0],     s->EX[1],  s->EV[0],
                   s->EV[1],   s->Hflf[0], s->Hflf[1],  s->dwell,  s->dwell_scratch,  s->trans,
                   s->ring,     s->dwell_ring, s->stage,  s->noise,  s->rexp,
@@ -2330,6 +2331,21 @@ int mjhmc_ring_read(mjhmc_sampler* s, int slot0, int n, int stacked, double* hos
   }
   return 0;
 }
+
+#ifdef MJHMC_TEST_HOOKS
+// test build only: a host (ndims, N) float64 block into ring slot `slot`, through the re-tiling every state upload takes
+// (synthetic chains with a known answer for the chain-statistics tests)
+extern "C" int mjhmc_test_ring_write(mjhmc_sampler* s, int slot, const double* X) {
+  if (!s || !X || slot < 0 || slot >= s->ring_slots) return fail(MJHMC_ERR_INVALID, "bad argument");
+  char* dst = (char*)s->ring + (size_t)slot * mat_bytes(s);
+  if ((char*)s->Xcur == dst) return fail(MJHMC_ERR_INVALID, "the slot holds the live state");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  if (s->undo_valid && (char*)s->undo_X == dst) s->undo_valid = false;
+  TRY(upload_matrix(s, X, dst));
+  HIPCHK(hipStreamSynchronize(s->stream));   // (X is the caller's for the duration of the call only)
+  return 0;
+}
+#endif
 
 int mjhmc_ring_moments(mjhmc_sampler* s, int slot0, int n, double shift, double* sum, double* sumsq) {
   if (!s || !sum || !sumsq) return fail(MJHMC_ERR_INVALID, "NULL argument");

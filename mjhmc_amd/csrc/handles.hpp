@@ -87,6 +87,7 @@ struct Shape {
 constexpr int kMaxDenseParts = 4;   // free-running parts of a dense batch (iterate_t)
 
 struct mjhmc_estimator;  // weighted-moment accumulator over ring blocks (estimators.hip)
+struct mjhmc_chainstats; // per-chain weighted sums over ring blocks (chainstats.hip)
 struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (api.hip)
 struct HostTraj;  // proposal workspace of a host-energy sampler (host_energy.hip)
 
@@ -151,6 +152,7 @@ struct mjhmc_sampler {
   int ring_slots = 0;
   uint64_t ring_gen = 0;                      // counts the (re-)allocations of the ring: what an estimator was sized for
   std::vector<mjhmc_estimator*> estimators;   // accumulators created on this sampler (estimators.hip); freed with it
+  std::vector<mjhmc_chainstats*> chainstats;  // per-chain accumulators created on this sampler (chainstats.hip); freed with it
   double* stage = nullptr;  // device staging, float64 host layout
   size_t stage_elems = 0;
   void* noise = nullptr;    // replay normals, particle-major
@@ -189,6 +191,9 @@ inline size_t mat_bytes(const mjhmc_sampler* s) { return (size_t)s->Npad * row_b
 
 // estimators.hip
 void estimator_free_all(mjhmc_sampler* s);
+
+// chainstats.hip
+void chainstats_free_all(mjhmc_sampler* s);
 
 // host_energy.hip
 void host_traj_free(mjhmc_sampler* s);

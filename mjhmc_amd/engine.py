@@ -378,6 +378,12 @@ class DeviceSampler(object):
         device between ``accumulate`` calls, ``read`` is the only download.  The ring must exist (ring_alloc)."""
         return DeviceEstimator(self, want_cov)
 
+    def chain_stats(self, n_parts=1):
+        """Per-chain weighted sums over blocks of this sampler's ring (mjhmc_chainstats_*): what R-hat and the
+        multi-chain effective sample size are made of.  ``n_parts`` = 2 keeps the two halves of a run apart (split
+        R-hat).  The ring must exist (ring_alloc); the sums take n_parts * (2 * row pitch + 1) * Npad * 8 bytes."""
+        return DeviceChainStats(self, n_parts)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -437,6 +443,60 @@ class DeviceEstimator(object):
     def close(self):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
             self.lib.mjhmc_estimator_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceChainStats(object):
+    """Per chain (particle) p and part h: a0 = sum_k w, a1 = sum_k w (x - c), a2 = sum_k w (x - c)^2 over the states
+    of the ring blocks given to ``accumulate``, in float64 and in a fixed operation order (include/mjhmc_hip.h:
+    mjhmc_chainstats_accumulate): bit-identical to the same float64 operations on the host, whatever the blocks."""
+
+    def __init__(self, dev, n_parts=1):
+        self.dev, self.lib, self.n_parts = dev, dev.lib, int(n_parts)
+        self.ndims, self.nparticles = dev.ndims, dev.nparticles
+        h = ctypes.c_void_p()
+        check(self.lib.mjhmc_chainstats_create(dev.handle, self.n_parts, ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def set_shift(self, c=None):
+        c = None if c is None else as_f64(np.asarray(c, dtype=np.float64).reshape(-1), (self.ndims,))
+        check(self.lib.mjhmc_chainstats_set_shift(self.handle, ptr(c)), self.lib)
+
+    def accumulate(self, x_slot0, n, w_slot0=-1, part=0):
+        """States of ring slots [x_slot0, x_slot0 + n) added to the chains' sums of ``part``, weights of dwell slots
+        [w_slot0, w_slot0 + n) (-1: unit weights; a jump sampler's time average takes w_slot0 = x_slot0 + 1)."""
+        check(self.lib.mjhmc_chainstats_accumulate(self.handle, int(part), int(x_slot0), int(w_slot0), int(n)), self.lib)
+
+    def read(self, part=0):
+        """The fold of one part over its chains: (n_chains, n_states_per_chain, Sw, Sm (D,), Sq (D,), Sv (D,)) = the
+        number of chains, the states each has, and the sums over chains of a0, of the chain means m = a1 / a0, of m^2
+        and of the chain variances a2 / a0 - m^2."""
+        D = self.ndims
+        M, n, Sw = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        Sm, Sq, Sv = np.empty(D), np.empty(D), np.empty(D)
+        check(self.lib.mjhmc_chainstats_read(self.handle, int(part), ctypes.byref(M), ctypes.byref(n), ctypes.byref(Sw),
+                                             ptr(Sm), ptr(Sq), ptr(Sv)), self.lib)
+        return int(M.value), int(n.value), Sw.value, Sm, Sq, Sv
+
+    def read_chains(self, part=0):
+        """(a0 (N,), a1 (D, N), a2 (D, N)): the per-chain sums themselves, an O(N * D) download"""
+        D, N = self.ndims, self.nparticles
+        a0, a1, a2 = np.empty(N), np.empty((D, N)), np.empty((D, N))
+        check(self.lib.mjhmc_chainstats_read_chains(self.handle, int(part), ptr(a0), ptr(a1), ptr(a2)), self.lib)
+        return a0, a1, a2
+
+    def reset(self):
+        check(self.lib.mjhmc_chainstats_reset(self.handle), self.lib)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+            self.lib.mjhmc_chainstats_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

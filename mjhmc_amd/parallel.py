@@ -315,6 +315,18 @@ def reduce_moment_sums(comm, sums):
             None if C is None else flat[1 + 2 * D:].reshape(D, D).copy(), n_states)
 
 
+def reduce_chain_sums(comm, parts):
+    """[(n_chains, n_states_per_chain, Sw, Sm, Sq, Sv) per part] of DeviceChainStats.read() summed over the shards in ONE
+    collective: the 3 * ndims + 2 sums of every part add over ranks (every chain is its own term), as long as every rank
+    took them about the same shift (HMCBase.diagnostics broadcasts rank 0's).  The number of chains travels as a float64
+    (exact below 2^53); the states per chain are the same on every rank."""
+    D = parts[0][3].size
+    flat = np.concatenate([np.concatenate([[float(M), Sw], Sm, Sq, Sv]) for M, _, Sw, Sm, Sq, Sv in parts])
+    flat = np.asarray(comm.allreduce_f64(flat, 'sum'), dtype=np.float64).reshape(len(parts), 3 * D + 2)
+    return [(int(row[0]), parts[h][1], float(row[1]), row[2:2 + D].copy(), row[2 + D:2 + 2 * D].copy(), row[2 + 2 * D:].copy())
+            for h, row in enumerate(flat)]
+
+
 def assemble_stacked(comm, plan, local, n, preserve_order):
     """HMCBase.sample / resample=False (markov_jump_hmc.py:166-173,331-338) from per-rank host blocks (the
     host-staged path of the torch shim; RcclComm gathers the device rings instead, see allgather_ring).

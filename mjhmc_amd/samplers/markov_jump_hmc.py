@@ -33,6 +33,50 @@ class Expectations(object):
         self.cov = None if C is None else C / W - np.outer(m1, m1)
 
 
+class Diagnostics(object):
+    """What ``diagnostics()`` returns: do the chains agree with each other, and how many independent draws are they worth.
+
+    Built from the per-part sums of ``DeviceChainStats.read()`` -- ``parts`` = [(n_chains, n_states_per_chain, Sw, Sm, Sq,
+    Sv), ...], already summed over ranks, all about ``shift``.  With ``M`` = chains x parts (``n_chains``), ``n`` = states
+    per chain and part (``n_states``), m = a chain's (weighted) mean and v its variance normalised by its weight, per
+    dimension:
+
+      chain_mean_avg = sum m / M                       between = (sum m^2 - M chain_mean_avg^2) / (M - 1)
+      within = sum v / M                               var_plus = within + between
+      rhat = sqrt((n - 1) / n * var_plus / within)     the potential scale reduction: the textbook
+                                                       sqrt(((n - 1) / n W + B / n) / W) with W = n / (n - 1) within and
+                                                       B / n = between, so one expression serves weighted chains too
+      ess_per_chain = var_plus / between               the variance of the chain means across chains IS var / ESS
+      ess = M * ess_per_chain                          NOT capped at M * n: antithetic chains may exceed it
+      mean = shift + chain_mean_avg
+
+    and the scalars ``total_weight`` (sum of all weights), ``grad_evals`` (the increase of ``distribution.dEdX_count`` over
+    the call), ``ess_per_grad = ess / grad_evals``, plus the raw sums ``Sw, Sm, Sq, Sv`` (added over parts) and ``parts``.
+    Every chain counts equally whatever its total holding time: chain_mean_avg is the plain average of the chain means,
+    not the pooled time average of ``expectations()``.  With ``M`` = 10^5 chains the relative standard error of
+    ``between``, and so of the ESS, is sqrt(2 / (M - 1)) = 0.45 %."""
+
+    def __init__(self, parts, shift, grad_evals=0):
+        self.parts = parts
+        self.shift = shift
+        self.n_chains = M = int(sum(p[0] for p in parts))
+        self.n_states = n = int(parts[0][1])
+        self.Sw = self.total_weight = float(sum(p[2] for p in parts))
+        self.Sm = sum(p[3] for p in parts)
+        self.Sq = sum(p[4] for p in parts)
+        self.Sv = sum(p[5] for p in parts)
+        self.chain_mean_avg = self.Sm / M
+        self.between = (self.Sq - M * self.chain_mean_avg * self.chain_mean_avg) / (M - 1)
+        self.within = self.Sv / M
+        self.var_plus = self.within + self.between
+        self.rhat = np.sqrt((n - 1.0) / n * self.var_plus / self.within)
+        self.ess_per_chain = self.var_plus / self.between
+        self.ess = M * self.ess_per_chain
+        self.mean = shift + self.chain_mean_avg
+        self.grad_evals = int(grad_evals)
+        self.ess_per_grad = self.ess / self.grad_evals if self.grad_evals else np.full_like(self.ess, np.nan)
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -379,22 +423,9 @@ class HMCBase(object):
         est = self._dev.estimator(cov)
         try:
             if shift is not None:
-                shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
-                if shift.shape != (self.ndims,):
-                    raise ValueError('shift must have ndims = %d entries' % self.ndims)
-                if self._comm is not None:
-                    shift = self._comm.bcast(shift.copy(), 0)
+                shift = self._checked_shift(shift)
                 est.set_shift(shift)
-            done = last = 0
-            while done < n_iter:
-                k = min(block, n_iter - done)
-                if not lead:
-                    self._run(k, ring_slot0=0, keep_trace=done > 0)
-                elif done == 0:
-                    self._run(k + 1, ring_slot0=0)         # states in slots 0 .. k, their holding times in 1 .. k (+ the next block's)
-                else:
-                    self._dev.ring_copy(last, 0)           # the state whose holding time the first iteration of this block draws
-                    self._run(k, ring_slot0=1, keep_trace=True)
+            for _, k in self._ring_blocks([n_iter], block):
                 est.accumulate(0, k, w_slot0=1 if lead else -1)
                 if shift is None:                          # the first block's own mean, then the same block again about it
                     W, S1 = self._reduce_sums(est.read())[:2]
@@ -402,7 +433,6 @@ class HMCBase(object):
                     est.reset()
                     est.set_shift(shift)
                     est.accumulate(0, k, w_slot0=1 if lead else -1)
-                last, done = k, done + k
             self._publish()
             if lead:
                 self._read_dwell()
@@ -410,6 +440,99 @@ class HMCBase(object):
         finally:
             est.close()
         return Expectations(W, S1, S2, C, n_states, shift)
+
+    def _checked_shift(self, shift):
+        shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
+        if shift.shape != (self.ndims,):
+            raise ValueError('shift must have ndims = %d entries' % self.ndims)
+        if self._comm is not None:
+            shift = self._comm.bcast(shift.copy(), 0)
+        return shift
+
+    def _ring_blocks(self, segments, block):
+        """The block walk of expectations() and diagnostics(): runs sum(segments) states of every particle through the
+        ring, at most ``block`` at a time and never across a segment boundary, and yields ``(segment, k)`` when the next k
+        states sit in ring slots 0 .. k - 1 -- for the jump samplers with their holding times in dwell slots 1 .. k (the
+        run's first block runs k + 1 iterations; every later one starts from a copy of the last state in the lead slot)."""
+        lead = 1 if self._dwell_weighted else 0
+        done = last = 0
+        for seg, length in enumerate(segments):
+            seg_done = 0
+            while seg_done < length:
+                k = min(block, length - seg_done)
+                if not lead:
+                    self._run(k, ring_slot0=0, keep_trace=done > 0)
+                elif done == 0:
+                    self._run(k + 1, ring_slot0=0)         # states in slots 0 .. k, their holding times in 1 .. k (+ the next block's)
+                else:
+                    self._dev.ring_copy(last, 0)           # the state whose holding time the first iteration of this block draws
+                    self._run(k, ring_slot0=1, keep_trace=True)
+                yield seg, k
+                last, done, seg_done = k, done + k, seg_done + k
+
+    def diagnostics(self, n_iter, split=True, block=None, shift=None):
+        """R-hat and the multi-chain effective sample size of ``n_iter`` consecutive states of every particle, every
+        particle being one chain: per-chain sums kept on the device (csrc/chainstats.hip), O(ndims) numbers to the host
+        whatever the length of the run and the number of chains.  Returns a ``Diagnostics``.
+
+        ``split=True`` (even ``n_iter`` >= 4) treats the two halves of every chain as two chains of ``n_iter / 2`` states
+        -- a chain that drifts disagrees with itself; ``split=False`` (``n_iter`` >= 2) takes the chains whole.  The run
+        itself is that of ``expectations(n_iter)``: the same iterations, the same weights (holding times for the jump
+        samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the same counters, ``dwelling_times`` and
+        final state, in blocks of ``block`` states that never straddle the half boundary.  ``shift``: the vector the
+        device sums are taken about; None takes the pooled mean of the first block (one extra moment pass over it, before
+        the chain sums start).  Sharded samplers sum over ranks, use rank 0's shift and the smallest ``block`` of all
+        ranks.  The per-chain sums take device memory (parts x (2 x row pitch + 1) x padded particles x 8 bytes): they
+        are created before the block size is taken from what the device has left."""
+        n_iter = int(n_iter)
+        if split and (n_iter < 4 or n_iter % 2):
+            raise ValueError('split=True needs an even n_iter >= 4, got %d' % n_iter)
+        if not split and n_iter < 2:
+            raise ValueError('n_iter must be >= 2, got %d' % n_iter)
+        if shift is not None and np.size(shift) != self.ndims:
+            raise ValueError('shift must have ndims = %d entries' % self.ndims)
+        lead = 1 if self._dwell_weighted else 0
+        segments = [n_iter // 2, n_iter // 2] if split else [n_iter]
+        grad0 = self.distribution.dEdX_count
+        self._dev.ring_alloc(1 + lead)                     # (the sums have the ring's row layout: it must exist)
+        cs = self._dev.chain_stats(len(segments))
+        try:
+            if block is None:
+                block = self._dev.ring_budget_slots(segments[0] + lead, staging=False) - lead
+            block = max(1, min(int(block), segments[0]))
+            if self._comm is not None:
+                block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
+            if block + lead > self._dev.ring_slots:
+                # a ring that grows is a new ring, and the sums belong to the one they were created on: free them, grow
+                # the ring by the budget that counted them, take them again
+                cs.close()
+                self._dev.ring_alloc(block + lead)
+                cs = self._dev.chain_stats(len(segments))
+            if shift is not None:
+                shift = self._checked_shift(shift)
+                cs.set_shift(shift)
+            w_slot0 = 1 if lead else -1
+            for part, k in self._ring_blocks(segments, block):
+                if shift is None:
+                    est = self._dev.estimator(False)
+                    try:
+                        est.accumulate(0, k, w_slot0=w_slot0)
+                        W, S1 = self._reduce_sums(est.read())[:2]
+                    finally:
+                        est.close()
+                    shift = S1 / W
+                    cs.set_shift(shift)
+                cs.accumulate(0, k, w_slot0=w_slot0, part=part)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            parts = [cs.read(h) for h in range(len(segments))]
+        finally:
+            cs.close()
+        if self._comm is not None:
+            from ..parallel import reduce_chain_sums
+            parts = reduce_chain_sums(self._comm, parts)
+        return Diagnostics(parts, shift, self.distribution.dEdX_count - grad0)
 
     def _reduce_sums(self, sums):
         if self._comm is None:

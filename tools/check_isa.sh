@@ -185,4 +185,31 @@ for name, body in re.findall(r'^(_ZN5mjhmc\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel'
 print('check_isa energy_funnel (row form): %s' % ('FAILED: %d kernel(s)' % bad if bad else 'ok'))
 sys.exit(1 if bad else 0)
 PY
+# The chain pass of the convergence diagnostics (chainstats.hip): a streaming pass whose lane keeps
+# its chain's sums in registers (a bfloat16 lane: 16 float64 accumulators, 8 shifts, the loads in flight) -- that fits
+# with room to spare, so scratch memory or a spilled register in any cs_*_kernel is a bug.
+[ -n "${SKIP_COMPILE:-}" ] || $HIPCC $FLAGS --cuda-device-only -S chainstats.hip -o /tmp/mjhmc_chainstats.s 2> /dev/null || { echo "compile of chainstats failed"; exit 2; }
+python3 - /tmp/mjhmc_chainstats.s <<'PY' || RC=1
+import re, sys
+txt = open(sys.argv[1]).read()
+bad = seen = 0
+for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.vgpr_spill_count:\s+(\d+)', txt, flags=re.S):
+    name, body = m.group(1), m.group(2)
+    if 'cs_' not in name:
+        continue
+    g = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, body).group(1))
+    scratch, sgpr_spill, vgpr, vgpr_spill = g('private_segment_fixed_size'), g('sgpr_spill_count'), g('vgpr_count'), int(m.group(3))
+    chain = 'cs_chain_kernel' in name
+    seen += chain
+    tag = ''
+    if scratch or sgpr_spill or vgpr_spill or (chain and vgpr > 128):     # (<= 128 VGPRs: four waves per SIMD at the least)
+        bad += 1
+        tag = '   <-- VIOLATION'
+    print('%-60s vgpr %3d spilled %3d scratch %4d B sgpr spills %3d%s' % (name[:60], vgpr, vgpr_spill, scratch, sgpr_spill, tag))
+if seen != 3:
+    bad += 1
+    print('expected the three instances of cs_chain_kernel (float64, float32, bfloat16 state), found %d' % seen)
+print('check_isa chainstats: %s' % ('FAILED: %d kernel(s)' % bad if bad else 'ok'))
+sys.exit(1 if bad else 0)
+PY
 exit $RC
