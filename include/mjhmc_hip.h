@@ -385,6 +385,38 @@ int mjhmc_chainstats_read_chains(mjhmc_chainstats* cs, int part, double* a0, dou
  * markov_jump_hmc.py:150-173, 293-338) */
 int mjhmc_chainstats_reset(mjhmc_chainstats* cs);
 
+/* Weighted marginal histograms of ring blocks, kept on the device (csrc/histograms.hip): medians, quantiles, credible
+ * intervals and a CDF of every dimension without downloading the states -- what np.histogram of the rows of
+ * sample(preserve_order=True) (markov_jump_hmc.py:150-173, 293-338), weighted by the holding times for the jump
+ * samplers, is on the host.  n_bins bins (1 .. 1024) between lo[d] and hi[d] (ndims finite doubles each, lo < hi) plus an
+ * underflow and an overflow bin per dimension; `quantum` q is a positive power of two.  With inv_d = n_bins / (hi_d -
+ * lo_d) in float64, for every state element x (widened exactly to float64) and its weight w:
+ *     t = (x - lo_d) * inv_d                      two rounded float64 operations, not fused
+ *     bin = 0 when !(t >= 0) (NaN lands here);  n_bins + 1 when t >= n_bins;  1 + (int)t otherwise
+ *     u = rint(w / q)                             nearest-even; the division is exact
+ *     count[d][bin] += 1;  mass[d][bin] += u      uint64 tables [ndims][n_bins + 2]
+ * and W_units += u once per state (the row sum of every mass[d]).  Every sum is an integer: the tables are bit-identical
+ * from run to run, do not depend on how a run is cut into blocks, and add exactly over ranks.
+ * |q * mass[d][b] - (sum of the w of bin b)| <= 0.5 * q * count[d][b].
+ * Ownership as for mjhmc_estimator: a histogram belongs to the sampler it was created on (and to its ring: a
+ * re-allocated ring invalidates it), mjhmc_sampler_destroy frees every one still alive and the handle is INVALID from
+ * then on. */
+typedef struct mjhmc_histogram mjhmc_histogram;
+int mjhmc_histogram_create(mjhmc_sampler* s, int n_bins, const double* lo, const double* hi, double quantum,
+                           mjhmc_histogram** out);
+int mjhmc_histogram_destroy(mjhmc_histogram* h);
+/* Adds the n states of ring slots [x_slot0, x_slot0 + n) with the weights of dwell-ring slots [w_slot0, w_slot0 + n),
+ * or unit weights for w_slot0 == -1: the pairing of mjhmc_estimator_accumulate (a jump sampler takes w_slot0 =
+ * x_slot0 + 1).  The weights are checked on the device ahead of the pass; a refused block adds nothing.
+ * MJHMC_ERR_INVALID: slots outside the ring, n < 1, a ring re-allocated since create, a weight with w / q >= 2^53, or a
+ * block that would take W_units to 2^63 or beyond.  MJHMC_ERR_NONFINITE: a weight that is not finite, or negative. */
+int mjhmc_histogram_accumulate(mjhmc_histogram* h, int x_slot0, int w_slot0, int n);
+/* count, mass: ndims * (n_bins + 2) values each, row d = [underflow, bin 0 .. n_bins - 1, overflow]; the total of the
+ * units and the number of (slot, particle) states added so far. */
+int mjhmc_histogram_read(mjhmc_histogram* h, uint64_t* count, uint64_t* mass, uint64_t* W_units, int64_t* n_states);
+/* zero tables and totals; range, bins and quantum stay */
+int mjhmc_histogram_reset(mjhmc_histogram* h);
+
 /* The leapfrog operator on caller-supplied states: HMCState.leapfrog (n_steps = 1) and HMCState.L
  * (n_steps = num_leapfrog_steps) of mjhmc/samplers/hmc_state.py:86-100, in the reference's literal operation order
  * (half kicks not merged, every product rounded before its sum).  X, V and the outputs are (ndims, n) float64 C order

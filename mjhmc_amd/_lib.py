@@ -104,6 +104,11 @@ PROTOTYPES = {
     'mjhmc_chainstats_read': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _dp, _P, _P, _P]),
     'mjhmc_chainstats_read_chains': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _P]),
     'mjhmc_chainstats_reset': (ctypes.c_int, [_P]),
+    'mjhmc_histogram_create': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_histogram_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_histogram_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_histogram_read': (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_histogram_reset': (ctypes.c_int, [_P]),
     'mjhmc_leapfrog': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _P, _P, _P, _P, _P]),
     'mjhmc_ring_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_autocor': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),
@@ -133,6 +138,7 @@ TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_gather_columns_local': (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P]),
     'mjhmc_test_ring_write_dwell': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, ctypes.c_double]),
     'mjhmc_test_ring_write': (ctypes.c_int, [_P, ctypes.c_int, _P]),
+    'mjhmc_test_ring_fill_padding': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
 }
 
 _lib = None

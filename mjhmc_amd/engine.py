@@ -384,6 +384,12 @@ class DeviceSampler(object):
         R-hat).  The ring must exist (ring_alloc); the sums take n_parts * (2 * row pitch + 1) * Npad * 8 bytes."""
         return DeviceChainStats(self, n_parts)
 
+    def histogram(self, bins, lo, hi, quantum=1.0):
+        """Weighted marginal histograms over blocks of this sampler's ring (mjhmc_histogram_*): ``bins`` bins between
+        ``lo`` and ``hi`` (scalars or ndims-vectors) plus an underflow and an overflow bin per dimension, integer counts
+        and integer masses in units of ``quantum`` (a power of two).  The ring must exist (ring_alloc)."""
+        return DeviceHistogram(self, bins, lo, hi, quantum)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -497,6 +503,51 @@ class DeviceChainStats(object):
     def close(self):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
             self.lib.mjhmc_chainstats_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceHistogram(object):
+    """Per dimension d and bin b: count[d][b] states and mass[d][b] = sum of rint(w / quantum) over the (slot, particle)
+    states of the ring blocks given to ``accumulate`` whose element x_d falls into bin b -- b = 0 below ``lo`` (and NaN),
+    bins + 1 from ``hi`` on, 1 + int((x - lo) * (bins / (hi - lo))) between (include/mjhmc_hip.h: mjhmc_histogram_create).
+    Integer sums: bit-identical from run to run, whatever the blocks."""
+
+    def __init__(self, dev, bins, lo, hi, quantum=1.0):
+        self.dev, self.lib = dev, dev.lib
+        self.ndims, self.bins, self.quantum = dev.ndims, int(bins), float(quantum)
+        self.lo = as_f64(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.ndims,)))
+        self.hi = as_f64(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.ndims,)))
+        h = ctypes.c_void_p()
+        check(self.lib.mjhmc_histogram_create(dev.handle, self.bins, ptr(self.lo), ptr(self.hi), self.quantum,
+                                              ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A refused block (a weight that is not finite, negative
+        or too large for the quantum) raises and adds nothing."""
+        check(self.lib.mjhmc_histogram_accumulate(self.handle, int(x_slot0), int(w_slot0), int(n)), self.lib)
+
+    def read(self):
+        """(count (D, bins + 2) uint64, mass (D, bins + 2) uint64 in units of the quantum, W_units, n_states)"""
+        shape = (self.ndims, self.bins + 2)
+        count, mass = np.empty(shape, dtype=np.uint64), np.empty(shape, dtype=np.uint64)
+        W, n = ctypes.c_uint64(), ctypes.c_int64()
+        check(self.lib.mjhmc_histogram_read(self.handle, ptr(count), ptr(mass), ctypes.byref(W), ctypes.byref(n)), self.lib)
+        return count, mass, int(W.value), int(n.value)
+
+    def reset(self):
+        check(self.lib.mjhmc_histogram_reset(self.handle), self.lib)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+            self.lib.mjhmc_histogram_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

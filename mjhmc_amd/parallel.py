@@ -327,6 +327,21 @@ def reduce_chain_sums(comm, parts):
             for h, row in enumerate(flat)]
 
 
+def reduce_histogram(comm, counts, units, W_units, n_states):
+    """(counts, units, W_units, n_states) of DeviceHistogram.read() summed over the shards in ONE integer collective: the
+    tables are integers, so the ranks add exactly as long as every rank binned with the same range and quantum
+    (HMCBase.marginals broadcasts rank 0's).  Every entry stays below 2^63 (the device refuses a block that would take a
+    rank's W_units there), so it travels as an int64; a sum over ranks that reaches 2^63 is an error."""
+    flat = np.concatenate([counts.ravel().astype(np.int64), units.ravel().astype(np.int64),
+                           np.array([W_units, n_states], dtype=np.int64)])
+    out = np.asarray(comm.allreduce_ints(flat, 'sum'), dtype=np.int64)
+    if np.any(out < 0):
+        raise OverflowError('the total weight of all ranks reaches 2^63 quanta: take a larger quantum')
+    m = counts.size
+    return (out[:m].astype(np.uint64).reshape(counts.shape), out[m:2 * m].astype(np.uint64).reshape(units.shape),
+            int(out[-2]), int(out[-1]))
+
+
 def assemble_stacked(comm, plan, local, n, preserve_order):
     """HMCBase.sample / resample=False (markov_jump_hmc.py:166-173,331-338) from per-rank host blocks (the
     host-staged path of the torch shim; RcclComm gathers the device rings instead, see allgather_ring).

@@ -77,6 +77,99 @@ class Diagnostics(object):
         self.ess_per_grad = self.ess / self.grad_evals if self.grad_evals else np.full_like(self.ess, np.nan)
 
 
+class Marginals(object):
+    """What ``marginals()`` returns: one weighted histogram per dimension, and the quantiles read off it.  Pure NumPy.
+
+    Built from the integer tables of ``DeviceHistogram.read()`` (already summed over ranks): ``counts`` and ``units``
+    (ndims, bins + 2) uint64 -- column 0 holds what fell below ``lo`` (and NaN), column bins + 1 what fell at or above
+    ``hi``, columns 1 .. bins the bins between, all of one width per dimension -- the total ``W_units`` and the number of
+    states ``n_states``.  ``quantum`` q is the weight of one unit:
+
+      mass = q * units                                 |mass - the bin's sum of weights| <= 0.5 q counts
+      total_weight = q * W_units                       every row of units adds up to W_units, exactly
+      edges (ndims, bins + 1)                          edges[d][j] = lo_d + j (hi_d - lo_d) / bins
+      density (ndims, bins)                            mass of the inner bins / (total_weight * bin width)
+      out_of_range (ndims,)                            the share of the weight in the two outer bins
+
+    ``cdf(x)`` is the piecewise-linear distribution function through the bin edges: exact (as a ratio of the integer sums)
+    at an edge, linear inside a bin, NaN outside [lo, hi].  ``quantile(p)`` is its inverse and raises ValueError when the
+    answer lies in an outer bin, where the histogram has no resolution; ``median`` and the equal-tailed
+    ``interval(level)`` are quantiles.  The device assigns bins by (x - lo) * (bins / (hi - lo)) in float64, so a state
+    within a rounding error of an edge may sit on either side of it."""
+
+    def __init__(self, lo, hi, bins, quantum, counts, units, W_units, n_states):
+        self.lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+        self.hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+        self.bins, self.quantum = int(bins), float(quantum)
+        self.ndims = self.lo.size
+        self.counts = np.asarray(counts, dtype=np.uint64).reshape(self.ndims, self.bins + 2)
+        self.units = np.asarray(units, dtype=np.uint64).reshape(self.ndims, self.bins + 2)
+        self.W_units, self.n_states = int(W_units), int(n_states)
+        self.mass = self.quantum * self.units.astype(np.float64)
+        self.total_weight = self.quantum * float(self.W_units)
+        self.width = (self.hi - self.lo) / self.bins
+        self.edges = self.lo[:, None] + np.arange(self.bins + 1)[None, :] * self.width[:, None]
+        self.edges[:, -1] = self.hi
+        W = float(self.W_units) if self.W_units else np.nan
+        self.density = self.units[:, 1:-1].astype(np.float64) / (W * self.width[:, None])
+        self.out_of_range = (self.units[:, 0].astype(np.float64) + self.units[:, -1].astype(np.float64)) / W
+        # the distribution function at the edges: units below the edge (the underflow bin included) / all units
+        self._F = np.cumsum(self.units[:, :-1], axis=1, dtype=np.uint64).astype(np.float64) / W
+
+    def _per_dim(self, v):
+        """scalar, (K,), (ndims, K) -> (ndims, K) and the shape to return"""
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0:
+            return np.broadcast_to(v, (self.ndims, 1)), (self.ndims,)
+        if v.ndim == 1:
+            return np.broadcast_to(v[None, :], (self.ndims, v.size)), (self.ndims, v.size)
+        if v.ndim == 2 and v.shape[0] == self.ndims:
+            return v, v.shape
+        raise ValueError('expected a scalar, a vector (applied to every dimension) or an (ndims, K) array, got shape %r' % (v.shape,))
+
+    def cdf(self, x):
+        """x: a scalar or a (K,) vector, taken for every dimension, or (ndims, K).  Returns (ndims,), (ndims, K)."""
+        X, shape = self._per_dim(x)
+        out = np.full(X.shape, np.nan)
+        for d in range(self.ndims):
+            e, F, xd = self.edges[d], self._F[d], X[d]
+            ok = (xd >= e[0]) & (xd <= e[-1])
+            j = np.clip(np.searchsorted(e, xd[ok], side='right') - 1, 0, self.bins - 1)
+            frac = (xd[ok] - e[j]) / (e[j + 1] - e[j])
+            out[d, ok] = np.where(frac >= 1.0, F[j + 1], F[j] + frac * (F[j + 1] - F[j]))
+        return out.reshape(shape)
+
+    def quantile(self, p):
+        """p in [0, 1]: a scalar or a (K,) vector, taken for every dimension, or (ndims, K).  The smallest x with
+        cdf(x) = p.  ValueError when it lies below ``lo`` or above ``hi`` in some dimension."""
+        P, shape = self._per_dim(p)
+        if np.any(~((P >= 0.0) & (P <= 1.0))):
+            raise ValueError('p must be in [0, 1]')
+        out = np.empty(P.shape)
+        for d in range(self.ndims):
+            e, F, pd = self.edges[d], self._F[d], P[d]
+            if np.any(pd < F[0]) or np.any(pd > F[-1]):
+                raise ValueError('dimension %d: the quantile lies in an outer bin (%.3g of the weight below lo = %g, %.3g at '
+                                 'or above hi = %g): widen the range' % (d, F[0], e[0], 1.0 - F[-1], e[-1]))
+            i = np.searchsorted(F, pd, side='left')          # F[i - 1] < p <= F[i]
+            j = np.maximum(i, 1) - 1
+            rise = F[j + 1] - F[j]
+            frac = np.where(i == 0, 0.0, (pd - F[j]) / np.where(rise > 0, rise, 1.0))
+            out[d] = np.where(frac >= 1.0, e[j + 1], e[j] + frac * (e[j + 1] - e[j]))
+        return out.reshape(shape)
+
+    @property
+    def median(self):
+        return self.quantile(0.5)
+
+    def interval(self, level=0.95):
+        """the equal-tailed interval that holds ``level`` of the weight: (lower (ndims,), upper (ndims,))"""
+        if not 0.0 < level < 1.0:
+            raise ValueError('level must be in (0, 1)')
+        tail = 0.5 * (1.0 - level)
+        return self.quantile(tail), self.quantile(1.0 - tail)
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -533,6 +626,77 @@ class HMCBase(object):
             from ..parallel import reduce_chain_sums
             parts = reduce_chain_sums(self._comm, parts)
         return Diagnostics(parts, shift, self.distribution.dEdX_count - grad0)
+
+    def marginals(self, n_iter, bins=256, range=None, block=None, span=8.0):
+        """Weighted histograms of every dimension over ``n_iter`` consecutive states of every particle, accumulated on
+        the device (csrc/histograms.hip): the host receives 2 x ndims x (bins + 2) integers whatever the length of the
+        run.  Returns a ``Marginals`` (quantiles, median, credible intervals, CDF).
+
+        The run itself is that of ``expectations(n_iter)``: the same iterations, the same weights (holding times for the
+        jump samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the same counters,
+        ``dwelling_times`` and final state, in blocks of ``block`` states.  ``range``: ``(lo, hi)``, scalars or
+        ndims-vectors; None takes mean -/+ ``span`` standard deviations from one moment pass over the first block.  The
+        jump samplers count weights in units of q = 2^(floor(log2(mean weight of the first block)) - 24); the others in
+        units of 1.  Sharded samplers use rank 0's range and quantum and the smallest ``block`` of all ranks, and add
+        their integer tables over ranks."""
+        n_iter, bins = int(n_iter), int(bins)
+        if n_iter < 1:
+            raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        if not 1 <= bins <= 1024:
+            raise ValueError('bins must be in [1, 1024], got %d' % bins)
+        if range is not None:
+            if len(range) != 2:
+                raise ValueError('range must be (lo, hi)')
+            lo, hi = [np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.ndims,))) if np.size(v) in (1, self.ndims)
+                      else None for v in range]
+            if lo is None or hi is None:
+                raise ValueError('lo and hi must be scalars or have ndims = %d entries' % self.ndims)
+            if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+                raise ValueError('range needs finite lo < hi in every dimension')
+        elif not span > 0:
+            raise ValueError('span must be positive')
+        lead = 1 if self._dwell_weighted else 0
+        if block is None:
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False) - lead
+        block = max(1, min(int(block), n_iter))
+        if self._comm is not None:
+            block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
+        self._dev.ring_alloc(block + lead)
+        w_slot0 = 1 if lead else -1
+        hist, q = None, 1.0
+        try:
+            for _, k in self._ring_blocks([n_iter], block):
+                if hist is None:
+                    if range is None or lead:
+                        est = self._dev.estimator(False)
+                        try:
+                            est.accumulate(0, k, w_slot0=w_slot0)
+                            W, S1, S2, _, n_first = self._reduce_sums(est.read())
+                        finally:
+                            est.close()
+                        if lead:
+                            q = 2.0 ** (np.floor(np.log2(W / n_first)) - 24)
+                        if range is None:
+                            mean = S1 / W
+                            sd = np.sqrt(np.maximum(S2 / W - mean * mean, 0.0))
+                            sd = np.where(sd > 0, sd, 1.0)             # (a constant coordinate still needs lo < hi)
+                            lo, hi = mean - span * sd, mean + span * sd
+                    if self._comm is not None:
+                        packed = self._comm.bcast(np.concatenate([lo, hi, [q]]), 0)
+                        lo, hi, q = packed[:self.ndims].copy(), packed[self.ndims:2 * self.ndims].copy(), float(packed[-1])
+                    hist = self._dev.histogram(bins, lo, hi, q)
+                hist.accumulate(0, k, w_slot0=w_slot0)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            counts, units, W_units, n_states = hist.read()
+        finally:
+            if hist is not None:
+                hist.close()
+        if self._comm is not None:
+            from ..parallel import reduce_histogram
+            counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
+        return Marginals(lo, hi, bins, q, counts, units, W_units, n_states)
 
     def _reduce_sums(self, sums):
         if self._comm is None:

@@ -212,4 +212,37 @@ if seen != 3:
 print('check_isa chainstats: %s' % ('FAILED: %d kernel(s)' % bad if bad else 'ok'))
 sys.exit(1 if bad else 0)
 PY
+# The histogram pass of marginals() (histograms.hip): a streaming pass whose lane holds its 16
+# bytes of kRowsInFlight rows, the range constants of its 2 / 4 / 8 dimensions and their LDS cell offsets -- no scratch
+# memory or spilled register in any hist_*_kernel, at most 128 VGPRs in the pass (four waves per SIMD at the least), and
+# the binning must be LDS integer atomics that return nothing (ds_add_u32 / ds_add_u64, no compare-and-swap loop).
+[ -n "${SKIP_COMPILE:-}" ] || $HIPCC $FLAGS --cuda-device-only -S histograms.hip -o /tmp/mjhmc_histograms.s 2> /dev/null || { echo "compile of histograms failed"; exit 2; }
+python3 - /tmp/mjhmc_histograms.s <<'PY' || RC=1
+import re, sys
+txt = open(sys.argv[1]).read()
+bad = seen = 0
+for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.vgpr_spill_count:\s+(\d+)', txt, flags=re.S):
+    name, body = m.group(1), m.group(2)
+    if 'hist_' not in name:
+        continue
+    g = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, body).group(1))
+    scratch, sgpr_spill, vgpr, vgpr_spill = g('private_segment_fixed_size'), g('sgpr_spill_count'), g('vgpr_count'), int(m.group(3))
+    hist = 'hist_kernel' in name
+    seen += hist
+    tag = ''
+    if scratch or sgpr_spill or vgpr_spill or (hist and vgpr > 128):
+        bad += 1
+        tag = '   <-- VIOLATION'
+    print('%-72s vgpr %3d spilled %3d scratch %4d B sgpr spills %3d%s' % (name[:72], vgpr, vgpr_spill, scratch, sgpr_spill, tag))
+if seen != 3:
+    bad += 1
+    print('expected the three instances of hist_kernel (float64, float32, bfloat16 state), found %d' % seen)
+n32, n64 = len(re.findall(r'^\s*ds_add_u32\b', txt, flags=re.M)), len(re.findall(r'^\s*ds_add_u64\b', txt, flags=re.M))
+loops = len(re.findall(r'cmpswap|ds_cmpst|ds_add_rtn', txt))
+print('LDS atomics: ds_add_u32 %d, ds_add_u64 %d, returning or compare-and-swap forms %d' % (n32, n64, loops))
+if not n32 or not n64 or loops:
+    bad += 1
+print('check_isa histograms: %s' % ('FAILED: %d violation(s)' % bad if bad else 'ok'))
+sys.exit(1 if bad else 0)
+PY
 exit $RC
