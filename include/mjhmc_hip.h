@@ -417,6 +417,52 @@ int mjhmc_histogram_read(mjhmc_histogram* h, uint64_t* count, uint64_t* mass, ui
 /* zero tables and totals; range, bins and quantum stay */
 int mjhmc_histogram_reset(mjhmc_histogram* h);
 
+/* Device functionals: statistics of caller expressions g(x) of the recorded states (csrc/functionals.hip), for which
+ * the reference has only sample(preserve_order=True) (markov_jump_hmc.py:150-173, 293-338) and NumPy on the host.  The
+ * coupled-energy convention of mjhmc_energy_create_expr_coupled, as an observable:
+ *     S[j] = sum_{d < ndims} stat_j(x_d, d; p)     j < J, 0 <= J <= 8
+ *     g[k] = value_k(S; p)                         k < K, 1 <= K <= 16
+ * `stats` and `values` hold C expressions separated by ';' (stats may be NULL or empty): a stat is an expression of `x`
+ * (the coordinate, widened exactly to float64 from a float64, float32 or bfloat16 ring), `d` (its index, int) and `p[m]`
+ * (the nparams float64 parameters); a value is an expression of `S[j]` and `p[m]`.  `d == 3 ? x : 0.0` picks a coordinate.
+ * Everything is float64 and compiled without contraction: an expression of + - * /, comparisons and ?: rounds operation
+ * by operation.  One kernel (csrc/functionals.hpp) evaluates a block of sample-ring slots into a DERIVED ring of float64
+ * rows [Npad][pitchK] -- the row layout of every sample ring, K "dimensions" -- and the accumulators created ON the
+ * functionals (mjhmc_estimator_create_on, ...) read that ring: their accumulate / set_shift / read / read_chains / reset
+ * / destroy entry points work unchanged, with x_slot0 a slot of the DERIVED ring, w_slot0 a slot of the SAMPLER's dwell
+ * ring, and K for ndims.
+ * The summation order of a stat is a function of the ring's row shape alone: values are bit-identical from run to run
+ * and do not depend on how a run is cut into blocks.  Rows p >= N are neither read nor written.
+ * Ownership: a functionals belongs to the sampler (mjhmc_sampler_destroy frees every one still alive) and to the sample
+ * ring it was created on (a re-allocated sample ring invalidates it); mjhmc_functionals_destroy frees the handles created
+ * on it, which are INVALID from then on.
+ * MJHMC_ERR_INVALID with a message: more than 8 stats, K outside [1, 16], NULL arguments, no sample ring yet, and
+ * expressions that do not compile (the hipRTC log is the message). */
+typedef struct mjhmc_functionals mjhmc_functionals;
+/* compiles the expressions for float64 rows of ndims and keeps nothing: needs no device */
+int mjhmc_functionals_check(int ndims, const char* stats, const char* values, const char* include_dir);
+int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* values, const double* params, size_t nparams,
+                             const char* include_dir, mjhmc_functionals** out);
+int mjhmc_functionals_destroy(mjhmc_functionals* f);
+/* K, and the bytes of one slot of the derived ring (Npad * pitchK * 8) */
+int mjhmc_functionals_info(mjhmc_functionals* f, int* n_values, uint64_t* slot_bytes);
+/* at least n_slots slots of derived ring, zeroed.  Never shrinks; a growth is a NEW ring (its contents are gone and the
+ * handles created on the old one refuse to accumulate) */
+int mjhmc_functionals_ring_alloc(mjhmc_functionals* f, int n_slots);
+/* Derived slots [out_slot0, out_slot0 + n) from the sampler's ring slots [x_slot0, x_slot0 + n), on the sampler's
+ * stream; reads a flag back (one synchronisation).  MJHMC_ERR_NONFINITE: a value of a particle p < N is not finite -- the
+ * message names the lowest such value index; the slots hold what was computed and should not be accumulated.
+ * MJHMC_ERR_INVALID: slots outside either ring, n < 1, no derived ring, a sample ring re-allocated since create. */
+int mjhmc_functionals_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out_slot0);
+/* host_out: (K, n, N) float64 C order, the values of derived slots [slot0, slot0 + n) (tests and inspection) */
+int mjhmc_functionals_read(mjhmc_functionals* f, int slot0, int n, double* host_out);
+/* mjhmc_estimator_create / mjhmc_chainstats_create / mjhmc_histogram_create on the derived ring (which must exist):
+ * K dimensions (lo, hi: K doubles each), the sampler's particles, stream and dwell ring */
+int mjhmc_estimator_create_on(mjhmc_functionals* f, int want_cov, mjhmc_estimator** out);
+int mjhmc_chainstats_create_on(mjhmc_functionals* f, int n_parts, mjhmc_chainstats** out);
+int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo, const double* hi, double quantum,
+                              mjhmc_histogram** out);
+
 /* The leapfrog operator on caller-supplied states: HMCState.leapfrog (n_steps = 1) and HMCState.L
  * (n_steps = num_leapfrog_steps) of mjhmc/samplers/hmc_state.py:86-100, in the reference's literal operation order
  * (half kicks not merged, every product rounded before its sum).  X, V and the outputs are (ndims, n) float64 C order

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-KERNEL_HEADERS = os.path.join(_HERE, 'csrc')     # elementwise.hpp / philox.hpp: what hipRTC compiles user expressions against
+KERNEL_HEADERS = os.path.join(_HERE, 'csrc')     # elementwise.hpp / philox.hpp / functionals.hpp: what hipRTC compiles user expressions against
 LIB_PATH = os.environ.get('MJHMC_HIP_LIB') or os.path.join(_HERE, 'lib', 'libmjhmc_hip.so')
 
 # enums of include/mjhmc_hip.h
@@ -109,6 +109,17 @@ PROTOTYPES = {
     'mjhmc_histogram_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'mjhmc_histogram_read': (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)]),
     'mjhmc_histogram_reset': (ctypes.c_int, [_P]),
+    'mjhmc_functionals_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
+    'mjhmc_functionals_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, _P, ctypes.c_size_t, ctypes.c_char_p,
+                                                ctypes.POINTER(_P)]),
+    'mjhmc_functionals_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_functionals_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
+    'mjhmc_functionals_ring_alloc': (ctypes.c_int, [_P, ctypes.c_int]),
+    'mjhmc_functionals_evaluate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_functionals_read': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P]),
+    'mjhmc_estimator_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
+    'mjhmc_chainstats_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
+    'mjhmc_histogram_create_on': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_leapfrog': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _P, _P, _P, _P, _P]),
     'mjhmc_ring_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_autocor': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),

@@ -1053,6 +1053,7 @@ int mjhmc_sampler_destroy(mjhmc_sampler* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->ctx->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
+  functionals_free_all(s);   // (and the handles created on them)
   estimator_free_all(s);
   chainstats_free_all(s);
   histogram_free_all(s);

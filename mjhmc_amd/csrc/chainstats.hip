@@ -35,6 +35,7 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "ring_source.hpp"
 
 namespace {
 
@@ -327,8 +328,10 @@ constexpr int kChainMaxParts = 2;
 
 struct mjhmc_chainstats {
   mjhmc_sampler* s = nullptr;
+  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
+  int D = 0, pitch = 0;       // dimensions and row pitch of a state of that ring
   int n_parts = 1;
-  uint64_t ring_gen = 0;      // the sampler's ring at create: the sums have its row layout
+  uint64_t ring_gen = 0;      // that ring at create: the sums have its row layout
   ChainFoldPlan plan;
   double* acc = nullptr;      // [n_parts] x { a0 [Npad], a1 [Npad][pitch], a2 [Npad][pitch] }
   double* shift = nullptr;    // [D]
@@ -336,15 +339,11 @@ struct mjhmc_chainstats {
   double* fout = nullptr;     // [1 + 3 D]
   int* bad = nullptr;
   int64_t n_slots[kChainMaxParts] = {0, 0};   // states per chain added to each part
-  size_t part_elems() const { return (size_t)(2 * s->sh.pitch + 1) * s->Npad; }
+  size_t part_elems() const { return (size_t)(2 * pitch + 1) * s->Npad; }
   double* a0(int h) const { return acc + (size_t)h * part_elems(); }
   double* a1(int h) const { return a0(h) + s->Npad; }
-  double* a2(int h) const { return a1(h) + (size_t)s->Npad * s->sh.pitch; }
+  double* a2(int h) const { return a1(h) + (size_t)s->Npad * pitch; }
 };
-
-static RingView chain_ring_view(const mjhmc_sampler* s, int slot0) {
-  return RingView{(const char*)s->ring + (size_t)slot0 * mat_bytes(s), s->dtype, s->Npad, s->N, s->D, s->sh.pitch};
-}
 
 static void chainstats_free(mjhmc_chainstats* cs) {
   for (void* p : {(void*)cs->acc, (void*)cs->shift, (void*)cs->fpart, (void*)cs->fout, (void*)cs->bad})
@@ -357,6 +356,17 @@ void chainstats_free_all(mjhmc_sampler* s) {
   s->chainstats.clear();
 }
 
+void chainstats_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
+  std::vector<mjhmc_chainstats*> keep;
+  for (mjhmc_chainstats* cs : s->chainstats) {
+    if (cs->fn == f)
+      chainstats_free(cs);
+    else
+      keep.push_back(cs);
+  }
+  s->chainstats.swap(keep);
+}
+
 static int chain_check_part(const mjhmc_chainstats* cs, int part) {
   if (!cs) return mjhmc_fail(MJHMC_ERR_INVALID, "chainstats is NULL");
   if (part < 0 || part >= cs->n_parts)
@@ -364,23 +374,26 @@ static int chain_check_part(const mjhmc_chainstats* cs, int part) {
   return 0;
 }
 
-extern "C" {
-
-int mjhmc_chainstats_create(mjhmc_sampler* s, int n_parts, mjhmc_chainstats** out) {
-  if (!s || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+static int chainstats_create_on_source(mjhmc_sampler* s, const mjhmc_functionals* fn, int n_parts, mjhmc_chainstats** out) {
   if (n_parts < 1 || n_parts > kChainMaxParts) return mjhmc_fail(MJHMC_ERR_INVALID, "n_parts must be 1 or 2");
-  if (!s->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  const RingSource src = ring_source(s, fn);
+  if (!src.base)
+    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
+                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
   // the chain pass addresses a slot in 16-byte chunks of the state's own type: rows must be whole chunks of it
-  const int vec = s->dtype == MJHMC_F64 ? 2 : (s->dtype == MJHMC_F32 ? 4 : 8);
-  if (s->sh.esize * vec != 16 || s->sh.pitch % vec != 0)
+  const int vec = src.dtype == MJHMC_F64 ? 2 : (src.dtype == MJHMC_F32 ? 4 : 8);
+  if (src.esize * vec != 16 || src.pitch % vec != 0)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
   HIPCHK(hipSetDevice(s->ctx->device));
   mjhmc_chainstats* cs = new mjhmc_chainstats();
   cs->s = s;
+  cs->fn = fn;
+  cs->D = src.D;
+  cs->pitch = src.pitch;
   cs->n_parts = n_parts;
-  cs->ring_gen = s->ring_gen;
-  cs->plan = chain_fold_plan(chain_ring_view(s, 0));
-  const size_t D = (size_t)s->D, acc_bytes = (size_t)n_parts * cs->part_elems() * sizeof(double);
+  cs->ring_gen = src.gen;
+  cs->plan = chain_fold_plan(ring_source_view(s, src, 0));
+  const size_t D = (size_t)src.D, acc_bytes = (size_t)n_parts * cs->part_elems() * sizeof(double);
   hipError_t e = hipMalloc((void**)&cs->acc, acc_bytes);
   if (e == hipSuccess) e = hipMalloc((void**)&cs->shift, D * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&cs->fpart, cs->plan.partial_elems * sizeof(double));
@@ -401,6 +414,18 @@ int mjhmc_chainstats_create(mjhmc_sampler* s, int n_parts, mjhmc_chainstats** ou
   s->chainstats.push_back(cs);
   *out = cs;
   return 0;
+}
+
+extern "C" {
+
+int mjhmc_chainstats_create(mjhmc_sampler* s, int n_parts, mjhmc_chainstats** out) {
+  if (!s || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  return chainstats_create_on_source(s, nullptr, n_parts, out);
+}
+
+int mjhmc_chainstats_create_on(mjhmc_functionals* f, int n_parts, mjhmc_chainstats** out) {
+  if (!f || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  return chainstats_create_on_source(functionals_sampler(f), f, n_parts, out);
 }
 
 int mjhmc_chainstats_destroy(mjhmc_chainstats* cs) {
@@ -430,9 +455,9 @@ int mjhmc_chainstats_set_shift(mjhmc_chainstats* cs, const double* c) {
       return mjhmc_fail(MJHMC_ERR_INVALID, "the shift belongs to the sums already accumulated: mjhmc_chainstats_reset first");
   mjhmc_sampler* s = cs->s;
   HIPCHK(hipSetDevice(s->ctx->device));
-  const size_t bytes = (size_t)s->D * sizeof(double);
+  const size_t bytes = (size_t)cs->D * sizeof(double);
   if (c) {
-    for (int d = 0; d < s->D; ++d)
+    for (int d = 0; d < cs->D; ++d)
       if (!std::isfinite(c[d])) return mjhmc_fail(MJHMC_ERR_INVALID, "shift entry " + std::to_string(d) + " is not finite");
     HIPCHK(hipMemcpyAsync(cs->shift, c, bytes, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));   // (c is the caller's for the duration of the call only)
@@ -445,12 +470,13 @@ int mjhmc_chainstats_set_shift(mjhmc_chainstats* cs, const double* c) {
 int mjhmc_chainstats_accumulate(mjhmc_chainstats* cs, int part, int x_slot0, int w_slot0, int n) {
   TRY(chain_check_part(cs, part));
   mjhmc_sampler* s = cs->s;
-  if (cs->ring_gen != s->ring_gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "the sample ring was re-allocated after mjhmc_chainstats_create: create a new one");
+  const RingSource src = ring_source(s, cs->fn);
+  if (cs->ring_gen != src.gen)
+    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_chainstats_create: create a new one");
   if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > s->ring_slots)
+  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
     return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots));
+                                             ") are outside the ring of " + std::to_string(src.slots));
   if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
     return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
                                              ") are outside the ring of " + std::to_string(s->ring_slots) +
@@ -458,7 +484,7 @@ int mjhmc_chainstats_accumulate(mjhmc_chainstats* cs, int part, int x_slot0, int
   HIPCHK(hipSetDevice(s->ctx->device));
   const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
   std::string err;
-  const int rc = chain_accumulate(s->stream, chain_ring_view(s, x_slot0), n, w, cs->shift, cs->a0(part), cs->a1(part),
+  const int rc = chain_accumulate(s->stream, ring_source_view(s, src, x_slot0), n, w, cs->shift, cs->a0(part), cs->a1(part),
                                   cs->a2(part), cs->bad, err);
   if (rc) return mjhmc_fail(rc, err);
   if (w) {   // (unit weights raise no flag: nothing to wait for)
@@ -485,10 +511,11 @@ int mjhmc_chainstats_read(mjhmc_chainstats* cs, int part, int64_t* n_chains, int
   mjhmc_sampler* s = cs->s;
   HIPCHK(hipSetDevice(s->ctx->device));
   std::string err;
-  const int rc = chain_fold(s->stream, chain_ring_view(s, 0), cs->plan, cs->a0(part), cs->a1(part), cs->a2(part), cs->fpart,
+  // (the fold reads the per-chain sums, not the ring: the view gives it N, D and the pitch)
+  const int rc = chain_fold(s->stream, ring_source_view(s, ring_source(s, cs->fn), 0), cs->plan, cs->a0(part), cs->a1(part), cs->a2(part), cs->fpart,
                             cs->fout, err);
   if (rc) return mjhmc_fail(rc, err);
-  const size_t D = (size_t)s->D;
+  const size_t D = (size_t)cs->D;
   std::vector<double> h(1 + 3 * D);
   HIPCHK(hipMemcpyAsync(h.data(), cs->fout, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
@@ -506,14 +533,14 @@ int mjhmc_chainstats_read_chains(mjhmc_chainstats* cs, int part, double* a0, dou
   mjhmc_sampler* s = cs->s;
   HIPCHK(hipSetDevice(s->ctx->device));
   if (a0) TRY(copy_to_host(s, cs->a0(part), a0, (size_t)s->N * sizeof(double)));
-  const size_t elems = (size_t)s->D * s->N;
+  const size_t elems = (size_t)cs->D * s->N;
   double* const host[2] = {a1, a2};
   const double* const dev[2] = {cs->a1(part), cs->a2(part)};
   for (int m = 0; m < 2; ++m) {
     if (!host[m]) continue;
     TRY(ensure_stage(s, elems));
-    const dim3 grid((unsigned)((s->N + 31) / 32), (unsigned)((s->D + 31) / 32)), block(32, 8);
-    hipLaunchKernelGGL(cs_to_dim_major, grid, block, 0, s->stream, dev[m], s->stage, s->D, s->N, s->sh.pitch);
+    const dim3 grid((unsigned)((s->N + 31) / 32), (unsigned)((cs->D + 31) / 32)), block(32, 8);
+    hipLaunchKernelGGL(cs_to_dim_major, grid, block, 0, s->stream, dev[m], s->stage, cs->D, s->N, cs->pitch);
     HIPCHK(hipGetLastError());
     TRY(copy_to_host(s, s->stage, host[m], elems * sizeof(double)));
   }

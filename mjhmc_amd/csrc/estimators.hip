@@ -37,6 +37,7 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "ring_source.hpp"
 
 namespace {
 
@@ -417,8 +418,10 @@ int estimator_cov(hipStream_t st, const RingView& r, int n, const double* w, con
 // ---------------------------------------------------------------------------------------------------------------------
 struct mjhmc_estimator {
   mjhmc_sampler* s = nullptr;
+  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
+  int D = 0;                  // dimensions of a state of that ring
   bool want_cov = false;
-  uint64_t ring_gen = 0;      // the sampler's ring at create: the plan and the scratch buffers are sized for it
+  uint64_t ring_gen = 0;      // that ring at create: the plan and the scratch buffers are sized for it
   EstimatorPlan plan;
   double* acc = nullptr;      // [1 + 2 D]: W, S1, S2
   double* C = nullptr;        // [D][D]
@@ -429,9 +432,6 @@ struct mjhmc_estimator {
   int64_t n_states = 0;
 };
 
-static RingView ring_view(const mjhmc_sampler* s, int slot0) {
-  return RingView{(const char*)s->ring + (size_t)slot0 * mat_bytes(s), s->dtype, s->Npad, s->N, s->D, s->sh.pitch};
-}
 
 static void estimator_free(mjhmc_estimator* est) {
   for (void* p : {(void*)est->acc, (void*)est->C, (void*)est->shift, (void*)est->mpart, (void*)est->cpart, (void*)est->bad})
@@ -444,21 +444,34 @@ void estimator_free_all(mjhmc_sampler* s) {
   s->estimators.clear();
 }
 
-extern "C" {
+void estimator_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
+  std::vector<mjhmc_estimator*> keep;
+  for (mjhmc_estimator* est : s->estimators) {
+    if (est->fn == f)
+      estimator_free(est);
+    else
+      keep.push_back(est);
+  }
+  s->estimators.swap(keep);
+}
 
-int mjhmc_estimator_create(mjhmc_sampler* s, int want_cov, mjhmc_estimator** out) {
-  if (!s || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
-  if (!s->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
-  if (want_cov && s->D > kEstimatorMaxCovDims)
+static int estimator_create_on_source(mjhmc_sampler* s, const mjhmc_functionals* fn, int want_cov, mjhmc_estimator** out) {
+  const RingSource src = ring_source(s, fn);
+  if (!src.base)
+    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
+                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  if (want_cov && src.D > kEstimatorMaxCovDims)
     return mjhmc_fail(MJHMC_ERR_INVALID, "the covariance pass takes at most " + std::to_string(kEstimatorMaxCovDims) +
-                                             " dims (ndims = " + std::to_string(s->D) + "): ask for the moments only");
+                                             " dims (ndims = " + std::to_string(src.D) + "): ask for the moments only");
   HIPCHK(hipSetDevice(s->ctx->device));
   mjhmc_estimator* est = new mjhmc_estimator();
   est->s = s;
+  est->fn = fn;
+  est->D = src.D;
   est->want_cov = want_cov != 0;
-  est->ring_gen = s->ring_gen;
-  est->plan = estimator_plan(ring_view(s, 0), est->want_cov);
-  const size_t D = (size_t)s->D;
+  est->ring_gen = src.gen;
+  est->plan = estimator_plan(ring_source_view(s, src, 0), est->want_cov);
+  const size_t D = (size_t)src.D;
   hipError_t e = hipMalloc((void**)&est->acc, (1 + 2 * D) * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&est->shift, D * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&est->mpart, est->plan.moment_partial_elems * sizeof(double));
@@ -480,6 +493,18 @@ int mjhmc_estimator_create(mjhmc_sampler* s, int want_cov, mjhmc_estimator** out
   return 0;
 }
 
+extern "C" {
+
+int mjhmc_estimator_create(mjhmc_sampler* s, int want_cov, mjhmc_estimator** out) {
+  if (!s || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  return estimator_create_on_source(s, nullptr, want_cov, out);
+}
+
+int mjhmc_estimator_create_on(mjhmc_functionals* f, int want_cov, mjhmc_estimator** out) {
+  if (!f || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  return estimator_create_on_source(functionals_sampler(f), f, want_cov, out);
+}
+
 int mjhmc_estimator_destroy(mjhmc_estimator* est) {
   if (!est) return 0;
   mjhmc_sampler* s = est->s;
@@ -494,7 +519,7 @@ int mjhmc_estimator_reset(mjhmc_estimator* est) {
   if (!est) return mjhmc_fail(MJHMC_ERR_INVALID, "estimator is NULL");
   mjhmc_sampler* s = est->s;
   HIPCHK(hipSetDevice(s->ctx->device));
-  const size_t D = (size_t)s->D;
+  const size_t D = (size_t)est->D;
   HIPCHK(hipMemsetAsync(est->acc, 0, (1 + 2 * D) * sizeof(double), s->stream));
   if (est->want_cov) HIPCHK(hipMemsetAsync(est->C, 0, D * D * sizeof(double), s->stream));
   HIPCHK(hipMemsetAsync(est->bad, 0, sizeof(int), s->stream));
@@ -508,9 +533,9 @@ int mjhmc_estimator_set_shift(mjhmc_estimator* est, const double* c) {
     return mjhmc_fail(MJHMC_ERR_INVALID, "the shift belongs to the sums already accumulated: mjhmc_estimator_reset first");
   mjhmc_sampler* s = est->s;
   HIPCHK(hipSetDevice(s->ctx->device));
-  const size_t bytes = (size_t)s->D * sizeof(double);
+  const size_t bytes = (size_t)est->D * sizeof(double);
   if (c) {
-    for (int d = 0; d < s->D; ++d)
+    for (int d = 0; d < est->D; ++d)
       if (!std::isfinite(c[d])) return mjhmc_fail(MJHMC_ERR_INVALID, "shift entry " + std::to_string(d) + " is not finite");
     HIPCHK(hipMemcpyAsync(est->shift, c, bytes, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));   // (c is the caller's for the duration of the call only)
@@ -523,18 +548,19 @@ int mjhmc_estimator_set_shift(mjhmc_estimator* est, const double* c) {
 int mjhmc_estimator_accumulate(mjhmc_estimator* est, int x_slot0, int w_slot0, int n) {
   if (!est) return mjhmc_fail(MJHMC_ERR_INVALID, "estimator is NULL");
   mjhmc_sampler* s = est->s;
-  if (est->ring_gen != s->ring_gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "the sample ring was re-allocated after mjhmc_estimator_create: create a new estimator");
+  const RingSource src = ring_source(s, est->fn);
+  if (est->ring_gen != src.gen)
+    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_estimator_create: create a new estimator");
   if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > s->ring_slots)
+  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
     return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots));
+                                             ") are outside the ring of " + std::to_string(src.slots));
   if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
     return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
                                              ") are outside the ring of " + std::to_string(s->ring_slots) +
                                              " (-1 asks for unit weights)");
   HIPCHK(hipSetDevice(s->ctx->device));
-  const RingView view = ring_view(s, x_slot0);
+  const RingView view = ring_source_view(s, src, x_slot0);
   const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
   std::string err;
   int rc = estimator_moments(s->stream, view, n, w, est->shift, est->plan, est->mpart, est->acc, est->bad, err);
@@ -558,7 +584,7 @@ int mjhmc_estimator_read(mjhmc_estimator* est, double* W, double* S1, double* S2
   if (C && !est->want_cov) return mjhmc_fail(MJHMC_ERR_INVALID, "this estimator was created without the covariance");
   mjhmc_sampler* s = est->s;
   HIPCHK(hipSetDevice(s->ctx->device));
-  const size_t D = (size_t)s->D;
+  const size_t D = (size_t)est->D;
   std::vector<double> h(1 + 2 * D);
   HIPCHK(hipMemcpyAsync(h.data(), est->acc, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   if (C) HIPCHK(hipMemcpyAsync(C, est->C, D * D * sizeof(double), hipMemcpyDeviceToHost, s->stream));

@@ -1,0 +1,354 @@
+// Device functionals (include/mjhmc_hip.h: mjhmc_functionals_*): statistics of caller expressions g(x) without the
+// samples ever reaching the host.  The caller states
+//     S[j] = sum_{d < ndims} stat_j(x_d, d; p)   j < J <= 8        g[k] = value_k(S; p)   k < K, 1 <= K <= 16
+// as C expressions (`x` the coordinate widened exactly to float64, `d` its index, `p[m]` float64 parameters); this file
+// generates a functor around them, compiles functionals_eval_kernel (functionals.hpp) for it with hipRTC -- through
+// rtc_compile, i.e. with the library's own flags, -ffp-contract=off among them -- and owns the DERIVED ring the kernel
+// writes: float64 rows [Npad][pitchK], pitchK = pick_shape(K, MJHMC_F64).pitch, the layout of every sample ring.  The
+// accumulator handles (estimators.hip, chainstats.hip, histograms.hip) read either ring through RingSource
+// (ring_source.hpp), so moments, covariance, R-hat / ESS and histograms of g need no kernel of their own.
+#include "functionals.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/mjhmc_hip.h"
+#include "handles.hpp"
+#include "ring_source.hpp"
+#include "user_expr.hpp"
+
+struct mjhmc_functionals {
+  mjhmc_sampler* s = nullptr;
+  int J = 0, K = 0, pitchK = 0;
+  uint64_t src_gen = 0;         // the sampler's ring at create: the kernel's geometry is that ring's
+  hipModule_t module = nullptr;
+  hipFunction_t fn = nullptr;
+  double* dparams = nullptr;
+  int* bad = nullptr;
+  double* ring = nullptr;       // [ring_slots][Npad][pitchK]
+  int ring_slots = 0;
+  uint64_t ring_gen = 0;        // counts the (re-)allocations of the derived ring
+  int chunks = 0, cw = 1, log_cw = 0;
+  bool wide = false;
+  size_t slot_bytes() const { return (size_t)s->Npad * pitchK * sizeof(double); }
+};
+
+namespace {
+
+std::vector<std::string> split_exprs(const char* text) {
+  std::vector<std::string> out;
+  std::string cur;
+  for (const char* c = text ? text : ""; *c; ++c) {
+    if (*c == ';') {
+      out.push_back(cur);
+      cur.clear();
+    } else {
+      cur.push_back(*c);
+    }
+  }
+  bool blank = true;
+  for (char ch : cur) blank = blank && (ch == ' ' || ch == '\t' || ch == '\n');
+  if (!blank) out.push_back(cur);
+  return out;
+}
+
+// the translation unit handed to hipRTC
+std::string functionals_source(const std::vector<std::string>& stats, const std::vector<std::string>& values) {
+  const int J = (int)stats.size(), K = (int)values.size();
+  std::string s;
+  s += "#include \"functionals.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += "// S[j] = sum_d stat_j(x_d, d; p), g[k] = value_k(S; p): the caller's expressions\n";
+  s += "struct UserFunctionals {\n";
+  s += "  static constexpr int J = " + std::to_string(J) + ", K = " + std::to_string(K) + ";\n";
+  s += "  const double* p;  // parameters, device memory\n";
+  for (int j = 0; j < J; ++j)
+    s += "  __device__ __forceinline__ double stat" + std::to_string(j) +
+         "(double x, int d) const { (void)x; (void)d; return (double)(" + stats[(size_t)j] + "); }\n";
+  s += "  __device__ __forceinline__ void add_stats(double x, int d, double* a) const {\n";
+  s += "    (void)x; (void)d; (void)a;\n";
+  for (int j = 0; j < J; ++j) s += "    a[" + std::to_string(j) + "] += stat" + std::to_string(j) + "(x, d);\n";
+  s += "  }\n";
+  for (int k = 0; k < K; ++k)
+    s += "  __device__ __forceinline__ double value" + std::to_string(k) + "(const double* S) const { (void)S; return (double)(" +
+         values[(size_t)k] + "); }\n";
+  s += "  __device__ __forceinline__ void values(const double* S, double* g) const {\n";
+  for (int k = 0; k < K; ++k) s += "    g[" + std::to_string(k) + "] = value" + std::to_string(k) + "(S);\n";
+  s += "  }\n";
+  s += "};\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
+struct Compiled {
+  std::vector<char> code;
+  std::string lowered;
+};
+
+// one compile per (source, instantiation) and process: a driver call creates a functionals per run
+int functionals_compile(const std::string& src, int dt, bool wide, const std::string& include_dir, const Compiled** out,
+                        std::string* err) {
+  static std::mutex mu;
+  static std::map<std::string, Compiled> cache;
+  const std::string name = "mjhmc::functionals_eval_kernel<" + std::to_string(dt) + ", mjhmc::UserFunctionals, " +
+                           (wide ? "true" : "false") + ">";
+  std::lock_guard<std::mutex> lock(mu);
+  const std::string key = name + "\n" + include_dir + "\n" + src;
+  auto it = cache.find(key);
+  if (it == cache.end()) {
+    Compiled c;
+    std::vector<std::string> lowered;
+    const int rc = rtc_compile(src, "mjhmc_functionals.hip", include_dir, {name}, &c.code, &lowered, err);
+    if (rc) {
+      const std::string was = "the energy expressions";
+      if (err->compare(0, was.size(), was) == 0) *err = "the functional expressions" + err->substr(was.size());
+      return rc;
+    }
+    c.lowered = lowered[0];
+    it = cache.emplace(key, std::move(c)).first;
+  }
+  *out = &it->second;
+  return 0;
+}
+
+int check_counts(int J, int K) {
+  if (J > mjhmc::kFnMaxStats)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "functionals take at most " + std::to_string(mjhmc::kFnMaxStats) + " stats (J = " +
+                                             std::to_string(J) + ")");
+  if (K < 1 || K > mjhmc::kFnMaxValues)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "the number of values K must be in [1, " + std::to_string(mjhmc::kFnMaxValues) +
+                                             "], got " + std::to_string(K));
+  return 0;
+}
+
+// lane map of a ring row of `pitch` elements of `vec` per 16 bytes (functionals.hpp)
+void row_geometry(int pitch, int vec, int* chunks, int* cw, int* log_cw, bool* wide) {
+  *chunks = pitch / vec;
+  *wide = *chunks > 64;
+  int c = 1, l = 0;
+  while (c < *chunks && c < 64) {
+    c <<= 1;
+    ++l;
+  }
+  *cw = c;
+  *log_cw = l;
+}
+
+void functionals_free(mjhmc_functionals* f) {
+  mjhmc_sampler* s = f->s;
+  estimator_free_owned(s, f);
+  chainstats_free_owned(s, f);
+  histogram_free_owned(s, f);
+  for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring})
+    if (p) (void)hipFree(p);
+  if (f->module) (void)hipModuleUnload(f->module);
+  delete f;
+}
+
+}  // namespace
+
+RingSource functionals_ring_source(const mjhmc_functionals* f) {
+  RingSource r;
+  r.base = (const char*)f->ring;
+  r.slot_bytes = f->slot_bytes();
+  r.slots = f->ring_slots;
+  r.dtype = MJHMC_F64;
+  r.D = f->K;
+  r.pitch = f->pitchK;
+  r.esize = 8;
+  r.gen = f->ring_gen;
+  r.owner = f;
+  return r;
+}
+
+mjhmc_sampler* functionals_sampler(const mjhmc_functionals* f) { return f->s; }
+
+void functionals_free_all(mjhmc_sampler* s) {
+  // (each takes its handles out of the sampler's lists)
+  for (mjhmc_functionals* f : s->functionals) functionals_free(f);
+  s->functionals.clear();
+}
+
+extern "C" {
+
+int mjhmc_functionals_check(int ndims, const char* stats, const char* values, const char* include_dir) {
+  if (!values || !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (ndims < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "ndims must be >= 1");
+  const std::vector<std::string> st = split_exprs(stats), va = split_exprs(values);
+  TRY(check_counts((int)st.size(), (int)va.size()));
+  Shape sh;
+  TRY(pick_shape(ndims, MJHMC_F64, &sh));
+  int chunks, cw, log_cw;
+  bool wide;
+  row_geometry(sh.pitch, 2, &chunks, &cw, &log_cw, &wide);
+  const Compiled* c = nullptr;
+  std::string err;
+  const int rc = functionals_compile(functionals_source(st, va), MJHMC_F64, wide, include_dir, &c, &err);
+  return rc ? mjhmc_fail(rc, err) : 0;
+}
+
+int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* values, const double* params, size_t nparams,
+                             const char* include_dir, mjhmc_functionals** out) {
+  if (!s || !values || !include_dir || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (nparams && !params) return mjhmc_fail(MJHMC_ERR_INVALID, "params is NULL");
+  const std::vector<std::string> st = split_exprs(stats), va = split_exprs(values);
+  TRY(check_counts((int)st.size(), (int)va.size()));
+  if (!s->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  // the kernel addresses a row in 16-byte chunks of the state's own type: rows must be whole chunks of it
+  const int vec = s->dtype == MJHMC_F64 ? 2 : (s->dtype == MJHMC_F32 ? 4 : 8);
+  if (s->sh.esize * vec != 16 || s->sh.pitch % vec != 0)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
+  Shape shK;
+  TRY(pick_shape((int)va.size(), MJHMC_F64, &shK));
+  if (shK.pitch != ((int)va.size() + 1) / 2 * 2) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "unexpected row pitch of the derived ring");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  int chunks, cw, log_cw;
+  bool wide;
+  row_geometry(s->sh.pitch, vec, &chunks, &cw, &log_cw, &wide);
+  const Compiled* c = nullptr;
+  std::string err;
+  const int rc = functionals_compile(functionals_source(st, va), s->dtype, wide, include_dir, &c, &err);
+  if (rc) return mjhmc_fail(rc, err);
+  mjhmc_functionals* f = new mjhmc_functionals();
+  f->s = s;
+  f->J = (int)st.size();
+  f->K = (int)va.size();
+  f->pitchK = shK.pitch;
+  f->src_gen = s->ring_gen;
+  f->chunks = chunks;
+  f->cw = cw;
+  f->log_cw = log_cw;
+  f->wide = wide;
+  hipError_t e = hipModuleLoadData(&f->module, c->code.data());
+  if (e == hipSuccess) e = hipModuleGetFunction(&f->fn, f->module, c->lowered.c_str());
+  if (e == hipSuccess) e = hipMalloc((void**)&f->dparams, (nparams ? nparams : 1) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&f->bad, sizeof(int));
+  if (e == hipSuccess && nparams)
+    e = hipMemcpyAsync(f->dparams, params, nparams * sizeof(double), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(f->bad, 0, sizeof(int), s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);   // (params is the caller's for the duration of the call only)
+  if (e != hipSuccess) {
+    functionals_free(f);
+    (void)hipGetLastError();
+    return mjhmc_fail(MJHMC_ERR_HIP, std::string("functionals: ") + hipGetErrorString(e));
+  }
+  s->functionals.push_back(f);
+  *out = f;
+  return 0;
+}
+
+int mjhmc_functionals_destroy(mjhmc_functionals* f) {
+  if (!f) return 0;
+  mjhmc_sampler* s = f->s;
+  (void)hipSetDevice(s->ctx->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  s->functionals.erase(std::remove(s->functionals.begin(), s->functionals.end(), f), s->functionals.end());
+  functionals_free(f);
+  return 0;
+}
+
+int mjhmc_functionals_info(mjhmc_functionals* f, int* n_values, uint64_t* slot_bytes) {
+  if (!f || !n_values || !slot_bytes) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  *n_values = f->K;
+  *slot_bytes = (uint64_t)f->slot_bytes();
+  return 0;
+}
+
+int mjhmc_functionals_ring_alloc(mjhmc_functionals* f, int n_slots) {
+  if (!f) return mjhmc_fail(MJHMC_ERR_INVALID, "functionals is NULL");
+  if (n_slots < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n_slots must be >= 1");
+  mjhmc_sampler* s = f->s;
+  HIPCHK(hipSetDevice(s->ctx->device));
+  if (n_slots <= f->ring_slots) return 0;
+  HIPCHK(hipStreamSynchronize(s->stream));
+  const size_t bytes = (size_t)n_slots * f->slot_bytes();
+  // the NEW ring first: a request the device cannot hold leaves the ring there was
+  double* ring = nullptr;
+  const hipError_t e = hipMalloc((void**)&ring, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    char msg[256];
+    std::snprintf(msg, sizeof(msg), "a derived ring of %d slots x %.3f GB does not fit the device (%s): the ring there was is kept",
+                  n_slots, f->slot_bytes() / 1e9, hipGetErrorString(e));
+    return mjhmc_fail(MJHMC_ERR_HIP, msg);
+  }
+  // rows p >= N stay zero for the life of the ring: the kernel never writes them
+  HIPCHK(hipMemsetAsync(ring, 0, bytes, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (f->ring) HIPCHK(hipFree(f->ring));
+  f->ring = ring;
+  f->ring_slots = n_slots;
+  ++f->ring_gen;
+  return 0;
+}
+
+int mjhmc_functionals_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out_slot0) {
+  if (!f) return mjhmc_fail(MJHMC_ERR_INVALID, "functionals is NULL");
+  mjhmc_sampler* s = f->s;
+  if (f->src_gen != s->ring_gen)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "the sample ring was re-allocated after mjhmc_functionals_create: create a new one");
+  if (!f->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)");
+  if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
+  if (x_slot0 < 0 || (int64_t)x_slot0 + n > s->ring_slots)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
+                                             ") are outside the ring of " + std::to_string(s->ring_slots));
+  if (out_slot0 < 0 || (int64_t)out_slot0 + n > f->ring_slots)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "derived slots [" + std::to_string(out_slot0) + ", " + std::to_string((int64_t)out_slot0 + n) +
+                                             ") are outside the derived ring of " + std::to_string(f->ring_slots));
+  HIPCHK(hipSetDevice(s->ctx->device));
+  mjhmc::FunctionalsArgs a;
+  a.src = (const char*)s->ring + (size_t)x_slot0 * mat_bytes(s);
+  a.dst = f->ring + (size_t)out_slot0 * s->Npad * f->pitchK;
+  a.Npad = s->Npad;
+  a.N = s->N;
+  a.n = n;
+  a.D = s->D;
+  a.pitch = s->sh.pitch;
+  a.chunks = f->chunks;
+  a.cw = f->cw;
+  a.log_cw = f->log_cw;
+  a.bad = f->bad;
+  struct {
+    const double* p;
+  } fn{f->dparams};
+  void* params[] = {&a, &fn};
+  const int64_t rows_per_block = f->wide ? 4 : (int64_t)mjhmc::kFnInFlight * (256 >> f->log_cw);
+  const int64_t gx = (s->N + rows_per_block - 1) / rows_per_block;
+  if (gx > 0x7FFFFFFFll) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "too many particles for one launch of the functionals pass");
+  HIPCHK(hipModuleLaunchKernel(f->fn, (unsigned)gx, (unsigned)std::min(n, 1024), 1, 256, 1, 1, 0, s->stream, params, nullptr));
+  int bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, f->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (bad) {
+    HIPCHK(hipMemsetAsync(f->bad, 0, sizeof(int), s->stream));
+    int k = 0;
+    while (!((bad >> k) & 1)) ++k;
+    return mjhmc_fail(MJHMC_ERR_NONFINITE, "value " + std::to_string(k) + " of the functionals is not finite for a state in slots [" +
+                                               std::to_string(x_slot0) + ", " + std::to_string(x_slot0 + n) +
+                                               "): do not accumulate derived slots [" + std::to_string(out_slot0) + ", " +
+                                               std::to_string(out_slot0 + n) + ")");
+  }
+  return 0;
+}
+
+int mjhmc_functionals_read(mjhmc_functionals* f, int slot0, int n, double* host_out) {
+  if (!f || !host_out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (slot0 < 0 || n < 1 || (int64_t)slot0 + n > f->ring_slots) return mjhmc_fail(MJHMC_ERR_INVALID, "slots out of range");
+  mjhmc_sampler* s = f->s;
+  HIPCHK(hipSetDevice(s->ctx->device));
+  // (a test and inspection path: the rows come over as they are and are re-tiled here)
+  std::vector<double> rows((size_t)s->Npad * f->pitchK);
+  for (int t = 0; t < n; ++t) {
+    TRY(copy_to_host(s, f->ring + (size_t)(slot0 + t) * s->Npad * f->pitchK, rows.data(), rows.size() * sizeof(double)));
+    for (int k = 0; k < f->K; ++k)
+      for (int64_t p = 0; p < s->N; ++p) host_out[((size_t)k * n + t) * s->N + p] = rows[(size_t)p * f->pitchK + k];
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -41,6 +41,7 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "ring_source.hpp"
 
 namespace {
 
@@ -320,7 +321,9 @@ int histogram_accumulate(hipStream_t st, const RingView& r, int n, const double*
 // ---------------------------------------------------------------------------------------------------------------------
 struct mjhmc_histogram {
   mjhmc_sampler* s = nullptr;
-  uint64_t ring_gen = 0;      // the sampler's ring at create: the plan is sized for it
+  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
+  int D = 0;                  // dimensions of a state of that ring
+  uint64_t ring_gen = 0;      // that ring at create: the plan is sized for it
   HistogramPlan plan;
   double inv_q = 1.0;
   double* range = nullptr;    // [2][D]: lo, inv
@@ -328,16 +331,12 @@ struct mjhmc_histogram {
   u64* partial = nullptr;     // the weight check's per-workgroup units
   int* bad = nullptr;
   int64_t n_states = 0;
-  size_t cells() const { return (size_t)s->D * (plan.bins + 2); }
+  size_t cells() const { return (size_t)D * (plan.bins + 2); }
   u64* count() const { return tables; }
   u64* mass() const { return tables + cells(); }
   u64* W_units() const { return tables + 2 * cells(); }
   size_t table_bytes() const { return (2 * cells() + 1) * sizeof(u64); }
 };
-
-static RingView hist_ring_view(const mjhmc_sampler* s, int slot0) {
-  return RingView{(const char*)s->ring + (size_t)slot0 * mat_bytes(s), s->dtype, s->Npad, s->N, s->D, s->sh.pitch};
-}
 
 static void histogram_free(mjhmc_histogram* h) {
   for (void* p : {(void*)h->range, (void*)h->tables, (void*)h->partial, (void*)h->bad})
@@ -350,10 +349,20 @@ void histogram_free_all(mjhmc_sampler* s) {
   s->histograms.clear();
 }
 
-extern "C" {
+void histogram_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
+  std::vector<mjhmc_histogram*> keep;
+  for (mjhmc_histogram* h : s->histograms) {
+    if (h->fn == f)
+      histogram_free(h);
+    else
+      keep.push_back(h);
+  }
+  s->histograms.swap(keep);
+}
 
-int mjhmc_histogram_create(mjhmc_sampler* s, int n_bins, const double* lo, const double* hi, double quantum,
-                           mjhmc_histogram** out) {
+// have: the sampler or the functionals handle was given (s itself is looked at only after the argument checks that need none)
+static int histogram_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_functionals* fn, int n_bins, const double* lo,
+                                      const double* hi, double quantum, mjhmc_histogram** out) {
   if (n_bins < 1 || n_bins > kHistogramMaxBins)
     return mjhmc_fail(MJHMC_ERR_INVALID, "n_bins must be in [1, " + std::to_string(kHistogramMaxBins) + "], got " +
                                              std::to_string(n_bins));
@@ -363,9 +372,12 @@ int mjhmc_histogram_create(mjhmc_sampler* s, int n_bins, const double* lo, const
   const double inv_q = 1.0 / quantum;   // exact, unless it leaves the normal range
   if (!std::isnormal(inv_q) || !std::isnormal(quantum))
     return mjhmc_fail(MJHMC_ERR_INVALID, "the quantum must be a positive power of two whose inverse is a normal float64");
-  if (!s || !lo || !hi || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
-  std::vector<double> range(2 * (size_t)s->D);
-  for (int d = 0; d < s->D; ++d) {
+  if (!have || !lo || !hi || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (fn) s = functionals_sampler(fn);
+  const RingSource src = ring_source(s, fn);
+  const int D = src.D;
+  std::vector<double> range(2 * (size_t)D);
+  for (int d = 0; d < D; ++d) {
     if (!std::isfinite(lo[d]) || !std::isfinite(hi[d]))
       return mjhmc_fail(MJHMC_ERR_INVALID, "the range of dimension " + std::to_string(d) + " is not finite");
     if (!(lo[d] < hi[d])) return mjhmc_fail(MJHMC_ERR_INVALID, "dimension " + std::to_string(d) + ": lo must be below hi");
@@ -373,19 +385,23 @@ int mjhmc_histogram_create(mjhmc_sampler* s, int n_bins, const double* lo, const
     if (!std::isfinite(inv) || !(inv > 0.0))
       return mjhmc_fail(MJHMC_ERR_INVALID, "dimension " + std::to_string(d) + ": n_bins / (hi - lo) is not a finite positive float64");
     range[d] = lo[d];
-    range[(size_t)s->D + d] = inv;
+    range[(size_t)D + d] = inv;
   }
-  if (!s->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  if (!src.base)
+    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
+                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
   // the pass addresses a row in 16-byte chunks of the state's own type: rows must be whole chunks of it
-  const int vec = s->dtype == MJHMC_F64 ? 2 : (s->dtype == MJHMC_F32 ? 4 : 8);
-  if (s->sh.esize * vec != 16 || s->sh.pitch % vec != 0)
+  const int vec = src.dtype == MJHMC_F64 ? 2 : (src.dtype == MJHMC_F32 ? 4 : 8);
+  if (src.esize * vec != 16 || src.pitch % vec != 0)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
   HIPCHK(hipSetDevice(s->ctx->device));
   mjhmc_histogram* h = new mjhmc_histogram();
   h->s = s;
-  h->ring_gen = s->ring_gen;
+  h->fn = fn;
+  h->D = D;
+  h->ring_gen = src.gen;
   h->inv_q = inv_q;
-  h->plan = histogram_plan(hist_ring_view(s, 0), n_bins);
+  h->plan = histogram_plan(ring_source_view(s, src, 0), n_bins);
   const size_t partial_bytes = (size_t)h->plan.check_gx * h->plan.check_gy * sizeof(u64);
   hipError_t e = hipMalloc((void**)&h->range, range.size() * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&h->tables, h->table_bytes());
@@ -404,6 +420,18 @@ int mjhmc_histogram_create(mjhmc_sampler* s, int n_bins, const double* lo, const
   s->histograms.push_back(h);
   *out = h;
   return 0;
+}
+
+extern "C" {
+
+int mjhmc_histogram_create(mjhmc_sampler* s, int n_bins, const double* lo, const double* hi, double quantum,
+                           mjhmc_histogram** out) {
+  return histogram_create_on_source(s != nullptr, s, nullptr, n_bins, lo, hi, quantum, out);
+}
+
+int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo, const double* hi, double quantum,
+                              mjhmc_histogram** out) {
+  return histogram_create_on_source(f != nullptr, nullptr, f, n_bins, lo, hi, quantum, out);
 }
 
 int mjhmc_histogram_destroy(mjhmc_histogram* h) {
@@ -429,12 +457,13 @@ int mjhmc_histogram_reset(mjhmc_histogram* h) {
 int mjhmc_histogram_accumulate(mjhmc_histogram* h, int x_slot0, int w_slot0, int n) {
   if (!h) return mjhmc_fail(MJHMC_ERR_INVALID, "histogram is NULL");
   mjhmc_sampler* s = h->s;
-  if (h->ring_gen != s->ring_gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "the sample ring was re-allocated after mjhmc_histogram_create: create a new histogram");
+  const RingSource src = ring_source(s, h->fn);
+  if (h->ring_gen != src.gen)
+    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_histogram_create: create a new histogram");
   if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > s->ring_slots)
+  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
     return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots));
+                                             ") are outside the ring of " + std::to_string(src.slots));
   if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
     return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
                                              ") are outside the ring of " + std::to_string(s->ring_slots) +
@@ -444,7 +473,7 @@ int mjhmc_histogram_accumulate(mjhmc_histogram* h, int x_slot0, int w_slot0, int
   HIPCHK(hipSetDevice(s->ctx->device));
   const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
   std::string err;
-  const int rc = histogram_accumulate(s->stream, hist_ring_view(s, x_slot0), n, w, h->range, h->range + s->D, h->inv_q, h->plan,
+  const int rc = histogram_accumulate(s->stream, ring_source_view(s, src, x_slot0), n, w, h->range, h->range + h->D, h->inv_q, h->plan,
                                       h->partial, h->count(), h->mass(), h->W_units(), h->bad, err);
   if (rc) return mjhmc_fail(rc, err);
   int bad = 0;

@@ -274,14 +274,14 @@ class DeviceSampler(object):
         attempts = n_done + 1 if n_done < n_iter else n_iter
         return [stats[i] for i in range(attempts)], n_done
 
-    def ring_budget_slots(self, n_wanted, share=0.6, staging=True):
+    def ring_budget_slots(self, n_wanted, share=0.6, staging=True, extra_bytes=0):
         """How many whole-state ring slots (of n_wanted) the device can take: those it already has, or `share` of the free
         memory -- at least 2 (an iteration reads one slot and writes the next).  ``staging``: every slot also gets a staging
         copy in the host layout (mjhmc_iterate_download: the streamed sample()); a ring that is recorded and then read or
-        gathered from needs none."""
+        gathered from needs none.  ``extra_bytes``: what else a slot costs (a slot of a derived ring, DeviceFunctionals)."""
         b = ctypes.c_uint64()
         check(self.lib.mjhmc_ring_slot_bytes(self.handle, ctypes.byref(b)), self.lib)
-        per = int(b.value) + (8 * self.ndims * self.nparticles if staging else 0)
+        per = int(b.value) + (8 * self.ndims * self.nparticles if staging else 0) + int(extra_bytes)
         free, _ = self.ctx.mem_info()
         fit = max(int(share * free // per) + self.ring_slots, 2)
         return min(int(n_wanted), fit)
@@ -390,6 +390,11 @@ class DeviceSampler(object):
         and integer masses in units of ``quantum`` (a power of two).  The ring must exist (ring_alloc)."""
         return DeviceHistogram(self, bins, lo, hi, quantum)
 
+    def functionals(self, values, stats=(), params=()):
+        """K values g[k] = value_k(S; p) of every recorded state, S[j] = sum_d stat_j(x_d, d; p): C expressions evaluated on
+        the device into a derived ring that the estimators read (mjhmc_functionals_*).  The ring must exist (ring_alloc)."""
+        return DeviceFunctionals(self, values, stats, params)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -418,11 +423,16 @@ class DeviceEstimator(object):
     """W = sum w, S1 = sum w (x - c), S2 = sum w (x - c)^2 and, with ``want_cov``, C = sum w (x - c)(x - c)^T over the
     (slot, particle) states of the ring blocks given to ``accumulate``; float64 throughout, bit-identical from run to run."""
 
-    def __init__(self, dev, want_cov=False):
-        self.dev, self.lib, self.want_cov = dev, dev.lib, bool(want_cov)
-        self.ndims = dev.ndims
+    def __init__(self, dev, want_cov=False, on=None):
+        """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (its K values are the
+        dimensions; x_slot0 then counts derived slots, w_slot0 still the sampler's dwell slots)"""
+        self.dev, self.lib, self.want_cov, self.on = dev, dev.lib, bool(want_cov), on
+        self.ndims = dev.ndims if on is None else on.n_values
         h = ctypes.c_void_p()
-        check(self.lib.mjhmc_estimator_create(dev.handle, 1 if want_cov else 0, ctypes.byref(h)), self.lib)
+        if on is None:
+            check(self.lib.mjhmc_estimator_create(dev.handle, 1 if want_cov else 0, ctypes.byref(h)), self.lib)
+        else:
+            check(self.lib.mjhmc_estimator_create_on(on.handle, 1 if want_cov else 0, ctypes.byref(h)), self.lib)
         self.handle = h
 
     def set_shift(self, c=None):
@@ -447,7 +457,8 @@ class DeviceEstimator(object):
         check(self.lib.mjhmc_estimator_reset(self.handle), self.lib)
 
     def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
+                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
             self.lib.mjhmc_estimator_destroy(self.handle)
         self.handle = None
 
@@ -463,11 +474,15 @@ class DeviceChainStats(object):
     of the ring blocks given to ``accumulate``, in float64 and in a fixed operation order (include/mjhmc_hip.h:
     mjhmc_chainstats_accumulate): bit-identical to the same float64 operations on the host, whatever the blocks."""
 
-    def __init__(self, dev, n_parts=1):
-        self.dev, self.lib, self.n_parts = dev, dev.lib, int(n_parts)
-        self.ndims, self.nparticles = dev.ndims, dev.nparticles
+    def __init__(self, dev, n_parts=1, on=None):
+        """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
+        self.dev, self.lib, self.n_parts, self.on = dev, dev.lib, int(n_parts), on
+        self.ndims, self.nparticles = (dev.ndims if on is None else on.n_values), dev.nparticles
         h = ctypes.c_void_p()
-        check(self.lib.mjhmc_chainstats_create(dev.handle, self.n_parts, ctypes.byref(h)), self.lib)
+        if on is None:
+            check(self.lib.mjhmc_chainstats_create(dev.handle, self.n_parts, ctypes.byref(h)), self.lib)
+        else:
+            check(self.lib.mjhmc_chainstats_create_on(on.handle, self.n_parts, ctypes.byref(h)), self.lib)
         self.handle = h
 
     def set_shift(self, c=None):
@@ -501,7 +516,8 @@ class DeviceChainStats(object):
         check(self.lib.mjhmc_chainstats_reset(self.handle), self.lib)
 
     def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
+                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
             self.lib.mjhmc_chainstats_destroy(self.handle)
         self.handle = None
 
@@ -518,14 +534,19 @@ class DeviceHistogram(object):
     bins + 1 from ``hi`` on, 1 + int((x - lo) * (bins / (hi - lo))) between (include/mjhmc_hip.h: mjhmc_histogram_create).
     Integer sums: bit-identical from run to run, whatever the blocks."""
 
-    def __init__(self, dev, bins, lo, hi, quantum=1.0):
-        self.dev, self.lib = dev, dev.lib
-        self.ndims, self.bins, self.quantum = dev.ndims, int(bins), float(quantum)
+    def __init__(self, dev, bins, lo, hi, quantum=1.0, on=None):
+        """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
+        self.dev, self.lib, self.on = dev, dev.lib, on
+        self.ndims, self.bins, self.quantum = (dev.ndims if on is None else on.n_values), int(bins), float(quantum)
         self.lo = as_f64(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.ndims,)))
         self.hi = as_f64(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.ndims,)))
         h = ctypes.c_void_p()
-        check(self.lib.mjhmc_histogram_create(dev.handle, self.bins, ptr(self.lo), ptr(self.hi), self.quantum,
-                                              ctypes.byref(h)), self.lib)
+        if on is None:
+            check(self.lib.mjhmc_histogram_create(dev.handle, self.bins, ptr(self.lo), ptr(self.hi), self.quantum,
+                                                  ctypes.byref(h)), self.lib)
+        else:
+            check(self.lib.mjhmc_histogram_create_on(on.handle, self.bins, ptr(self.lo), ptr(self.hi), self.quantum,
+                                                     ctypes.byref(h)), self.lib)
         self.handle = h
 
     def accumulate(self, x_slot0, n, w_slot0=-1):
@@ -546,8 +567,75 @@ class DeviceHistogram(object):
         check(self.lib.mjhmc_histogram_reset(self.handle), self.lib)
 
     def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
+                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
             self.lib.mjhmc_histogram_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def join_exprs(exprs):
+    """one expression or a sequence of them -> the ';'-separated bytes the C ABI takes (None for none)"""
+    exprs = [exprs] if isinstance(exprs, str) else list(exprs)
+    for e in exprs:
+        if ';' in str(e) or not str(e).strip():
+            raise ValueError('an expression is empty or holds a semicolon: %r' % (e,))
+    return ';'.join(str(e) for e in exprs).encode() if exprs else None
+
+
+class DeviceFunctionals(object):
+    """K float64 values of every recorded state of a sampler, g[k] = value_k(S; p) with S[j] = sum_d stat_j(x_d, d; p),
+    evaluated by one device pass from blocks of the sampler's ring into a derived ring of K-dimensional states
+    (include/mjhmc_hip.h: mjhmc_functionals_create).  ``estimator``, ``chain_stats`` and ``histogram`` give the sampler's
+    accumulators on the derived ring: their ``x_slot0`` counts derived slots, ``w_slot0`` the sampler's dwell slots."""
+
+    def __init__(self, dev, values, stats=(), params=()):
+        self.dev, self.lib = dev, dev.lib
+        self.nparticles = dev.nparticles
+        self.params = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel())
+        h = ctypes.c_void_p()
+        check(self.lib.mjhmc_functionals_create(dev.handle, join_exprs(stats), join_exprs(values),
+                                                ptr(self.params) if self.params.size else None, self.params.size,
+                                                _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
+        self.handle = h
+        k, b = ctypes.c_int(), ctypes.c_uint64()
+        check(self.lib.mjhmc_functionals_info(h, ctypes.byref(k), ctypes.byref(b)), self.lib)
+        self.n_values, self.slot_bytes = int(k.value), int(b.value)
+        self.ring_slots = 0
+
+    def ring_alloc(self, n_slots):
+        """at least ``n_slots`` derived slots; a ring that grows is a new ring (handles created on the old one refuse)"""
+        check(self.lib.mjhmc_functionals_ring_alloc(self.handle, int(n_slots)), self.lib)
+        self.ring_slots = max(self.ring_slots, int(n_slots))
+
+    def evaluate(self, x_slot0, n, out_slot0=0):
+        """derived slots [out_slot0, out_slot0 + n) from the sampler's ring slots [x_slot0, x_slot0 + n); raises
+        EngineError (MJHMC_ERR_NONFINITE) naming the value when one is not finite"""
+        check(self.lib.mjhmc_functionals_evaluate(self.handle, int(x_slot0), int(n), int(out_slot0)), self.lib)
+
+    def read(self, slot0, n):
+        """(K, n, N): the values of derived slots [slot0, slot0 + n)"""
+        out = np.empty((self.n_values, int(n), self.nparticles))
+        check(self.lib.mjhmc_functionals_read(self.handle, int(slot0), int(n), ptr(out)), self.lib)
+        return out
+
+    def estimator(self, want_cov=False):
+        return DeviceEstimator(self.dev, want_cov, on=self)
+
+    def chain_stats(self, n_parts=1):
+        return DeviceChainStats(self.dev, n_parts, on=self)
+
+    def histogram(self, bins, lo, hi, quantum=1.0):
+        return DeviceHistogram(self.dev, bins, lo, hi, quantum, on=self)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+            self.lib.mjhmc_functionals_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

@@ -170,6 +170,27 @@ class Marginals(object):
         return self.quantile(tail), self.quantile(1.0 - tail)
 
 
+class Functionals(object):
+    """What ``HMCBase.functionals()`` returns: the description of K functionals of the state,
+        S[j] = sum_d stat_j(x_d, d; p),   g[k] = value_k(S; p)
+    -- ``values`` (K C expressions of ``S[j]`` and ``p[m]``), ``stats`` (J <= 8 C expressions of ``x``, ``d`` and ``p[m]``),
+    ``params`` (float64), ``names`` (K strings) and ``n_values`` = K -- checked to compile, bound to no device.  Pass it
+    as ``of=`` to ``expectations()``, ``diagnostics()`` or ``marginals()``: their results then have K "dimensions"."""
+
+    def __init__(self, values, stats=(), params=(), names=None):
+        self.values = [values] if isinstance(values, str) else [str(v) for v in values]
+        self.stats = [stats] if isinstance(stats, str) else [str(t) for t in stats]
+        self.params = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel())
+        self.n_values = len(self.values)
+        self.names = ['g%d' % k for k in range(self.n_values)] if names is None else [str(n) for n in names]
+        if len(self.names) != self.n_values:
+            raise ValueError('names must have one entry per value (%d), got %d' % (self.n_values, len(self.names)))
+
+    def slot_bytes(self, nparticles):
+        """bytes of one slot of the derived ring: rows padded to 64, values to an even count, float64"""
+        return (int(nparticles) + 63) // 64 * 64 * ((self.n_values + 1) // 2 * 2) * 8
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -487,7 +508,37 @@ class HMCBase(object):
     # the jump processes weight every state by its holding time (ContinuousTimeHMC); a discrete-time chain's states count once
     _dwell_weighted = False
 
-    def expectations(self, n_iter, cov=False, block=None, shift=None):
+    def functionals(self, values, stats=(), params=(), names=None):
+        """K functionals of the state for ``expectations / diagnostics / marginals (..., of=F)``:
+            S[j] = sum_d stat_j(x_d, d; p),   g[k] = value_k(S; p)
+        ``values``: 1 .. 16 C expressions of ``S[j]`` and ``p[m]``; ``stats``: 0 .. 8 C expressions of ``x`` (a coordinate,
+        float64), ``d`` (its index) and ``p[m]``; ``params``: the float64 ``p``.  ``d == 3 ? x : 0.0`` picks a coordinate.
+        Everything is float64 and nothing is fused, so + - * /, comparisons and ?: round as the same NumPy expression
+        does.  The expressions are compiled here (no device needed): one that does not compile raises ValueError with the
+        compiler's message.  Returns a ``Functionals``."""
+        F = Functionals(values, stats, params, names)
+        lib = _lib.load()
+        rc = lib.mjhmc_functionals_check(int(self.ndims), engine.join_exprs(F.stats), engine.join_exprs(F.values),
+                                         _lib.KERNEL_HEADERS.encode())
+        if rc != 0:
+            msg = lib.mjhmc_last_error()
+            raise ValueError('functionals: %s' % (msg.decode() if msg else '?'))
+        return F
+
+    def _open_functionals(self, of, n_slots):
+        """the device side of ``of`` on this sampler's ring (which must have its final size), with a derived ring"""
+        fn = self._dev.functionals(of.values, of.stats, of.params)
+        try:
+            fn.ring_alloc(n_slots)
+        except Exception:
+            fn.close()
+            raise
+        return fn
+
+    def _extra_slot_bytes(self, of):
+        return 0 if of is None else of.slot_bytes(self._dev.nparticles)
+
+    def expectations(self, n_iter, cov=False, block=None, shift=None, of=None):
         """Mean, variance and (``cov=True``, ndims <= 512) covariance of ``n_iter`` consecutive states of every particle,
         accumulated on the device: the host receives O(D) or O(D^2) numbers whatever the length of the run
         (csrc/estimators.hip).  Returns an ``Expectations``.
@@ -500,25 +551,35 @@ class HMCBase(object):
         The run goes through the ring in blocks of ``block`` states (default: what the device holds).  ``shift``: the
         vector the device sums are taken about (cancellation); None takes the first block's own mean, at the price of
         reading that block twice.  The returned moments are about the true mean whatever the shift.  Sharded samplers
-        sum over ranks, use rank 0's shift and the smallest ``block`` of all ranks."""
+        sum over ranks, use rank 0's shift and the smallest ``block`` of all ranks.
+
+        ``of``: a ``Functionals`` (``functionals()``).  The run is exactly that of ``of=None``; every block is evaluated
+        into a derived ring on the device (csrc/functionals.hip) and the moments are those of the K functional values:
+        ``shift`` has K entries and the result K "dimensions"."""
         n_iter = int(n_iter)
         if n_iter < 1:
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        if of is not None and shift is not None and np.size(shift) != of.n_values:
+            raise ValueError('shift must have n_values = %d entries' % of.n_values)
         lead = 1 if self._dwell_weighted else 0
         if block is None:
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False) - lead
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
         block = max(1, min(int(block), n_iter))
         if self._comm is not None:
             # _run is collective for the jump samplers: every rank must walk the run in the same blocks, whatever its own
             # free memory or the caller's argument on that rank say
             block = int(self._comm.allreduce_ints([block], 'min')[0])
         self._dev.ring_alloc(block + lead)
-        est = self._dev.estimator(cov)
+        fn = est = None
         try:
+            fn = None if of is None else self._open_functionals(of, block)
+            est = (self._dev if fn is None else fn).estimator(cov)
             if shift is not None:
-                shift = self._checked_shift(shift)
+                shift = self._checked_shift(shift, of)
                 est.set_shift(shift)
             for _, k in self._ring_blocks([n_iter], block):
+                if fn is not None:
+                    fn.evaluate(0, k, 0)
                 est.accumulate(0, k, w_slot0=1 if lead else -1)
                 if shift is None:                          # the first block's own mean, then the same block again about it
                     W, S1 = self._reduce_sums(est.read())[:2]
@@ -531,12 +592,18 @@ class HMCBase(object):
                 self._read_dwell()
             W, S1, S2, C, n_states = self._reduce_sums(est.read())
         finally:
-            est.close()
+            if est is not None:
+                est.close()
+            if fn is not None:
+                fn.close()
         return Expectations(W, S1, S2, C, n_states, shift)
 
-    def _checked_shift(self, shift):
+    def _checked_shift(self, shift, of=None):
         shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
-        if shift.shape != (self.ndims,):
+        if of is not None:
+            if shift.shape != (of.n_values,):
+                raise ValueError('shift must have n_values = %d entries' % of.n_values)
+        elif shift.shape != (self.ndims,):
             raise ValueError('shift must have ndims = %d entries' % self.ndims)
         if self._comm is not None:
             shift = self._comm.bcast(shift.copy(), 0)
@@ -563,7 +630,7 @@ class HMCBase(object):
                 yield seg, k
                 last, done, seg_done = k, done + k, seg_done + k
 
-    def diagnostics(self, n_iter, split=True, block=None, shift=None):
+    def diagnostics(self, n_iter, split=True, block=None, shift=None, of=None):
         """R-hat and the multi-chain effective sample size of ``n_iter`` consecutive states of every particle, every
         particle being one chain: per-chain sums kept on the device (csrc/chainstats.hip), O(ndims) numbers to the host
         whatever the length of the run and the number of chains.  Returns a ``Diagnostics``.
@@ -576,38 +643,55 @@ class HMCBase(object):
         device sums are taken about; None takes the pooled mean of the first block (one extra moment pass over it, before
         the chain sums start).  Sharded samplers sum over ranks, use rank 0's shift and the smallest ``block`` of all
         ranks.  The per-chain sums take device memory (parts x (2 x row pitch + 1) x padded particles x 8 bytes): they
-        are created before the block size is taken from what the device has left."""
+        are created before the block size is taken from what the device has left.
+
+        ``of``: a ``Functionals`` (``functionals()``): the same run, the diagnostics of the K functional values (every
+        block is evaluated into a derived ring first; ``shift`` has K entries)."""
         n_iter = int(n_iter)
         if split and (n_iter < 4 or n_iter % 2):
             raise ValueError('split=True needs an even n_iter >= 4, got %d' % n_iter)
         if not split and n_iter < 2:
             raise ValueError('n_iter must be >= 2, got %d' % n_iter)
-        if shift is not None and np.size(shift) != self.ndims:
+        if of is not None:
+            if shift is not None and np.size(shift) != of.n_values:
+                raise ValueError('shift must have n_values = %d entries' % of.n_values)
+        elif shift is not None and np.size(shift) != self.ndims:
             raise ValueError('shift must have ndims = %d entries' % self.ndims)
         lead = 1 if self._dwell_weighted else 0
         segments = [n_iter // 2, n_iter // 2] if split else [n_iter]
         grad0 = self.distribution.dEdX_count
         self._dev.ring_alloc(1 + lead)                     # (the sums have the ring's row layout: it must exist)
-        cs = self._dev.chain_stats(len(segments))
+        fn = cs = None
         try:
+            fn = None if of is None else self._open_functionals(of, 1)
+            cs = (self._dev if fn is None else fn).chain_stats(len(segments))
             if block is None:
-                block = self._dev.ring_budget_slots(segments[0] + lead, staging=False) - lead
+                block = self._dev.ring_budget_slots(segments[0] + lead, staging=False,
+                                                    extra_bytes=self._extra_slot_bytes(of)) - lead
             block = max(1, min(int(block), segments[0]))
             if self._comm is not None:
                 block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
-            if block + lead > self._dev.ring_slots:
+            if block + lead > self._dev.ring_slots or (fn is not None and block > fn.ring_slots):
                 # a ring that grows is a new ring, and the sums belong to the one they were created on: free them, grow
-                # the ring by the budget that counted them, take them again
+                # the ring by the budget that counted them, take them again (the functionals belong to the sample ring
+                # in the same way, and the sums on them to the derived ring)
                 cs.close()
+                cs = None
+                if fn is not None:
+                    fn.close()
+                    fn = None
                 self._dev.ring_alloc(block + lead)
-                cs = self._dev.chain_stats(len(segments))
+                fn = None if of is None else self._open_functionals(of, block)
+                cs = (self._dev if fn is None else fn).chain_stats(len(segments))
             if shift is not None:
-                shift = self._checked_shift(shift)
+                shift = self._checked_shift(shift, of)
                 cs.set_shift(shift)
             w_slot0 = 1 if lead else -1
             for part, k in self._ring_blocks(segments, block):
+                if fn is not None:
+                    fn.evaluate(0, k, 0)
                 if shift is None:
-                    est = self._dev.estimator(False)
+                    est = (self._dev if fn is None else fn).estimator(False)
                     try:
                         est.accumulate(0, k, w_slot0=w_slot0)
                         W, S1 = self._reduce_sums(est.read())[:2]
@@ -621,13 +705,16 @@ class HMCBase(object):
                 self._read_dwell()
             parts = [cs.read(h) for h in range(len(segments))]
         finally:
-            cs.close()
+            if cs is not None:
+                cs.close()
+            if fn is not None:
+                fn.close()
         if self._comm is not None:
             from ..parallel import reduce_chain_sums
             parts = reduce_chain_sums(self._comm, parts)
         return Diagnostics(parts, shift, self.distribution.dEdX_count - grad0)
 
-    def marginals(self, n_iter, bins=256, range=None, block=None, span=8.0):
+    def marginals(self, n_iter, bins=256, range=None, block=None, span=8.0, of=None):
         """Weighted histograms of every dimension over ``n_iter`` consecutive states of every particle, accumulated on
         the device (csrc/histograms.hip): the host receives 2 x ndims x (bins + 2) integers whatever the length of the
         run.  Returns a ``Marginals`` (quantiles, median, credible intervals, CDF).
@@ -638,8 +725,13 @@ class HMCBase(object):
         ndims-vectors; None takes mean -/+ ``span`` standard deviations from one moment pass over the first block.  The
         jump samplers count weights in units of q = 2^(floor(log2(mean weight of the first block)) - 24); the others in
         units of 1.  Sharded samplers use rank 0's range and quantum and the smallest ``block`` of all ranks, and add
-        their integer tables over ranks."""
+        their integer tables over ranks.
+
+        ``of``: a ``Functionals`` (``functionals()``): the same run, one histogram per functional value (every block is
+        evaluated into a derived ring first; ``range`` entries are scalars or K-vectors, and the range=None moment pass,
+        ``span`` and the quantum rule apply to the values)."""
         n_iter, bins = int(n_iter), int(bins)
+        K = self.ndims if of is None else of.n_values
         if n_iter < 1:
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
         if not 1 <= bins <= 1024:
@@ -647,28 +739,32 @@ class HMCBase(object):
         if range is not None:
             if len(range) != 2:
                 raise ValueError('range must be (lo, hi)')
-            lo, hi = [np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.ndims,))) if np.size(v) in (1, self.ndims)
+            lo, hi = [np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (K,))) if np.size(v) in (1, K)
                       else None for v in range]
             if lo is None or hi is None:
-                raise ValueError('lo and hi must be scalars or have ndims = %d entries' % self.ndims)
+                raise ValueError('lo and hi must be scalars or have %s = %d entries' % ('ndims' if of is None else 'n_values', K))
             if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
                 raise ValueError('range needs finite lo < hi in every dimension')
         elif not span > 0:
             raise ValueError('span must be positive')
         lead = 1 if self._dwell_weighted else 0
         if block is None:
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False) - lead
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
         block = max(1, min(int(block), n_iter))
         if self._comm is not None:
             block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
         self._dev.ring_alloc(block + lead)
         w_slot0 = 1 if lead else -1
-        hist, q = None, 1.0
+        fn, hist, q = None, None, 1.0
         try:
+            fn = None if of is None else self._open_functionals(of, block)
+            src = self._dev if fn is None else fn
             for _, k in self._ring_blocks([n_iter], block):
+                if fn is not None:
+                    fn.evaluate(0, k, 0)
                 if hist is None:
                     if range is None or lead:
-                        est = self._dev.estimator(False)
+                        est = src.estimator(False)
                         try:
                             est.accumulate(0, k, w_slot0=w_slot0)
                             W, S1, S2, _, n_first = self._reduce_sums(est.read())
@@ -683,8 +779,8 @@ class HMCBase(object):
                             lo, hi = mean - span * sd, mean + span * sd
                     if self._comm is not None:
                         packed = self._comm.bcast(np.concatenate([lo, hi, [q]]), 0)
-                        lo, hi, q = packed[:self.ndims].copy(), packed[self.ndims:2 * self.ndims].copy(), float(packed[-1])
-                    hist = self._dev.histogram(bins, lo, hi, q)
+                        lo, hi, q = packed[:K].copy(), packed[K:2 * K].copy(), float(packed[-1])
+                    hist = src.histogram(bins, lo, hi, q)
                 hist.accumulate(0, k, w_slot0=w_slot0)
             self._publish()
             if lead:
@@ -693,6 +789,8 @@ class HMCBase(object):
         finally:
             if hist is not None:
                 hist.close()
+            if fn is not None:
+                fn.close()
         if self._comm is not None:
             from ..parallel import reduce_histogram
             counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
