@@ -463,6 +463,51 @@ int mjhmc_chainstats_create_on(mjhmc_functionals* f, int n_parts, mjhmc_chainsta
 int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo, const double* hi, double quantum,
                               mjhmc_histogram** out);
 
+/* Fair sample paths on a uniform time grid, kept on the device (csrc/timegrid.hip): the one result the weighted
+ * accumulators above cannot give -- a fair sample with its time order kept.  The reference's sample(resample=True)
+ * (markov_jump_hmc.py:293-338) pools particles and steps into one weighted draw ("preserve_order has no effect if
+ * resample is enabled"), and its figures take the autocorrelation of sample(resample=False), the embedded chain, whose
+ * samples its own docstring calls biased.  The unbiased object is the jump process x_p(t): chain p sits in state k for
+ * its holding time.  A time grid samples it at t_j = j * dt, j < n_grid, into a GRID RING of n_grid slots in the sample
+ * ring's own slot layout and dtype (stored elements copied verbatim), zeroed at create.  Per chain p < N it keeps a
+ * clock T[p] (float64, 0 at create) and a cursor j[p] (int32, 0 at create).
+ * Ownership as for mjhmc_estimator: a time grid belongs to the sampler it was created on, mjhmc_sampler_destroy frees
+ * every one still alive and the handle is INVALID from then on.  It has its own storage: a re-allocated sample ring does
+ * not invalidate it.
+ * MJHMC_ERR_INVALID: n_grid < 1, dt not finite or <= 0, no sample ring yet.  A grid the device cannot hold fails as
+ * mjhmc_ring_alloc does (the sizes in mjhmc_last_error()) and leaves nothing behind. */
+typedef struct mjhmc_timegrid mjhmc_timegrid;
+int mjhmc_timegrid_create(mjhmc_sampler* s, int n_grid, double dt, mjhmc_timegrid** out);
+int mjhmc_timegrid_destroy(mjhmc_timegrid* tg);
+/* The n states of ring slots [x_slot0, x_slot0 + n) with the holding times of dwell-ring slots [w_slot0, w_slot0 + n),
+ * or unit holding times for w_slot0 == -1: the pairing of mjhmc_estimator_accumulate (a jump sampler takes w_slot0 =
+ * x_slot0 + 1).  For every chain p < N, k = 0 .. n - 1 ascending:
+ *     w  = dwell[w_slot0 + k][p]                          (w_slot0 == -1: w = 1.0)
+ *     Tn = T[p] + w                                       one rounded float64 addition
+ *     while j[p] < n_grid and (double)j[p] * dt < Tn:     one rounded multiplication
+ *         grid[j[p]][p][:] = x[x_slot0 + k][p][:];  j[p] += 1
+ *     T[p] = Tn
+ * Grid point t_j takes the state with T_k <= t_j < T_{k+1}; a state of zero holding time is never emitted, one that
+ * spans several grid points is emitted for each.  The clock is a sequential sum from the stored value: grid, T and j do
+ * not depend on how a run is cut into blocks and are bit-identical from run to run.  Rows p >= N of the sample ring, the
+ * dwell ring and the grid are neither read nor written.
+ * MJHMC_ERR_INVALID: slots outside either ring, n < 1.  MJHMC_ERR_NONFINITE: a holding time that is not finite or is
+ * negative (checked on the device ahead of the pass); grid, clocks and cursors are as before the call.  Reading that
+ * flag back is the call's only synchronisation, and unit holding times need none. */
+int mjhmc_timegrid_accumulate(mjhmc_timegrid* tg, int x_slot0, int n, int w_slot0);
+/* *covered = min_p j[p], the grid slots complete for every chain; *max_filled = max_p j[p] (integer reductions) */
+int mjhmc_timegrid_progress(mjhmc_timegrid* tg, int* covered, int* max_filled);
+/* T (N doubles) and j (N int32) of the chains; either pointer may be NULL */
+int mjhmc_timegrid_read_clocks(mjhmc_timegrid* tg, double* T_host, int32_t* j_host);
+/* grid slots [slot0, slot0 + n) in float64, the layouts of mjhmc_ring_read: (D, n*N) time-major if stacked==0,
+ * (D, N, n) if stacked==1.  Slots a chain has not reached hold zeros for it. */
+int mjhmc_timegrid_read(mjhmc_timegrid* tg, int slot0, int n, int stacked, double* host_out);
+/* mjhmc_ring_autocor along the time axis of grid slots [slot0, slot0 + n): the unnormalised lag sums (n float64).
+ * MJHMC_ERR_INVALID when slot0 + n > covered: a slot some chain has not reached is no sample. */
+int mjhmc_timegrid_autocor(mjhmc_timegrid* tg, int slot0, int n, int linear, double* host_out);
+/* clocks and cursors to zero and the grid zeroed; n_grid and dt stay */
+int mjhmc_timegrid_reset(mjhmc_timegrid* tg);
+
 /* The leapfrog operator on caller-supplied states: HMCState.leapfrog (n_steps = 1) and HMCState.L
  * (n_steps = num_leapfrog_steps) of mjhmc/samplers/hmc_state.py:86-100, in the reference's literal operation order
  * (half kicks not merged, every product rounded before its sum).  X, V and the outputs are (ndims, n) float64 C order

@@ -120,6 +120,14 @@ PROTOTYPES = {
     'mjhmc_estimator_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
     'mjhmc_chainstats_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
     'mjhmc_histogram_create_on': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_timegrid_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_timegrid_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_timegrid_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_timegrid_progress': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    'mjhmc_timegrid_read_clocks': (ctypes.c_int, [_P, _P, _P]),
+    'mjhmc_timegrid_read': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    'mjhmc_timegrid_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    'mjhmc_timegrid_reset': (ctypes.c_int, [_P]),
     'mjhmc_leapfrog': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _P, _P, _P, _P, _P]),
     'mjhmc_ring_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_autocor': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),
@@ -150,6 +158,7 @@ TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_ring_write_dwell': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, ctypes.c_double]),
     'mjhmc_test_ring_write': (ctypes.c_int, [_P, ctypes.c_int, _P]),
     'mjhmc_test_ring_fill_padding': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_test_timegrid_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
 }
 
 _lib = None

@@ -90,6 +90,7 @@ struct mjhmc_estimator;  // weighted-moment accumulator over ring blocks (estima
 struct mjhmc_chainstats; // per-chain weighted sums over ring blocks (chainstats.hip)
 struct mjhmc_histogram;  // weighted marginal histograms over ring blocks (histograms.hip)
 struct mjhmc_functionals;  // caller expressions g(x) evaluated into a derived ring (functionals.hip)
+struct mjhmc_timegrid;   // the jump process sampled on a uniform time grid, in a grid ring of its own (timegrid.hip)
 struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (api.hip)
 struct HostTraj;  // proposal workspace of a host-energy sampler (host_energy.hip)
 
@@ -157,6 +158,7 @@ struct mjhmc_sampler {
   std::vector<mjhmc_chainstats*> chainstats;  // per-chain accumulators created on this sampler (chainstats.hip); freed with it
   std::vector<mjhmc_histogram*> histograms;   // histogram accumulators created on this sampler (histograms.hip); freed with it
   std::vector<mjhmc_functionals*> functionals;   // functionals created on this sampler (functionals.hip); freed with it, BEFORE the three lists above
+  std::vector<mjhmc_timegrid*> timegrids;     // time grids created on this sampler (timegrid.hip); freed with it
   double* stage = nullptr;  // device staging, float64 host layout
   size_t stage_elems = 0;
   void* noise = nullptr;    // replay normals, particle-major
@@ -204,6 +206,9 @@ void histogram_free_all(mjhmc_sampler* s);
 
 // functionals.hip (frees the accumulator handles created on each, too: call it before the three above)
 void functionals_free_all(mjhmc_sampler* s);
+
+// timegrid.hip
+void timegrid_free_all(mjhmc_sampler* s);
 
 // host_energy.hip
 void host_traj_free(mjhmc_sampler* s);

@@ -274,16 +274,21 @@ class DeviceSampler(object):
         attempts = n_done + 1 if n_done < n_iter else n_iter
         return [stats[i] for i in range(attempts)], n_done
 
-    def ring_budget_slots(self, n_wanted, share=0.6, staging=True, extra_bytes=0):
+    def ring_slot_bytes(self):
+        """device bytes of one ring slot (a padded state matrix + its dwelling times)"""
+        b = ctypes.c_uint64()
+        check(self.lib.mjhmc_ring_slot_bytes(self.handle, ctypes.byref(b)), self.lib)
+        return int(b.value)
+
+    def ring_budget_slots(self, n_wanted, share=0.6, staging=True, extra_bytes=0, reserve_bytes=0):
         """How many whole-state ring slots (of n_wanted) the device can take: those it already has, or `share` of the free
         memory -- at least 2 (an iteration reads one slot and writes the next).  ``staging``: every slot also gets a staging
         copy in the host layout (mjhmc_iterate_download: the streamed sample()); a ring that is recorded and then read or
-        gathered from needs none.  ``extra_bytes``: what else a slot costs (a slot of a derived ring, DeviceFunctionals)."""
-        b = ctypes.c_uint64()
-        check(self.lib.mjhmc_ring_slot_bytes(self.handle, ctypes.byref(b)), self.lib)
-        per = int(b.value) + (8 * self.ndims * self.nparticles if staging else 0) + int(extra_bytes)
+        gathered from needs none.  ``extra_bytes``: what else a slot costs (a slot of a derived ring, DeviceFunctionals).
+        ``reserve_bytes``: free memory spoken for (a time grid that is created once its dt is known)."""
+        per = self.ring_slot_bytes() + (8 * self.ndims * self.nparticles if staging else 0) + int(extra_bytes)
         free, _ = self.ctx.mem_info()
-        fit = max(int(share * free // per) + self.ring_slots, 2)
+        fit = max(int(share * max(free - int(reserve_bytes), 0) // per) + self.ring_slots, 2)
         return min(int(n_wanted), fit)
 
     def reset_flf_cache(self):
@@ -394,6 +399,11 @@ class DeviceSampler(object):
         """K values g[k] = value_k(S; p) of every recorded state, S[j] = sum_d stat_j(x_d, d; p): C expressions evaluated on
         the device into a derived ring that the estimators read (mjhmc_functionals_*).  The ring must exist (ring_alloc)."""
         return DeviceFunctionals(self, values, stats, params)
+
+    def time_grid(self, n_grid, dt):
+        """The jump process of every chain sampled at t_j = j * dt, j < n_grid, into a grid ring of this sampler's slot
+        layout (mjhmc_timegrid_*): a fair sample with its time order kept.  The ring must exist (ring_alloc)."""
+        return DeviceTimeGrid(self, n_grid, dt)
 
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
@@ -570,6 +580,66 @@ class DeviceHistogram(object):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
                 (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
             self.lib.mjhmc_histogram_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceTimeGrid(object):
+    """Per chain p a clock T[p] and a cursor j[p]; ``accumulate`` walks a block of ring slots in order and copies the state
+    that holds at t_j = j * dt into grid slot j for every grid point its holding time covers (include/mjhmc_hip.h:
+    mjhmc_timegrid_accumulate).  Grid, clocks and cursors are bit-identical to that sequence of float64 operations on the
+    host, whatever the blocks."""
+
+    def __init__(self, dev, n_grid, dt):
+        self.dev, self.lib = dev, dev.lib
+        self.ndims, self.nparticles = dev.ndims, dev.nparticles
+        self.n_grid, self.dt = int(n_grid), float(dt)
+        h = ctypes.c_void_p()
+        check(self.lib.mjhmc_timegrid_create(dev.handle, self.n_grid, self.dt, ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), holding times of dwell slots [w_slot0, w_slot0 + n) (-1: unit holding
+        times; a jump sampler takes w_slot0 = x_slot0 + 1).  A refused block (a holding time that is not finite or is
+        negative) raises and changes nothing."""
+        check(self.lib.mjhmc_timegrid_accumulate(self.handle, int(x_slot0), int(n), int(w_slot0)), self.lib)
+
+    def progress(self):
+        """(covered, max_filled): the grid slots complete for every chain, and for the chain that got furthest"""
+        c, m = ctypes.c_int(), ctypes.c_int()
+        check(self.lib.mjhmc_timegrid_progress(self.handle, ctypes.byref(c), ctypes.byref(m)), self.lib)
+        return int(c.value), int(m.value)
+
+    def read_clocks(self):
+        """(T (N,) float64, j (N,) int32)"""
+        T, j = np.empty(self.nparticles), np.empty(self.nparticles, dtype=np.int32)
+        check(self.lib.mjhmc_timegrid_read_clocks(self.handle, ptr(T), ptr(j)), self.lib)
+        return T, j
+
+    def read(self, slot0, n, stacked=True):
+        """grid slots [slot0, slot0 + n): (ndims, nparticles, n) if ``stacked``, else (ndims, n * nparticles) time-major"""
+        n = int(n)
+        out = np.empty((self.ndims, self.nparticles, n) if stacked else (self.ndims, n * self.nparticles))
+        check(self.lib.mjhmc_timegrid_read(self.handle, int(slot0), n, 1 if stacked else 0, ptr(out)), self.lib)
+        return out
+
+    def autocor(self, slot0, n, linear=False):
+        """Lag sums over time of grid slots [slot0, slot0 + n) (all of them covered), summed over all state elements."""
+        out = np.empty(int(n), dtype=np.float64)
+        check(self.lib.mjhmc_timegrid_autocor(self.handle, int(slot0), int(n), 1 if linear else 0, ptr(out)), self.lib)
+        return out
+
+    def reset(self):
+        check(self.lib.mjhmc_timegrid_reset(self.handle), self.lib)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+            self.lib.mjhmc_timegrid_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

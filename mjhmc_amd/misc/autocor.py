@@ -82,6 +82,27 @@ def calculate_autocorrelation(sampler, distribution, num_steps=None, num_grad_st
     return autocor, e_evals, grad_evals
 
 
+def calculate_time_autocorrelation(sampler, distribution, num_steps, dt=None, n_grid=None, **kwargs):
+    """The autocorrelation of the jump process itself, in process time: ``sampler.paths(num_steps, n_grid, dt)`` samples
+    every chain on the grid t_j = j dt on the device (a state counts for as long as it is held), and the curve is
+    ``fft_autocor`` along the covered part of that grid.  Returns (autocor [covered], grad_evals [covered]) with
+    ``grad_evals[k] = k * dt * grad_evals_per_time``, the gradient evaluations per particle that lag k costs.
+
+    The reference has no counterpart: its figures take the curve of ``resample=False`` (every state once, which its own
+    docstring calls biased), and ``calculate_autocorrelation`` on a resampling sampler draws step by step on the host.
+    A jump sampler's ``resample`` flag plays no part here: it only says what ``sample()`` returns."""
+    smp = sampler(distribution=distribution, **kwargs)
+    distribution.E_count = 0
+    distribution.dEdX_count = 0
+    paths = smp.paths(int(num_steps), n_grid=n_grid, dt=dt)
+    try:
+        autocor = paths.autocor()
+    finally:
+        paths.close()
+    grad_evals = np.arange(autocor.size) * paths.dt * paths.grad_evals_per_time
+    return autocor, grad_evals
+
+
 def generate_samples(sampler, distribution, num_steps=None, num_grad_steps=None, replay=None, **kwargs):
     """Same contract as the reference:
 

@@ -170,6 +170,65 @@ class Marginals(object):
         return self.quantile(tail), self.quantile(1.0 - tail)
 
 
+class Paths(object):
+    """What ``paths()`` returns: the jump process of every chain sampled on the uniform time grid t_j = j ``dt``,
+    j < ``n_grid`` -- a fair sample with its time order kept.  The grid stays on the device (csrc/timegrid.hip) until
+    ``close()``.
+
+      dt, n_grid            the grid
+      covered               the grid points every chain has reached (the minimum over chains and ranks): the usable length
+      mean_time             the mean over chains of the time a chain's recorded states span (the sum of their holding times)
+      grad_evals_per_time   gradient evaluations per chain / mean_time: what one unit of process time costs
+      n_chains              chains (all ranks)
+
+    ``read(n)`` downloads the first ``n`` (default ``covered``) grid points as (ndims, nbatch, n) float64 -- the columns of
+    this rank in a sharded run.  ``autocor(n, linear)`` is the autocorrelation along the grid, taken on the device:
+    ``linear=False`` is ``fft_autocor`` of that array (circular, 1 at lag 0), ``linear=True`` the lag-product means
+    np.mean(x[:, :, :-k] * x[:, :, k:]) divided by the one of lag 0; lag k is process time k ``dt``.  Both refuse
+    ``n > covered``: a grid point some chain has not reached is no sample."""
+
+    def __init__(self, grid, dt, n_grid, covered, mean_time, grad_evals_per_chain, n_chains, comm=None):
+        self._grid, self._comm = grid, comm
+        self.dt, self.n_grid, self.covered = float(dt), int(n_grid), int(covered)
+        self.mean_time = float(mean_time)
+        self.n_chains = int(n_chains)
+        self.grad_evals_per_chain = float(grad_evals_per_chain)
+        self.grad_evals_per_time = self.grad_evals_per_chain / self.mean_time if self.mean_time > 0 else float('nan')
+
+    def _length(self, n):
+        n = self.covered if n is None else int(n)
+        if n < 1 or n > self.covered:
+            raise ValueError('n must be in [1, covered = %d], got %d: grid points beyond `covered` are not reached by every '
+                             'chain (a longer run, a larger dt or a smaller n_grid covers more)' % (self.covered, n))
+        if self._grid is None:
+            raise ValueError('this Paths was closed')
+        return n
+
+    def read(self, n=None):
+        n = self._length(n)
+        return self._grid.read(0, n, stacked=True)
+
+    def autocor(self, n=None, linear=False):
+        n = self._length(n)
+        sums = self._grid.autocor(0, n, linear=linear)
+        if self._comm is not None:
+            sums = self._comm.allreduce_f64(sums)         # column shards add their lag sums
+        if linear:
+            sums = sums / (n - np.arange(n, dtype=np.float64))
+        return sums / sums[0]
+
+    def close(self):
+        if self._grid is not None:
+            self._grid.close()
+            self._grid = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Functionals(object):
     """What ``HMCBase.functionals()`` returns: the description of K functionals of the state,
         S[j] = sum_d stat_j(x_d, d; p),   g[k] = value_k(S; p)
@@ -795,6 +854,79 @@ class HMCBase(object):
             from ..parallel import reduce_histogram
             counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
         return Marginals(lo, hi, bins, q, counts, units, W_units, n_states)
+
+    def paths(self, n_iter, n_grid=None, dt=None, block=None):
+        """A fair sample of every chain with its time order kept: the process "chain p sits in state k for its holding
+        time" sampled at t_j = j ``dt``, j < ``n_grid``, on the device (csrc/timegrid.hip).  Returns a ``Paths`` (``read``,
+        ``autocor``, ``close``); the grid stays on the device.  The weighted estimators make pooled statistics fair and
+        lose the order; ``sample(resample=False)`` keeps the order and counts every state once whatever its holding time.
+
+        The run itself is that of ``expectations(n_iter)``: the same iterations, the same holding times (the jump
+        samplers run ``n_iter + 1`` iterations; a discrete-time sampler's states hold for one unit each), the same
+        counters, ``dwelling_times`` and final state, in blocks of ``block`` states.  ``dt=None`` takes the mean holding
+        time of the first block (one moment pass over it; 1 for a discrete-time sampler, whose grid is then its ring);
+        ``n_grid=None`` takes ``n_iter``.  With ``dt`` the mean holding time the chains reach grid point ``n_iter`` on
+        average, so about half of them stop short of it: ``covered`` says how many grid points all of them reached.
+        The grid takes ``n_grid`` ring slots of device memory, counted before the block size is taken from what the
+        device has left.  Sharded samplers use rank 0's ``dt`` and the smallest ``block`` of all ranks; ``covered`` is the
+        minimum over ranks."""
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        n_grid = n_iter if n_grid is None else int(n_grid)
+        if n_grid < 1:
+            raise ValueError('n_grid must be >= 1, got %d' % n_grid)
+        if dt is not None and not (np.isfinite(dt) and dt > 0):
+            raise ValueError('dt must be finite and positive, got %r' % (dt,))
+        lead = 1 if self._dwell_weighted else 0
+        w_slot0 = 1 if lead else -1
+        comm = self._comm
+        if dt is None and not lead:
+            dt = 1.0
+        if dt is not None and comm is not None:
+            dt = float(comm.bcast(np.array([dt], dtype=np.float64), 0)[0])
+        grad0 = self.distribution.dEdX_count
+        self._dev.ring_alloc(1 + lead)                     # (a grid is created on a sampler that has its ring)
+        tg = None
+        try:
+            if dt is not None:
+                tg = self._dev.time_grid(n_grid, dt)       # its own storage: the ring may still grow
+            if block is None:
+                reserve = 0 if tg is not None else n_grid * self._dev.ring_slot_bytes()
+                block = self._dev.ring_budget_slots(n_iter + lead, staging=False, reserve_bytes=reserve) - lead
+            block = max(1, min(int(block), n_iter))
+            if comm is not None:
+                block = int(comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
+            self._dev.ring_alloc(block + lead)
+            for _, k in self._ring_blocks([n_iter], block):
+                if tg is None:                             # dt = W / (N k), the mean holding time of the first block
+                    est = self._dev.estimator(False)
+                    try:
+                        est.accumulate(0, k, w_slot0=w_slot0)
+                        W, _, _, _, n_first = self._reduce_sums(est.read())
+                    finally:
+                        est.close()
+                    dt = float(W) / n_first
+                    if comm is not None:
+                        dt = float(comm.bcast(np.array([dt], dtype=np.float64), 0)[0])
+                    tg = self._dev.time_grid(n_grid, dt)
+                tg.accumulate(0, k, w_slot0=w_slot0)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            covered = tg.progress()[0]
+            T = tg.read_clocks()[0]
+            sum_T, n_chains = float(np.sum(T)), int(T.size)
+            if comm is not None:
+                covered = int(comm.allreduce_ints([covered], 'min')[0])
+                n_chains = int(comm.allreduce_ints([n_chains], 'sum')[0])
+                sum_T = float(comm.allreduce_f64(np.array([sum_T]))[0])
+        except Exception:
+            if tg is not None:
+                tg.close()
+            raise
+        grad = self.distribution.dEdX_count - grad0
+        return Paths(tg, dt, n_grid, covered, sum_T / n_chains, grad / float(n_chains), n_chains, comm)
 
     def _reduce_sums(self, sums):
         if self._comm is None:
