@@ -544,6 +544,28 @@ int mjhmc_ring_autocor(mjhmc_sampler* s, int slot0, int n, int linear, double* h
 int mjhmc_autocor(mjhmc_ctx* ctx, const double* samples, int64_t n_series, int n_samples, int linear,
                   double* host_out);
 
+/* Centred linear lag sums PER DIMENSION along the time axis of n consecutive slots (csrc/lagcov.hip): what the integrated
+ * autocorrelation time and the effective sample size of every coordinate are made of.  They replace the host computation
+ * of mjhmc/misc/autocor.py:177-211 (slow_autocorrelation: the lag-product means of the downloaded [n_dims, n_batch,
+ * n_samples] array, pooled over dimensions and taken about zero) by one streaming pass per band of 32 lags:
+ *     u[t][p][d] = (double)x[t][p][d] - shift[d]                                 one rounded float64 subtraction
+ *     A_out[k][d] = sum_{p < N} sum_{t = 0}^{n - 1 - k} u[t][p][d] * u[t + k][p][d]    k = 0 .. max_lag, (max_lag + 1, ndims) C order
+ *     S_out[d]    = sum_{p < N} sum_{t < n} u[t][p][d]                                 ndims float64; S_out may be NULL
+ * shift: ndims float64 on the host, NULL for zeros (the two give the same bits).  The sums are linear in time, not
+ * circular, and unnormalised, so that ranks holding column shards add theirs; A_out[k][d] / (N * (n - k)) is the lag-k
+ * product mean of dimension d.  Rows p >= N and columns d >= ndims are not read.  There is no floating-point atomic: the
+ * order of addition depends on (N, ndims, n, max_lag) alone and the result is bit-identical from run to run.
+ * MJHMC_ERR_INVALID (with a message): slots outside the ring or grid, n < 1, max_lag outside [0, min(n - 1, 256)], a shift
+ * entry that is not finite.
+ * mjhmc_grid_lagcov: grid slots [slot0, slot0 + n) of a time grid; refuses slot0 + n > covered as mjhmc_timegrid_autocor.
+ * mjhmc_ring_lagcov: ring slots [slot0, slot0 + n) of a sampler (the embedded chain; a discrete-time sampler's fair path).
+ * mjhmc_lagcov:      a host array laid out as for mjhmc_autocor, [n_dims, n_batch, n_samples] C order, re-tiled on the
+ *                    device into a temporary time-major view that the same kernels read (no sampler needed). */
+int mjhmc_grid_lagcov(mjhmc_timegrid* tg, int slot0, int n, int max_lag, const double* shift, double* A_out, double* S_out);
+int mjhmc_ring_lagcov(mjhmc_sampler* s, int slot0, int n, int max_lag, const double* shift, double* A_out, double* S_out);
+int mjhmc_lagcov(mjhmc_ctx* ctx, const double* samples, int n_dims, int64_t n_batch, int n_samples, int max_lag,
+                 const double* shift, double* A_out, double* S_out);
+
 /* ---- several GPUs: one process per GPU, particle COLUMNS sharded over the ranks ------------------
  * The reference is single-process; its particles are independent chains (mjhmc/samplers/hmc_state.py works column-wise
  * everywhere), so nothing is exchanged on the data path until sample() returns (markov_jump_hmc.py:150-173,293-338).

@@ -36,6 +36,10 @@ class EngineError(RuntimeError):
     pass
 
 
+class EngineValueError(EngineError, ValueError):
+    """MJHMC_ERR_INVALID from an entry point whose wrapper promises ValueError for a refused argument (check_args)"""
+
+
 _P = ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -131,6 +135,9 @@ PROTOTYPES = {
     'mjhmc_leapfrog': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _P, _P, _P, _P, _P]),
     'mjhmc_ring_autocor': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     'mjhmc_autocor': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),
+    'mjhmc_grid_lagcov': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    'mjhmc_ring_lagcov': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    'mjhmc_lagcov': (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     'mjhmc_draw_from': (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, _P, ctypes.POINTER(ctypes.c_int64)]),
     'mjhmc_min_idx': (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int64, _P]),
     'mjhmc_comm_unique_id': (ctypes.c_int, [_P]),
@@ -201,6 +208,14 @@ def check(rc, lib=None):
     if rc != 0:
         msg = (lib or load()).mjhmc_last_error()
         raise EngineError('libmjhmc_hip: %s (status %d)' % (msg.decode() if msg else '?', rc))
+
+
+def check_args(rc, lib=None):
+    """``check``, with MJHMC_ERR_INVALID raised as a ValueError (that is an EngineError too) carrying the library's message"""
+    if rc == -1:
+        msg = (lib or load()).mjhmc_last_error()
+        raise EngineValueError('libmjhmc_hip: %s (status %d)' % (msg.decode() if msg else '?', rc))
+    check(rc, lib)
 
 
 def as_f64(a, shape=None):

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "autocor.hpp"
+#include "lagcov.hpp"
 #include "handles.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -2446,6 +2447,27 @@ int mjhmc_autocor(mjhmc_ctx* ctx, const double* samples, int64_t n_series, int n
   HIPCHK(hipSetDevice(ctx->device));
   std::string err;
   const int rc = autocor_from_host(nullptr, samples, n_series, n_samples, linear, host_out, err);
+  return rc ? fail(rc, err) : 0;
+}
+
+int mjhmc_ring_lagcov(mjhmc_sampler* s, int slot0, int n, int max_lag, const double* shift, double* A_out, double* S_out) {
+  if (!s || !A_out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (slot0 < 0 || n < 1 || (int64_t)slot0 + n > s->ring_slots)
+    return fail(MJHMC_ERR_INVALID, "ring slots [" + std::to_string(slot0) + ", " + std::to_string((int64_t)slot0 + n) +
+                                       ") are outside the ring of " + std::to_string(s->ring_slots));
+  HIPCHK(hipSetDevice(s->ctx->device));
+  const RingView view{(const char*)s->ring + (size_t)slot0 * mat_bytes(s), s->dtype, s->Npad, s->N, s->D, s->sh.pitch};
+  std::string err;
+  const int rc = lagcov_from_ring(s->stream, view, n, max_lag, shift, A_out, S_out, err);
+  return rc ? fail(rc, err) : 0;
+}
+
+int mjhmc_lagcov(mjhmc_ctx* ctx, const double* samples, int n_dims, int64_t n_batch, int n_samples, int max_lag,
+                 const double* shift, double* A_out, double* S_out) {
+  if (!ctx || !samples || !A_out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  std::string err;
+  const int rc = lagcov_from_host(nullptr, samples, n_dims, n_batch, n_samples, max_lag, shift, A_out, S_out, err);
   return rc ? fail(rc, err) : 0;
 }
 

@@ -42,6 +42,7 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "lagcov.hpp"
 
 namespace {
 
@@ -384,6 +385,18 @@ int mjhmc_timegrid_autocor(mjhmc_timegrid* tg, int slot0, int n, int linear, dou
   TRY(timegrid_check_slots(tg, slot0, n, covered, "covered grid"));
   std::string err;
   const int rc = autocor_from_ring(s->stream, tg->view(slot0), n, linear, host_out, err);
+  return rc ? mjhmc_fail(rc, err) : 0;
+}
+
+int mjhmc_grid_lagcov(mjhmc_timegrid* tg, int slot0, int n, int max_lag, const double* shift, double* A_out, double* S_out) {
+  if (!tg || !A_out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  mjhmc_sampler* s = tg->s;
+  HIPCHK(hipSetDevice(s->ctx->device));
+  int covered = 0, max_filled = 0;
+  TRY(timegrid_progress(tg, &covered, &max_filled));
+  TRY(timegrid_check_slots(tg, slot0, n, covered, "covered grid"));
+  std::string err;
+  const int rc = lagcov_from_ring(s->stream, tg->view(slot0), n, max_lag, shift, A_out, S_out, err);
   return rc ? mjhmc_fail(rc, err) : 0;
 }
 

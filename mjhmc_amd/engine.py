@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr, as_f64
+from ._lib import check, check_args, ptr, as_f64
 
 _DTYPES = {'float64': _lib.F64, 'f64': _lib.F64, np.float64: _lib.F64, 'float32': _lib.F32, 'f32': _lib.F32,
            np.float32: _lib.F32, 'bfloat16': _lib.BF16, 'bf16': _lib.BF16}
@@ -20,6 +20,14 @@ def dtype_code(dtype):
         return _DTYPES[dtype]
     except KeyError:
         raise ValueError('dtype must be float64, float32 or bfloat16, got %r' % (dtype,))
+
+
+def _lagcov_args(ndims, max_lag, shift):
+    """(max_lag, shift or None, A (max_lag + 1, ndims), S (ndims,)) of a lag_cov call; the range checks are the library's"""
+    max_lag = int(max_lag)
+    if shift is not None:
+        shift = as_f64(shift, (ndims,))
+    return max_lag, shift, np.empty((max(max_lag, 0) + 1, ndims)), np.empty(ndims)
 
 
 class Context(object):
@@ -54,6 +62,19 @@ class Context(object):
                                      1 if linear else 0, ptr(out)), self.lib)
         return out
 
+    def lag_cov(self, samples, max_lag, shift=None):
+        """Per-dimension lag sums of a host array [n_dims, n_batch, n_samples]: ``(A, S)`` with ``A[k, d] = sum_p sum_t u_t
+        u_{t+k}`` (linear in time, k = 0 .. max_lag <= min(n_samples - 1, 256)), ``S[d] = sum_p sum_t u_t``, u = x - shift[d]
+        (``shift=None``: zeros).  The array is re-tiled on the device and read by the kernels of ``ring_lag_cov``; see
+        mjhmc_lagcov in include/mjhmc_hip.h.  A refused argument raises ValueError with the library's message."""
+        samples = np.ascontiguousarray(samples, dtype=np.float64)
+        if samples.ndim != 3:
+            raise ValueError('samples must be [n_dims, n_batch, n_samples], got shape %r' % (samples.shape,))
+        D, N, n = samples.shape
+        max_lag, shift, A, S = _lagcov_args(D, max_lag, shift)
+        check_args(self.lib.mjhmc_lagcov(self.handle, ptr(samples), int(D), int(N), int(n), max_lag, ptr(shift), ptr(A), ptr(S)),
+                   self.lib)
+        return A, S
 
     def draw_from(self, rates, unit_exp):
         """Waiting times ``(1 / rate) * e`` (inf where the rate is 0); returns (draws, first_bad) with first_bad = -1
@@ -374,6 +395,13 @@ class DeviceSampler(object):
         check(self.lib.mjhmc_ring_autocor(self.handle, int(slot0), int(n), 1 if linear else 0, ptr(out)), self.lib)
         return out
 
+    def ring_lag_cov(self, slot0, n, max_lag, shift=None):
+        """Per-dimension lag sums over time of ring slots [slot0, slot0 + n): ``(A (max_lag + 1, ndims), S (ndims,))``, see
+        mjhmc_ring_lagcov in include/mjhmc_hip.h.  A refused argument raises ValueError with the library's message."""
+        max_lag, shift, A, S = _lagcov_args(self.ndims, max_lag, shift)
+        check_args(self.lib.mjhmc_ring_lagcov(self.handle, int(slot0), int(n), max_lag, ptr(shift), ptr(A), ptr(S)), self.lib)
+        return A, S
+
     def ring_copy(self, src_slot, dst_slot):
         """Ring slot ``src_slot`` (state and dwelling times) copied to ``dst_slot`` on the device."""
         check(self.lib.mjhmc_ring_copy(self.handle, int(src_slot), int(dst_slot)), self.lib)
@@ -633,6 +661,14 @@ class DeviceTimeGrid(object):
         out = np.empty(int(n), dtype=np.float64)
         check(self.lib.mjhmc_timegrid_autocor(self.handle, int(slot0), int(n), 1 if linear else 0, ptr(out)), self.lib)
         return out
+
+    def lag_cov(self, slot0, n, max_lag, shift=None):
+        """Per-dimension lag sums over time of grid slots [slot0, slot0 + n) (all of them covered): ``(A (max_lag + 1, ndims),
+        S (ndims,))``, see mjhmc_grid_lagcov in include/mjhmc_hip.h.  A refused argument raises ValueError with the
+        library's message."""
+        max_lag, shift, A, S = _lagcov_args(self.ndims, max_lag, shift)
+        check_args(self.lib.mjhmc_grid_lagcov(self.handle, int(slot0), int(n), max_lag, ptr(shift), ptr(A), ptr(S)), self.lib)
+        return A, S
 
     def reset(self):
         check(self.lib.mjhmc_timegrid_reset(self.handle), self.lib)

@@ -64,6 +64,56 @@ def autocorrelation(samples, e_evals, grad_evals, half_window=True, normalize=Tr
     return autocor, e_evals, grad_evals
 
 
+def integrated_autocorrelation_time(A, n, n_chains):
+    """Per-dimension autocorrelation, integrated autocorrelation time and truncation window from centred linear lag sums.
+
+    A: (K + 1, D) float64, ``A[k, d] = sum over chains and t < n - k of u_t u_{t+k}`` with u the series minus its mean
+    (``Paths.lag_cov``, ``DeviceTimeGrid.lag_cov``: the sums of all ``n_chains`` chains over ``n`` grid points).
+    Returns ``(rho (K + 1, D), tau (D,), window (D,) int, converged (D,) bool)``:
+
+      rho[k]   = (A[k] / (n_chains (n - k))) / (A[0] / (n_chains n))                  lag-product means over the one of lag 0
+      Gamma_m  = rho[2m] + rho[2m + 1],  m < M = (K + 1) // 2                         Geyer's sums of adjacent pairs
+      m*       = the first m with Gamma_m <= 0 (initial positive sequence), or M if there is none: the window was too
+                 short and converged[d] = False
+      Gamma'_m = min(Gamma'_{m-1}, Gamma_m),  m < m*                                  (initial monotone sequence)
+      tau      = -1 + 2 sum_{m < m*} Gamma'_m                                         in grid steps
+      window   = 2 m*                                                                 the lags that entered tau
+
+    m* = 0 (no pair at all: K = 0, or a first pair that is not positive) gives tau = NaN and converged = False.  A dimension
+    with A[0] = 0 (a constant series) or a sum that is not finite gives NaN throughout, window 0 and converged = False,
+    without floating-point warnings.  The effective sample size of a dimension is n_chains n / tau."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim == 1:
+        A = A[:, None]
+    if A.ndim != 2 or A.shape[0] < 1:
+        raise ValueError('A must be (max_lag + 1, ndims), got shape %r' % (A.shape,))
+    K, D = A.shape[0] - 1, A.shape[1]
+    n, n_chains = int(n), int(n_chains)
+    if n_chains < 1 or n < K + 1:
+        raise ValueError('need n_chains >= 1 and n > max_lag = %d, got n_chains = %d, n = %d' % (K, n_chains, n))
+    ok = np.isfinite(A).all(axis=0) & (A[0] > 0)
+    safe = np.where(ok, A, 1.0)
+    k = np.arange(K + 1, dtype=np.float64)[:, None]
+    rho = np.where(ok, (safe / (n_chains * (n - k))) / (safe[0] / (float(n_chains) * n)), np.nan)
+    M = (K + 1) // 2
+    tau = np.full(D, np.nan)
+    window = np.zeros(D, dtype=np.int64)
+    converged = np.zeros(D, dtype=bool)
+    if M == 0:
+        return rho, tau, window, converged
+    gamma = np.where(ok, rho[0:2 * M:2] + rho[1:2 * M:2], 0.0)          # (M, D); a dead dimension stops at m* = 0
+    stop = gamma <= 0
+    m_star = np.where(stop.any(axis=0), np.argmax(stop, axis=0), M)
+    mono = np.minimum.accumulate(gamma, axis=0)
+    inside = np.arange(M)[:, None] < m_star[None, :]
+    total = np.where(inside, mono, 0.0).sum(axis=0)
+    live = ok & (m_star > 0)
+    tau = np.where(live, -1.0 + 2.0 * total, np.nan)
+    window = np.where(ok, 2 * m_star, 0).astype(np.int64)
+    converged = live & (m_star < M)
+    return rho, tau, window, converged
+
+
 def calculate_autocorrelation(sampler, distribution, num_steps=None, num_grad_steps=None, sample_steps=1,
                               half_window=False, use_cached_var=False, replay=None, **kwargs):
     """mjhmc/misc/autocor.py:10-35.  Returns (autocor, e_evals, grad_evals).

@@ -170,6 +170,24 @@ class Marginals(object):
         return self.quantile(tail), self.quantile(1.0 - tail)
 
 
+class AutocorrelationTimes(object):
+    """What ``Paths.iat()`` returns, per dimension: ``rho`` (max_lag + 1, ndims), ``tau`` (grid steps), ``tau_time``
+    (process time), ``tau_grad_evals`` (gradient evaluations per chain), ``window`` (lags that entered tau), ``converged``;
+    ``n`` grid points and ``max_lag`` as used."""
+
+    def __init__(self, rho, tau, tau_time, tau_grad_evals, window, converged, n, max_lag):
+        self.rho, self.tau, self.tau_time, self.tau_grad_evals = rho, tau, tau_time, tau_grad_evals
+        self.window, self.converged, self.n, self.max_lag = window, converged, int(n), int(max_lag)
+
+
+class EffectiveSamples(object):
+    """What ``Paths.ess()`` returns, per dimension: ``ess`` = n_chains n / tau, ``ess_per_grad`` = ess over the run's
+    gradient evaluations (all chains), and the ``tau``, ``window`` and ``converged`` they come from."""
+
+    def __init__(self, ess, ess_per_grad, tau, window, converged):
+        self.ess, self.ess_per_grad, self.tau, self.window, self.converged = ess, ess_per_grad, tau, window, converged
+
+
 class Paths(object):
     """What ``paths()`` returns: the jump process of every chain sampled on the uniform time grid t_j = j ``dt``,
     j < ``n_grid`` -- a fair sample with its time order kept.  The grid stays on the device (csrc/timegrid.hip) until
@@ -185,7 +203,12 @@ class Paths(object):
     this rank in a sharded run.  ``autocor(n, linear)`` is the autocorrelation along the grid, taken on the device:
     ``linear=False`` is ``fft_autocor`` of that array (circular, 1 at lag 0), ``linear=True`` the lag-product means
     np.mean(x[:, :, :-k] * x[:, :, k:]) divided by the one of lag 0; lag k is process time k ``dt``.  Both refuse
-    ``n > covered``: a grid point some chain has not reached is no sample."""
+    ``n > covered``: a grid point some chain has not reached is no sample.
+
+    Per dimension, also on the device (csrc/lagcov.hip) and over all ranks: ``lag_cov(max_lag, n, center)`` are the linear
+    lag sums of the (centred) series, ``iat(max_lag, n)`` the autocorrelation, the integrated autocorrelation time and its
+    truncation window (``misc.autocor.integrated_autocorrelation_time``), ``ess(max_lag, n)`` the effective sample size
+    ``n_chains n / tau`` and what one effective sample costs in gradient evaluations."""
 
     def __init__(self, grid, dt, n_grid, covered, mean_time, grad_evals_per_chain, n_chains, comm=None):
         self._grid, self._comm = grid, comm
@@ -216,6 +239,46 @@ class Paths(object):
         if linear:
             sums = sums / (n - np.arange(n, dtype=np.float64))
         return sums / sums[0]
+
+    def lag_cov(self, max_lag, n=None, center=True):
+        """``(A, S, shift)``: ``A[k, d] = sum over chains and t < n - k of u_t u_{t+k}``, k = 0 .. ``max_lag`` <= min(n - 1,
+        256), and ``S[d] = sum u_t`` with u = x - shift[d], over the first ``n`` (default ``covered``) grid points of every
+        chain of every rank.  ``center=True`` takes shift = the mean over chains and grid points, from a first device pass
+        with ``max_lag`` 0 (its S, added over the ranks, over ``n_chains n``); ``center=False`` takes zeros.  A refused
+        ``max_lag`` raises ValueError with the library's message."""
+        n = self._length(n)
+        shift = np.zeros(self._grid.ndims)
+        if center:
+            S = self._grid.lag_cov(0, n, 0)[1]
+            if self._comm is not None:
+                S = self._comm.allreduce_f64(S)
+            shift = S / (float(self.n_chains) * n)
+        A, S = self._grid.lag_cov(0, n, max_lag, shift if center else None)
+        if self._comm is not None:                        # column shards add their lag sums
+            A = self._comm.allreduce_f64(A.ravel()).reshape(A.shape)
+            S = self._comm.allreduce_f64(S)
+        return A, S, shift
+
+    def iat(self, max_lag=None, n=None):
+        """Per dimension: the autocorrelation ``rho`` (max_lag + 1, ndims) of the centred series, the integrated
+        autocorrelation time ``tau`` in grid steps, ``tau_time = tau dt`` in process time, ``tau_grad_evals = tau dt
+        grad_evals_per_time`` in gradient evaluations per chain, the truncation ``window`` and ``converged`` (False: the
+        window ended before the pair sums turned non-positive -- take a larger ``max_lag`` or a longer run); see
+        ``misc.autocor.integrated_autocorrelation_time``.  ``max_lag=None`` takes min(n - 1, 256)."""
+        from ..misc.autocor import integrated_autocorrelation_time
+        n = self._length(n)
+        max_lag = min(n - 1, 256) if max_lag is None else int(max_lag)
+        A, _, _ = self.lag_cov(max_lag, n, center=True)
+        rho, tau, window, converged = integrated_autocorrelation_time(A, n, self.n_chains)
+        return AutocorrelationTimes(rho, tau, tau * self.dt, tau * self.dt * self.grad_evals_per_time, window, converged, n,
+                                    max_lag)
+
+    def ess(self, max_lag=None, n=None):
+        """Per dimension: ``ess = n_chains n / tau`` and ``ess_per_grad = ess / (n_chains grad_evals_per_chain)``, effective
+        samples per gradient evaluation of the run; ``tau``, ``window`` and ``converged`` of ``iat`` ride along."""
+        t = self.iat(max_lag, n)
+        ess = float(self.n_chains) * t.n / t.tau
+        return EffectiveSamples(ess, ess / (self.n_chains * self.grad_evals_per_chain), t.tau, t.window, t.converged)
 
     def close(self):
         if self._grid is not None:
