@@ -417,6 +417,44 @@ int mjhmc_histogram_read(mjhmc_histogram* h, uint64_t* count, uint64_t* mass, ui
 /* zero tables and totals; range, bins and quantum stay */
 int mjhmc_histogram_reset(mjhmc_histogram* h);
 
+/* Weighted JOINT histograms of pairs of state dimensions over ring blocks, kept on the device (csrc/pairhist.hip): the
+ * picture the reference draws with hist_2d / gauss_2d / jump_plot (mjhmc/misc/plotting.py) -- what np.histogram2d of two
+ * rows of sample(preserve_order=True) (markov_jump_hmc.py:150-173, 293-338), weighted by the holding times for the jump
+ * samplers, is on the host.  The contract is that of mjhmc_histogram_accumulate, taken per axis.
+ * n_pairs = P pairs (i_p, j_p) of state dimensions (pairs: int32 [P][2]; 0 <= i, j < ndims; i == j, repeated pairs and
+ * both orders of a pair are legal), n_bins = B bins per axis, per pair and axis a range lo[p][a] < hi[p][a] (lo, hi:
+ * double [P][2], finite; a = 0 the i axis, a = 1 the j axis), one `quantum` q, a positive power of two.  With
+ * inv[p][a] = B / (hi[p][a] - lo[p][a]) in float64, for every state (its elements widened exactly to float64) of weight w:
+ *     t_a = (x_a - lo[p][a]) * inv[p][a]          two rounded float64 operations, not fused
+ *     b_a = 0 when !(t_a >= 0) (NaN lands here);  B + 1 when t_a >= B;  1 + (int)t_a otherwise
+ *     u   = rint(w / q)                           nearest-even; the division is exact
+ *     count[p][b_1][b_0] += 1;  mass[p][b_1][b_0] += u       uint64 tables [P][B + 2][B + 2], the i axis fastest
+ * and W_units += u once per state.  Every sum is an integer: the tables are bit-identical from run to run, do not depend
+ * on how a run is cut into blocks, and add exactly over ranks; there is no floating-point atomic in the pass.  With equal
+ * range, B and q, summing pair p's tables over the j axis (all B + 2 entries, outer bins included) gives exactly dimension
+ * i_p's row of mjhmc_histogram's tables of the same block.
+ * Limits, each refused with MJHMC_ERR_INVALID and a message that names it: 1 <= P <= 64, 1 <= B <= 128; a sampler of 2^32
+ * particles or more is refused with MJHMC_ERR_UNSUPPORTED (N < 2^32).
+ * Ownership as for mjhmc_histogram: a pair histogram belongs to the sampler it was created on (and to its ring: a
+ * re-allocated ring invalidates it), mjhmc_sampler_destroy frees every one still alive and the handle is INVALID from
+ * then on. */
+typedef struct mjhmc_pairhist mjhmc_pairhist;
+int mjhmc_pairhist_create(mjhmc_sampler* s, int n_pairs, const int32_t* pairs, int n_bins, const double* lo, const double* hi,
+                          double quantum, mjhmc_pairhist** out);
+int mjhmc_pairhist_destroy(mjhmc_pairhist* h);
+/* Adds the n states of ring slots [x_slot0, x_slot0 + n) with the weights of dwell-ring slots [w_slot0, w_slot0 + n),
+ * or unit weights for w_slot0 == -1: the pairing of mjhmc_histogram_accumulate (a jump sampler takes w_slot0 =
+ * x_slot0 + 1).  Rows p >= N and the dwell ring's padding are never read.  The weights are checked on the device ahead
+ * of the pass by the 1-D pass's own check; a refused block adds nothing, with that pass's codes and messages:
+ * MJHMC_ERR_NONFINITE: a weight that is not finite, or negative.  MJHMC_ERR_INVALID: a weight with w / q >= 2^53, a block
+ * that would take W_units to 2^63 or beyond, slots outside the ring, n < 1, or a ring re-allocated since create. */
+int mjhmc_pairhist_accumulate(mjhmc_pairhist* h, int x_slot0, int w_slot0, int n);
+/* count, mass: n_pairs * (n_bins + 2) * (n_bins + 2) values each, table p row b_1 = [underflow of i, i bins 0 .. n_bins - 1,
+ * overflow of i]; the total of the units and the number of (slot, particle) states added so far. */
+int mjhmc_pairhist_read(mjhmc_pairhist* h, uint64_t* count, uint64_t* mass, uint64_t* W_units, int64_t* n_states);
+/* zero tables and totals; pairs, ranges, bins and quantum stay */
+int mjhmc_pairhist_reset(mjhmc_pairhist* h);
+
 /* Device functionals: statistics of caller expressions g(x) of the recorded states (csrc/functionals.hip), for which
  * the reference has only sample(preserve_order=True) (markov_jump_hmc.py:150-173, 293-338) and NumPy on the host.  The
  * coupled-energy convention of mjhmc_energy_create_expr_coupled, as an observable:
@@ -462,6 +500,9 @@ int mjhmc_estimator_create_on(mjhmc_functionals* f, int want_cov, mjhmc_estimato
 int mjhmc_chainstats_create_on(mjhmc_functionals* f, int n_parts, mjhmc_chainstats** out);
 int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo, const double* hi, double quantum,
                               mjhmc_histogram** out);
+/* mjhmc_pairhist_create on the derived ring: pairs of the K functional values */
+int mjhmc_pairhist_create_on(mjhmc_functionals* f, int n_pairs, const int32_t* pairs, int n_bins, const double* lo,
+                             const double* hi, double quantum, mjhmc_pairhist** out);
 
 /* Fair sample paths on a uniform time grid, kept on the device (csrc/timegrid.hip): the one result the weighted
  * accumulators above cannot give -- a fair sample with its time order kept.  The reference's sample(resample=True)

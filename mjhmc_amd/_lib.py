@@ -113,6 +113,12 @@ PROTOTYPES = {
     'mjhmc_histogram_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'mjhmc_histogram_read': (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)]),
     'mjhmc_histogram_reset': (ctypes.c_int, [_P]),
+    'mjhmc_pairhist_create': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_pairhist_create_on': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_pairhist_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_pairhist_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_pairhist_read': (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_pairhist_reset': (ctypes.c_int, [_P]),
     'mjhmc_functionals_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_functionals_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, _P, ctypes.c_size_t, ctypes.c_char_p,
                                                 ctypes.POINTER(_P)]),

@@ -144,6 +144,7 @@ void functionals_free(mjhmc_functionals* f) {
   estimator_free_owned(s, f);
   chainstats_free_owned(s, f);
   histogram_free_owned(s, f);
+  pairhist_free_owned(s, f);
   for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring})
     if (p) (void)hipFree(p);
   if (f->module) (void)hipModuleUnload(f->module);

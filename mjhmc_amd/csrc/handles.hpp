@@ -89,6 +89,7 @@ constexpr int kMaxDenseParts = 4;   // free-running parts of a dense batch (iter
 struct mjhmc_estimator;  // weighted-moment accumulator over ring blocks (estimators.hip)
 struct mjhmc_chainstats; // per-chain weighted sums over ring blocks (chainstats.hip)
 struct mjhmc_histogram;  // weighted marginal histograms over ring blocks (histograms.hip)
+struct mjhmc_pairhist;   // weighted joint histograms of pairs of dimensions over ring blocks (pairhist.hip)
 struct mjhmc_functionals;  // caller expressions g(x) evaluated into a derived ring (functionals.hip)
 struct mjhmc_timegrid;   // the jump process sampled on a uniform time grid, in a grid ring of its own (timegrid.hip)
 struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (api.hip)
@@ -157,7 +158,8 @@ struct mjhmc_sampler {
   std::vector<mjhmc_estimator*> estimators;   // accumulators created on this sampler (estimators.hip); freed with it
   std::vector<mjhmc_chainstats*> chainstats;  // per-chain accumulators created on this sampler (chainstats.hip); freed with it
   std::vector<mjhmc_histogram*> histograms;   // histogram accumulators created on this sampler (histograms.hip); freed with it
-  std::vector<mjhmc_functionals*> functionals;   // functionals created on this sampler (functionals.hip); freed with it, BEFORE the three lists above
+  std::vector<mjhmc_pairhist*> pairhists;     // pair-histogram accumulators created on this sampler (pairhist.hip); freed with it
+  std::vector<mjhmc_functionals*> functionals;   // functionals created on this sampler (functionals.hip); freed with it, BEFORE the four lists above
   std::vector<mjhmc_timegrid*> timegrids;     // time grids created on this sampler (timegrid.hip); freed with it
   double* stage = nullptr;  // device staging, float64 host layout
   size_t stage_elems = 0;
@@ -204,7 +206,10 @@ void chainstats_free_all(mjhmc_sampler* s);
 // histograms.hip
 void histogram_free_all(mjhmc_sampler* s);
 
-// functionals.hip (frees the accumulator handles created on each, too: call it before the three above)
+// pairhist.hip
+void pairhist_free_all(mjhmc_sampler* s);
+
+// functionals.hip (frees the accumulator handles created on each, too: call it before the four above)
 void functionals_free_all(mjhmc_sampler* s);
 
 // timegrid.hip

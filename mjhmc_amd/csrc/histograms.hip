@@ -264,10 +264,44 @@ HistogramPlan histogram_plan(const RingView& r, int bins) {
   const int64_t want = std::max<int64_t>(1, 1024 / pl.gy);
   const int64_t have = (r.N + (int64_t)rw * kRowsInFlight - 1) / ((int64_t)rw * kRowsInFlight);
   pl.gx = (int)std::max<int64_t>(1, std::min(want, have));
-  pl.check_gx = (int)std::max<int64_t>(1, std::min<int64_t>(256, (r.N + 255) / 256));
-  pl.check_gy = kCheckMaxGy;
+  histogram_check_grid(r.N, &pl.check_gx, &pl.check_gy);
   pl.lds_bytes = (size_t)pl.strip * per_dim;
   return pl;
+}
+
+void histogram_check_grid(int64_t N, int* check_gx, int* check_gy) {
+  *check_gx = (int)std::max<int64_t>(1, std::min<int64_t>(256, (N + 255) / 256));
+  *check_gy = kCheckMaxGy;
+}
+
+void histogram_weight_pass(hipStream_t st, const double* w, int64_t Npad, int64_t N, int n, double inv_q, int check_gx,
+                           int check_gy, u64* partial, u64* W_units, int* bad) {
+  int n_partial = 0;
+  u64 extra = 0;
+  if (w) {
+    const int gy = std::min(n, check_gy);
+    n_partial = check_gx * gy;
+    hipLaunchKernelGGL(hist_check_kernel, dim3(check_gx, gy), dim3(256), 0, st, w, Npad, N, n, inv_q, partial, bad);
+  } else {
+    // unit weights: n * N states of rint(1 / q) units each (the caller refused 1 / q >= 2^53)
+    const u64 unit = (u64)rint(inv_q), states = (u64)n * (u64)N;
+    extra = (unit && states > (kUnitsLimit - 1) / unit) ? kUnitsLimit : unit * states;
+  }
+  hipLaunchKernelGGL(hist_decide_kernel, dim3(1), dim3(256), 0, st, partial, n_partial, extra, W_units, bad);
+}
+
+int histogram_refusal(int bad, int w_slot0, int n) {
+  const std::string where = "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string(w_slot0 + n) + ")";
+  if (bad & kHistBadNonfinite)
+    return mjhmc_fail(MJHMC_ERR_NONFINITE, "a dwelling time in " + where +
+                                               " is not finite or is negative (a state whose total jump rate is zero "
+                                               "leaves an infinite one): nothing of this block was added");
+  if (bad & kHistBadTooLarge)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "a weight in " + where +
+                                             " is 2^53 quanta or more (w / quantum must stay below 2^53: take a larger "
+                                             "quantum): nothing of this block was added");
+  return mjhmc_fail(MJHMC_ERR_INVALID, "this block would take the total weight to 2^63 quanta or beyond (take a larger "
+                                       "quantum): nothing of this block was added");
 }
 
 int histogram_accumulate(hipStream_t st, const RingView& r, int n, const double* w, const double* lo, const double* inv,
@@ -277,18 +311,7 @@ int histogram_accumulate(hipStream_t st, const RingView& r, int n, const double*
     err = "the histogram pass counts a workgroup's states per bin in 32 bits: fewer than 2^32 particles";
     return MJHMC_ERR_UNSUPPORTED;
   }
-  int n_partial = 0;
-  u64 extra = 0;
-  if (w) {
-    const int gy = std::min(n, pl.check_gy);
-    n_partial = pl.check_gx * gy;
-    hipLaunchKernelGGL(hist_check_kernel, dim3(pl.check_gx, gy), dim3(256), 0, st, w, r.Npad, r.N, n, inv_q, partial, bad);
-  } else {
-    // unit weights: n * N states of rint(1 / q) units each (the caller refused 1 / q >= 2^53)
-    const u64 unit = (u64)rint(inv_q), states = (u64)n * (u64)r.N;
-    extra = (unit && states > (kUnitsLimit - 1) / unit) ? kUnitsLimit : unit * states;
-  }
-  hipLaunchKernelGGL(hist_decide_kernel, dim3(1), dim3(256), 0, st, partial, n_partial, extra, W_units, bad);
+  histogram_weight_pass(st, w, r.Npad, r.N, n, inv_q, pl.check_gx, pl.check_gy, partial, W_units, bad);
   // a workgroup's count of a bin is 32 bits wide: at most 2^32 - 1 states per launch of the pass
   const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>(n, 0xFFFFFFFFll / r.N));
   const dim3 grid(pl.gx, pl.gy), block(256);
@@ -481,17 +504,7 @@ int mjhmc_histogram_accumulate(mjhmc_histogram* h, int x_slot0, int w_slot0, int
   HIPCHK(hipStreamSynchronize(s->stream));
   if (bad) {
     HIPCHK(hipMemsetAsync(h->bad, 0, sizeof(int), s->stream));
-    const std::string where = "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string(w_slot0 + n) + ")";
-    if (bad & kHistBadNonfinite)
-      return mjhmc_fail(MJHMC_ERR_NONFINITE, "a dwelling time in " + where +
-                                                 " is not finite or is negative (a state whose total jump rate is zero "
-                                                 "leaves an infinite one): nothing of this block was added");
-    if (bad & kHistBadTooLarge)
-      return mjhmc_fail(MJHMC_ERR_INVALID, "a weight in " + where +
-                                               " is 2^53 quanta or more (w / quantum must stay below 2^53: take a larger "
-                                               "quantum): nothing of this block was added");
-    return mjhmc_fail(MJHMC_ERR_INVALID, "this block would take the total weight to 2^63 quanta or beyond (take a larger "
-                                         "quantum): nothing of this block was added");
+    return histogram_refusal(bad, w_slot0, n);
   }
   h->n_states += (int64_t)n * s->N;
   return 0;

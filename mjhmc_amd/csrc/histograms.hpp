@@ -36,3 +36,12 @@ constexpr int kHistBadTotal = 4;       // the block would take W_units to 2^63 o
 int histogram_accumulate(hipStream_t st, const RingView& r, int n, const double* w, const double* lo, const double* inv,
                          double inv_q, const HistogramPlan& plan, unsigned long long* partial, unsigned long long* count,
                          unsigned long long* mass, unsigned long long* W_units, int* bad, std::string& err);
+
+// The weight logic of a block on its own, for the passes that share it (pairhist.hip).  histogram_check_grid: the check's
+// grid for N particles; `partial` holds check_gx * check_gy values.  histogram_weight_pass: the check (w != nullptr) and the
+// decision of histogram_accumulate, two launches on `st`.  histogram_refusal: the error a raised flag becomes -- code
+// and message recorded through mjhmc_fail -- for the dwell slots [w_slot0, w_slot0 + n) of the refused block.
+void histogram_check_grid(int64_t N, int* check_gx, int* check_gy);
+void histogram_weight_pass(hipStream_t st, const double* w, int64_t Npad, int64_t N, int n, double inv_q, int check_gx,
+                           int check_gy, unsigned long long* partial, unsigned long long* W_units, int* bad);
+int histogram_refusal(int bad, int w_slot0, int n);

@@ -1,4 +1,4 @@
-// Where an accumulator handle (mjhmc_estimator, mjhmc_chainstats, mjhmc_histogram) reads its states from: the sampler's
+// Where an accumulator handle (mjhmc_estimator, mjhmc_chainstats, mjhmc_histogram, mjhmc_pairhist) reads its states from: the sampler's
 // own sample ring, or the derived ring of a mjhmc_functionals (functionals.hip).  The handles read base pointer, slot
 // bytes, slot count, dtype, D, pitch and generation through this descriptor only; particles (N, Npad), stream and
 // the dwell ring are the sampler's in both cases.
@@ -42,7 +42,8 @@ inline RingView ring_source_view(const mjhmc_sampler* s, const RingSource& r, in
   return RingView{r.base + (size_t)slot0 * r.slot_bytes, r.dtype, s->Npad, s->N, r.D, r.pitch};
 }
 
-// the handles of one owner among a sampler's (estimators.hip, chainstats.hip, histograms.hip): mjhmc_functionals_destroy
+// the handles of one owner among a sampler's (estimators.hip, chainstats.hip, histograms.hip, pairhist.hip): mjhmc_functionals_destroy
 void estimator_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f);
 void chainstats_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f);
 void histogram_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f);
+void pairhist_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f);

@@ -423,6 +423,13 @@ class DeviceSampler(object):
         and integer masses in units of ``quantum`` (a power of two).  The ring must exist (ring_alloc)."""
         return DeviceHistogram(self, bins, lo, hi, quantum)
 
+    def pair_histogram(self, pairs, bins, lo, hi, quantum=1.0):
+        """Weighted joint histograms of ``pairs`` [(i, j), ...] of state dimensions over blocks of this sampler's ring
+        (mjhmc_pairhist_*): ``bins`` bins per axis between ``lo`` and ``hi`` (scalars or (P, 2) arrays, column 0 the i
+        axis) plus an outer bin at either end of an axis, integer counts and integer masses in units of ``quantum`` (a
+        power of two).  The ring must exist (ring_alloc)."""
+        return DevicePairHistogram(self, pairs, bins, lo, hi, quantum)
+
     def functionals(self, values, stats=(), params=()):
         """K values g[k] = value_k(S; p) of every recorded state, S[j] = sum_d stat_j(x_d, d; p): C expressions evaluated on
         the device into a derived ring that the estimators read (mjhmc_functionals_*).  The ring must exist (ring_alloc)."""
@@ -685,6 +692,57 @@ class DeviceTimeGrid(object):
             pass
 
 
+class DevicePairHistogram(object):
+    """Per pair p = (i, j) and cell (b_j, b_i): count[p][b_j][b_i] states and mass[p][b_j][b_i] = sum of rint(w / quantum)
+    over the (slot, particle) states of the ring blocks given to ``accumulate`` whose elements x_i, x_j fall into bins b_i,
+    b_j of their axes -- per axis the bins of DeviceHistogram (include/mjhmc_hip.h: mjhmc_pairhist_create).  Integer sums:
+    bit-identical from run to run, whatever the blocks."""
+
+    def __init__(self, dev, pairs, bins, lo, hi, quantum=1.0, on=None):
+        """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
+        self.dev, self.lib, self.on = dev, dev.lib, on
+        self.ndims, self.bins, self.quantum = (dev.ndims if on is None else on.n_values), int(bins), float(quantum)
+        self.pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        self.n_pairs = P = self.pairs.shape[0]
+        self.lo = as_f64(np.broadcast_to(np.asarray(lo, dtype=np.float64), (P, 2)))
+        self.hi = as_f64(np.broadcast_to(np.asarray(hi, dtype=np.float64), (P, 2)))
+        h = ctypes.c_void_p()
+        create, src = (self.lib.mjhmc_pairhist_create, dev) if on is None else (self.lib.mjhmc_pairhist_create_on, on)
+        check(create(src.handle, P, ptr(self.pairs), self.bins, ptr(self.lo), ptr(self.hi), self.quantum, ctypes.byref(h)),
+              self.lib)
+        self.handle = h
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A refused block (a weight that is not finite, negative
+        or too large for the quantum) raises and adds nothing."""
+        check(self.lib.mjhmc_pairhist_accumulate(self.handle, int(x_slot0), int(w_slot0), int(n)), self.lib)
+
+    def read(self):
+        """(count (P, bins + 2, bins + 2) uint64, mass likewise in units of the quantum, W_units, n_states); the last
+        axis is the pair's first dimension"""
+        shape = (self.n_pairs, self.bins + 2, self.bins + 2)
+        count, mass = np.empty(shape, dtype=np.uint64), np.empty(shape, dtype=np.uint64)
+        W, n = ctypes.c_uint64(), ctypes.c_int64()
+        check(self.lib.mjhmc_pairhist_read(self.handle, ptr(count), ptr(mass), ctypes.byref(W), ctypes.byref(n)), self.lib)
+        return count, mass, int(W.value), int(n.value)
+
+    def reset(self):
+        check(self.lib.mjhmc_pairhist_reset(self.handle), self.lib)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
+                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
+            self.lib.mjhmc_pairhist_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def join_exprs(exprs):
     """one expression or a sequence of them -> the ';'-separated bytes the C ABI takes (None for none)"""
     exprs = [exprs] if isinstance(exprs, str) else list(exprs)
@@ -697,7 +755,7 @@ def join_exprs(exprs):
 class DeviceFunctionals(object):
     """K float64 values of every recorded state of a sampler, g[k] = value_k(S; p) with S[j] = sum_d stat_j(x_d, d; p),
     evaluated by one device pass from blocks of the sampler's ring into a derived ring of K-dimensional states
-    (include/mjhmc_hip.h: mjhmc_functionals_create).  ``estimator``, ``chain_stats`` and ``histogram`` give the sampler's
+    (include/mjhmc_hip.h: mjhmc_functionals_create).  ``estimator``, ``chain_stats``, ``histogram`` and ``pair_histogram`` give the sampler's
     accumulators on the derived ring: their ``x_slot0`` counts derived slots, ``w_slot0`` the sampler's dwell slots."""
 
     def __init__(self, dev, values, stats=(), params=()):
@@ -738,6 +796,9 @@ class DeviceFunctionals(object):
 
     def histogram(self, bins, lo, hi, quantum=1.0):
         return DeviceHistogram(self.dev, bins, lo, hi, quantum, on=self)
+
+    def pair_histogram(self, pairs, bins, lo, hi, quantum=1.0):
+        return DevicePairHistogram(self.dev, pairs, bins, lo, hi, quantum, on=self)
 
     def close(self):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)

@@ -170,6 +170,88 @@ class Marginals(object):
         return self.quantile(tail), self.quantile(1.0 - tail)
 
 
+class JointMarginals(object):
+    """What ``joint_marginals()`` returns: one weighted two-dimensional histogram per pair of dimensions.  Pure NumPy.
+
+    Built from the integer tables of ``DevicePairHistogram.read()`` (already summed over ranks): ``counts`` and ``units``
+    (P, bins + 2, bins + 2) uint64, indexed [pair][bin of the pair's SECOND dimension][bin of its FIRST dimension] -- per
+    axis bin 0 holds what fell below ``lo`` (and NaN), bin bins + 1 what fell at or above ``hi``, bins 1 .. bins the bins
+    between -- the total ``W_units`` and the number of states ``n_states``.  ``pairs`` (P, 2) are the dimensions (i, j),
+    ``lo`` and ``hi`` (P, 2) the range per pair and axis (column 0: i), ``quantum`` q the weight of one unit:
+
+      mass = q * units                                 |mass - the cell's sum of weights| <= 0.5 q counts
+      total_weight = q * W_units                       every pair's table adds up to W_units, exactly
+      edges_x, edges_y (P, bins + 1)                   the bin edges of the i axis and of the j axis
+      density (P, bins, bins)                          mass of the inner cells / (total_weight * cell area), [pair][j bin][i bin]:
+                                                       its sum times the cell area is 1 - out_of_range
+      out_of_range (P,)                                the share of the weight in any outer cell
+
+    ``marginal(p, axis)`` is the ``Marginals`` of one axis of pair p (0: i, 1: j), from the tables summed over the other
+    axis: the integers ``marginals()`` counts for that dimension on the same run and range.  ``hdr(level)`` is the
+    highest-density region."""
+
+    def __init__(self, pairs, lo, hi, bins, quantum, counts, units, W_units, n_states):
+        self.pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        self.n_pairs = P = self.pairs.shape[0]
+        self.lo = np.array(np.broadcast_to(np.asarray(lo, dtype=np.float64), (P, 2)))
+        self.hi = np.array(np.broadcast_to(np.asarray(hi, dtype=np.float64), (P, 2)))
+        self.bins, self.quantum = int(bins), float(quantum)
+        B = self.bins
+        self.counts = np.asarray(counts, dtype=np.uint64).reshape(P, B + 2, B + 2)
+        self.units = np.asarray(units, dtype=np.uint64).reshape(P, B + 2, B + 2)
+        self.W_units, self.n_states = int(W_units), int(n_states)
+        self.mass = self.quantum * self.units.astype(np.float64)
+        self.total_weight = self.quantum * float(self.W_units)
+        self.width = (self.hi - self.lo) / B                                  # (P, 2)
+        steps = np.arange(B + 1)[None, :]
+        self.edges_x = self.lo[:, :1] + steps * self.width[:, :1]
+        self.edges_y = self.lo[:, 1:] + steps * self.width[:, 1:]
+        self.edges_x[:, -1], self.edges_y[:, -1] = self.hi[:, 0], self.hi[:, 1]
+        W = float(self.W_units) if self.W_units else np.nan
+        inner = self.units[:, 1:-1, 1:-1]
+        self.cell_area = self.width[:, 0] * self.width[:, 1]
+        self.density = inner.astype(np.float64) / (W * self.cell_area[:, None, None])
+        self._inner_units = inner.reshape(P, -1).sum(axis=1, dtype=np.uint64)
+        outer = self.units.reshape(P, -1).sum(axis=1, dtype=np.uint64) - self._inner_units
+        self.out_of_range = outer.astype(np.float64) / W
+
+    def marginal(self, p, axis):
+        """the ``Marginals`` (one dimension) of pair ``p``'s axis 0 (its first dimension) or 1 (its second)"""
+        p, axis = int(p), int(axis)
+        if not 0 <= p < self.n_pairs or axis not in (0, 1):
+            raise ValueError('p must be in [0, %d) and axis 0 or 1' % self.n_pairs)
+        over = 0 if axis == 0 else 1                       # tables are [j bin][i bin]: the i axis remains after summing over j
+        return Marginals([self.lo[p, axis]], [self.hi[p, axis]], self.bins, self.quantum,
+                         self.counts[p].sum(axis=over, dtype=np.uint64)[None, :], self.units[p].sum(axis=over, dtype=np.uint64)[None, :],
+                         self.W_units, self.n_states)
+
+    def hdr(self, level=0.9):
+        """The highest-density region: per pair the smallest set of inner cells, taken in order of falling density, that
+        holds at least ``level`` of the total weight.  Returns ``(threshold (P,), mask (P, bins, bins) bool)``: the density
+        of the last cell taken, and the cells, indexed as ``density``.  Cells of equal density are taken in order of their
+        (flattened) index.  ValueError when ``out_of_range[p] > 1 - level``: the inner cells do not hold that much."""
+        from fractions import Fraction
+        if not 0.0 < level <= 1.0:
+            raise ValueError('level must be in (0, 1]')
+        if not self.W_units:
+            raise ValueError('the tables hold no weight')
+        need = Fraction(level) * self.W_units
+        need = int(need) + (1 if need != int(need) else 0)                 # units the region must hold: ceil(level * W_units)
+        B = self.bins
+        threshold, mask = np.empty(self.n_pairs), np.zeros((self.n_pairs, B * B), dtype=bool)
+        for p in range(self.n_pairs):
+            if int(self._inner_units[p]) < need:
+                raise ValueError('pair %d (%d, %d): %.3g of the weight lies outside the range, more than 1 - level = %.3g: '
+                                 'widen the range' % (p, self.pairs[p, 0], self.pairs[p, 1], self.out_of_range[p], 1.0 - level))
+            u = self.units[p, 1:-1, 1:-1].reshape(-1)
+            order = np.argsort(u.max() - u, kind='stable')                 # falling units (exact in uint64), ties by cell index
+            cum = np.cumsum(u[order], dtype=np.uint64)
+            k = int(np.searchsorted(cum, np.uint64(need), side='left'))
+            mask[p, order[:k + 1]] = True
+            threshold[p] = self.density[p].reshape(-1)[order[k]]
+        return threshold, mask.reshape(self.n_pairs, B, B)
+
+
 class AutocorrelationTimes(object):
     """What ``Paths.iat()`` returns, per dimension: ``rho`` (max_lag + 1, ndims), ``tau`` (grid steps), ``tau_time``
     (process time), ``tau_grad_evals`` (gradient evaluations per chain), ``window`` (lags that entered tau), ``converged``;
@@ -297,7 +379,7 @@ class Functionals(object):
         S[j] = sum_d stat_j(x_d, d; p),   g[k] = value_k(S; p)
     -- ``values`` (K C expressions of ``S[j]`` and ``p[m]``), ``stats`` (J <= 8 C expressions of ``x``, ``d`` and ``p[m]``),
     ``params`` (float64), ``names`` (K strings) and ``n_values`` = K -- checked to compile, bound to no device.  Pass it
-    as ``of=`` to ``expectations()``, ``diagnostics()`` or ``marginals()``: their results then have K "dimensions"."""
+    as ``of=`` to ``expectations()``, ``diagnostics()``, ``marginals()`` or ``joint_marginals()``: their results then have K "dimensions"."""
 
     def __init__(self, values, stats=(), params=(), names=None):
         self.values = [values] if isinstance(values, str) else [str(v) for v in values]
@@ -917,6 +999,93 @@ class HMCBase(object):
             from ..parallel import reduce_histogram
             counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
         return Marginals(lo, hi, bins, q, counts, units, W_units, n_states)
+
+    def joint_marginals(self, n_iter, pairs, bins=64, range=None, block=None, span=8.0, of=None):
+        """Weighted joint histograms of ``pairs`` [(i, j), ...] of dimensions over ``n_iter`` consecutive states of every
+        particle, accumulated on the device (csrc/pairhist.hip): the host receives 2 x P x (bins + 2)^2 integers whatever
+        the length of the run.  Returns a ``JointMarginals`` (density, marginals of either axis, highest-density regions).
+        1 <= P <= 64 pairs, 1 <= ``bins`` <= 128 per axis; i == j, repeated pairs and both orders of a pair are allowed.
+
+        The run itself is that of ``marginals(n_iter)``: the same iterations, weights, blocks, quantum rule and -- for
+        ``range=None`` -- the same moment pass over the first block (mean -/+ ``span`` standard deviations), the same
+        counters, ``dwelling_times`` and final state.  ``range``: ``(lo, hi)`` per DIMENSION, scalars or ndims-vectors: a
+        dimension has one range in every pair it appears in.  Sharded samplers use rank 0's ranges and quantum and the
+        smallest ``block`` of all ranks, and add their integer tables over ranks.
+
+        ``of``: a ``Functionals`` (``functionals()``): the same run, ``pairs`` index the K functional values (every block
+        is evaluated into a derived ring first; ``range`` entries are scalars or K-vectors)."""
+        n_iter, bins = int(n_iter), int(bins)
+        K = self.ndims if of is None else of.n_values
+        what = 'ndims' if of is None else 'n_values'
+        if n_iter < 1:
+            raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        if not 1 <= bins <= 128:
+            raise ValueError('bins must be in [1, 128], got %d' % bins)
+        pairs = np.asarray(pairs)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= 64 or pairs.dtype.kind not in 'iu':
+            raise ValueError('pairs must be 1 .. 64 pairs (i, j) of integers, got an array of shape %r' % (pairs.shape,))
+        pairs = pairs.astype(np.int64)
+        if pairs.min() < 0 or pairs.max() >= K:
+            raise ValueError('pairs must index [0, %s = %d)' % (what, K))
+        if range is not None:
+            if len(range) != 2:
+                raise ValueError('range must be (lo, hi)')
+            lo, hi = [np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (K,))) if np.size(v) in (1, K)
+                      else None for v in range]
+            if lo is None or hi is None:
+                raise ValueError('lo and hi must be scalars or have %s = %d entries' % (what, K))
+            if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+                raise ValueError('range needs finite lo < hi in every dimension')
+        elif not span > 0:
+            raise ValueError('span must be positive')
+        lead = 1 if self._dwell_weighted else 0
+        if block is None:
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
+        block = max(1, min(int(block), n_iter))
+        if self._comm is not None:
+            block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
+        self._dev.ring_alloc(block + lead)
+        w_slot0 = 1 if lead else -1
+        fn, hist, q = None, None, 1.0
+        try:
+            fn = None if of is None else self._open_functionals(of, block)
+            src = self._dev if fn is None else fn
+            for _, k in self._ring_blocks([n_iter], block):
+                if fn is not None:
+                    fn.evaluate(0, k, 0)
+                if hist is None:
+                    if range is None or lead:
+                        est = src.estimator(False)
+                        try:
+                            est.accumulate(0, k, w_slot0=w_slot0)
+                            W, S1, S2, _, n_first = self._reduce_sums(est.read())
+                        finally:
+                            est.close()
+                        if lead:
+                            q = 2.0 ** (np.floor(np.log2(W / n_first)) - 24)
+                        if range is None:
+                            mean = S1 / W
+                            sd = np.sqrt(np.maximum(S2 / W - mean * mean, 0.0))
+                            sd = np.where(sd > 0, sd, 1.0)             # (a constant coordinate still needs lo < hi)
+                            lo, hi = mean - span * sd, mean + span * sd
+                    if self._comm is not None:
+                        packed = self._comm.bcast(np.concatenate([lo, hi, [q]]), 0)
+                        lo, hi, q = packed[:K].copy(), packed[K:2 * K].copy(), float(packed[-1])
+                    hist = src.pair_histogram(pairs, bins, lo[pairs], hi[pairs], q)
+                hist.accumulate(0, k, w_slot0=w_slot0)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            counts, units, W_units, n_states = hist.read()
+        finally:
+            if hist is not None:
+                hist.close()
+            if fn is not None:
+                fn.close()
+        if self._comm is not None:
+            from ..parallel import reduce_histogram
+            counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
+        return JointMarginals(pairs, lo[pairs], hi[pairs], bins, q, counts, units, W_units, n_states)
 
     def paths(self, n_iter, n_grid=None, dt=None, block=None):
         """A fair sample of every chain with its time order kept: the process "chain p sits in state k for its holding
