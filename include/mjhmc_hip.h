@@ -481,6 +481,24 @@ typedef struct mjhmc_functionals mjhmc_functionals;
 int mjhmc_functionals_check(int ndims, const char* stats, const char* values, const char* include_dir);
 int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* values, const double* params, size_t nparams,
                              const char* include_dir, mjhmc_functionals** out);
+/* Energy observables: a functionals whose K = 3 values of every recorded state are
+ *     g[0] = E            the potential energy exactly as the sampler's own evaluation kernel returns it for the stored row
+ *                         (float32 for float32 / bfloat16 state, widened exactly)
+ *     g[1] = grad_sq      sum_{d < ndims} G_d * G_d, G = dE/dX of the same evaluation, each element widened exactly
+ *     g[2] = virial       sum_{d < ndims} x_d * G_d, x the stored state widened exactly
+ * -- what no sum of per-coordinate expressions gives for a coupled energy.  Integration by parts gives E[x . dE/dX] =
+ * ndims for every target with p(x) x -> 0 at infinity, so mean(virial) / ndims is a thermometer of the chain: 1 when it
+ * keeps exp(-E).  No expressions and no hipRTC: per slot mjhmc_functionals_evaluate runs the evaluation kernels of the
+ * sampler's energy on the ring slot (a ring slot has the layout of a state matrix) into scratch of the handle -- one
+ * gradient matrix and one energy vector, freed with the handle and by mjhmc_sampler_destroy -- and then one kernel
+ * (csrc/energy_observables.hpp) that forms the derived row [E, grad_sq, virial, 0.0]: products and sums in float64
+ * without contraction, in an order that is a function of (ndims, state type, row pitch) alone, so values are bit-identical
+ * from run to run and independent of the blocks.  A value that is not finite is reported as by any functionals, the
+ * message naming it (E, grad_sq, virial).  These evaluations are not part of the chain: no sampler state, counter or
+ * random stream is touched.  _info, _ring_alloc, _evaluate, _read, _destroy and every _create_on work as on any
+ * functionals.  MJHMC_ERR_INVALID: NULL arguments, no sample ring yet; MJHMC_ERR_UNSUPPORTED: a host-evaluated energy
+ * (MJHMC_E_HOST: the caller's callables are its only evaluation). */
+int mjhmc_functionals_create_energy(mjhmc_sampler* s, mjhmc_functionals** out);
 int mjhmc_functionals_destroy(mjhmc_functionals* f);
 /* K, and the bytes of one slot of the derived ring (Npad * pitchK * 8) */
 int mjhmc_functionals_info(mjhmc_functionals* f, int* n_values, uint64_t* slot_bytes);

@@ -122,6 +122,7 @@ PROTOTYPES = {
     'mjhmc_functionals_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_functionals_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, _P, ctypes.c_size_t, ctypes.c_char_p,
                                                 ctypes.POINTER(_P)]),
+    'mjhmc_functionals_create_energy': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
     'mjhmc_functionals_destroy': (ctypes.c_int, [_P]),
     'mjhmc_functionals_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
     'mjhmc_functionals_ring_alloc': (ctypes.c_int, [_P, ctypes.c_int]),
@@ -172,6 +173,8 @@ TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_ring_write': (ctypes.c_int, [_P, ctypes.c_int, _P]),
     'mjhmc_test_ring_fill_padding': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
     'mjhmc_test_timegrid_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
+    'mjhmc_test_functionals_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
+    'mjhmc_test_energy_observables_part': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
 }
 
 _lib = None

@@ -738,6 +738,12 @@ static int run_eval(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, con
                                : run_eval_t<float>(s, X, Gout, Eout, V, Vgen, EVout);
 }
 
+// E ([Npad] scalars) and dE/dX (a matrix) of the state matrix X, in the layout and element type the sampler's energy
+// family writes: what the energy observables evaluate every recorded slot with (functionals.hip)
+int sampler_eval_rows(mjhmc_sampler* s, const void* X, void* Gout, void* Eout) {
+  return run_eval(s, X, Gout, Eout, nullptr, nullptr, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------

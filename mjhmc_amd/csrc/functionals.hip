@@ -7,6 +7,10 @@
 // writes: float64 rows [Npad][pitchK], pitchK = pick_shape(K, MJHMC_F64).pitch, the layout of every sample ring.  The
 // accumulator handles (estimators.hip, chainstats.hip, histograms.hip) read either ring through RingSource
 // (ring_source.hpp), so moments, covariance, R-hat / ESS and histograms of g need no kernel of their own.
+//
+// A second kind of handle (mjhmc_functionals_create_energy) fills the same derived ring with the ENERGY OBSERVABLES
+// [E, grad_sq, virial] of every recorded state: no expressions and no hipRTC -- per slot the sampler's own evaluation
+// (api.hip: sampler_eval_rows) into scratch of the handle, then energy_observables_kernel (energy_observables.hpp).
 #include "functionals.hpp"
 
 #include <algorithm>
@@ -18,6 +22,7 @@
 #include <vector>
 
 #include "../../include/mjhmc_hip.h"
+#include "energy_observables.hpp"
 #include "handles.hpp"
 #include "ring_source.hpp"
 #include "user_expr.hpp"
@@ -35,6 +40,10 @@ struct mjhmc_functionals {
   uint64_t ring_gen = 0;        // counts the (re-)allocations of the derived ring
   int chunks = 0, cw = 1, log_cw = 0;
   bool wide = false;
+  // the energy observables: no module; E and dE/dX of ONE slot, in the layout and types the energy family writes
+  bool energy = false;
+  void* eo_G = nullptr;         // [Npad][pitch] float64 (float64 state) or float32
+  void* eo_E = nullptr;         // [Npad] of the same type
   size_t slot_bytes() const { return (size_t)s->Npad * pitchK * sizeof(double); }
 };
 
@@ -145,10 +154,62 @@ void functionals_free(mjhmc_functionals* f) {
   chainstats_free_owned(s, f);
   histogram_free_owned(s, f);
   pairhist_free_owned(s, f);
-  for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring})
+  for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring, f->eo_G, f->eo_E})
     if (p) (void)hipFree(p);
   if (f->module) (void)hipModuleUnload(f->module);
   delete f;
+}
+
+// the three values of slots [x_slot0, x_slot0 + n): per slot the evaluation launches of the energy family (one for the
+// elementwise, expression, ProductOfT float32-state and SparseImageCode kernels; narrow + force + widen passes on the
+// float64-state ProductOfT path) and ONE launch of energy_observables_kernel, all on the sampler's stream; the scratch is
+// reused slot after slot in stream order.  One flag read-back (one synchronisation) for the block.
+const char* const kEnergyObsNames[3] = {"E", "grad_sq", "virial"};
+
+// one slot: the evaluation into the scratch (eval), the reduction of slot and scratch into the derived slot (reduce)
+int energy_slot(mjhmc_functionals* f, int x_slot, int out_slot, bool eval, bool reduce) {
+  mjhmc_sampler* s = f->s;
+  const char* X = (const char*)s->ring + (size_t)x_slot * mat_bytes(s);
+  if (eval) TRY(sampler_eval_rows(s, X, f->eo_G, f->eo_E));
+  if (!reduce) return 0;
+  mjhmc::EnergyObsArgs a;
+  a.X = X;
+  a.G = f->eo_G;
+  a.E = f->eo_E;
+  a.dst = f->ring + (size_t)out_slot * s->Npad * f->pitchK;
+  a.N = s->N;
+  a.D = s->D;
+  a.pitch = s->sh.pitch;
+  a.chunks = f->chunks;
+  a.cw = f->cw;
+  a.log_cw = f->log_cw;
+  a.bad = f->bad;
+  if (!mjhmc::energy_observables_launch(a, s->dtype, s->dtype != MJHMC_F64, f->wide, s->stream))
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "no energy-observables kernel for this state type");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int energy_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out_slot0) {
+  mjhmc_sampler* s = f->s;
+  const int64_t rows_per_block = f->wide ? 4 : (int64_t)mjhmc::kFnInFlight * (256 >> f->log_cw);
+  if ((s->N + rows_per_block - 1) / rows_per_block > 0x7FFFFFFFll)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "too many particles for one launch of the energy-observables pass");
+  for (int t = 0; t < n; ++t) TRY(energy_slot(f, x_slot0 + t, out_slot0 + t, true, true));
+  int bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, f->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (bad) {
+    HIPCHK(hipMemsetAsync(f->bad, 0, sizeof(int), s->stream));
+    int k = 0;
+    while (!((bad >> k) & 1)) ++k;
+    return mjhmc_fail(MJHMC_ERR_NONFINITE, "value " + std::to_string(k) + " (" + kEnergyObsNames[k] +
+                                               ") of the energy observables is not finite for a state in slots [" +
+                                               std::to_string(x_slot0) + ", " + std::to_string(x_slot0 + n) +
+                                               "): do not accumulate derived slots [" + std::to_string(out_slot0) + ", " +
+                                               std::to_string(out_slot0 + n) + ")");
+  }
+  return 0;
 }
 
 }  // namespace
@@ -243,6 +304,48 @@ int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* va
   return 0;
 }
 
+int mjhmc_functionals_create_energy(mjhmc_sampler* s, mjhmc_functionals** out) {
+  if (!s || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (s->en->is_host())
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED,
+                      "a host-evaluated energy has no device evaluation: the caller's callables are the only evaluation of E "
+                      "and dE/dX, so the energy observables of its states are the caller's to form");
+  if (!s->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  const int vec = s->dtype == MJHMC_F64 ? 2 : (s->dtype == MJHMC_F32 ? 4 : 8);
+  if (s->sh.esize * vec != 16 || s->sh.pitch % vec != 0)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
+  Shape shK;
+  TRY(pick_shape(mjhmc::kEnergyObsValues, MJHMC_F64, &shK));
+  if (shK.pitch != mjhmc::kEnergyObsPitch) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "unexpected row pitch of the derived ring");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  mjhmc_functionals* f = new mjhmc_functionals();
+  f->s = s;
+  f->energy = true;
+  f->K = mjhmc::kEnergyObsValues;
+  f->pitchK = shK.pitch;
+  f->src_gen = s->ring_gen;
+  row_geometry(s->sh.pitch, vec, &f->chunks, &f->cw, &f->log_cw, &f->wide);
+  // dE/dX has the state's row pitch in every family (SparseImageCode: [Npad][ndims] float32, pitch == ndims) and is
+  // float64 exactly where the state is; E is a scalar of the same type per row.  Rows p >= N: zero, and never read.
+  const size_t gsize = s->dtype == MJHMC_F64 ? 8 : 4;
+  const size_t gbytes = (size_t)s->Npad * s->sh.pitch * gsize, ebytes = (size_t)s->Npad * gsize;
+  hipError_t e = hipMalloc(&f->eo_G, gbytes);
+  if (e == hipSuccess) e = hipMalloc(&f->eo_E, ebytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&f->bad, sizeof(int));
+  if (e == hipSuccess) e = hipMemsetAsync(f->eo_G, 0, gbytes, s->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(f->eo_E, 0, ebytes, s->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(f->bad, 0, sizeof(int), s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e != hipSuccess) {
+    functionals_free(f);
+    (void)hipGetLastError();
+    return mjhmc_fail(MJHMC_ERR_HIP, std::string("energy observables: ") + hipGetErrorString(e));
+  }
+  s->functionals.push_back(f);
+  *out = f;
+  return 0;
+}
+
 int mjhmc_functionals_destroy(mjhmc_functionals* f) {
   if (!f) return 0;
   mjhmc_sampler* s = f->s;
@@ -302,6 +405,7 @@ int mjhmc_functionals_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out
     return mjhmc_fail(MJHMC_ERR_INVALID, "derived slots [" + std::to_string(out_slot0) + ", " + std::to_string((int64_t)out_slot0 + n) +
                                              ") are outside the derived ring of " + std::to_string(f->ring_slots));
   HIPCHK(hipSetDevice(s->ctx->device));
+  if (f->energy) return energy_evaluate(f, x_slot0, n, out_slot0);
   mjhmc::FunctionalsArgs a;
   a.src = (const char*)s->ring + (size_t)x_slot0 * mat_bytes(s);
   a.dst = f->ring + (size_t)out_slot0 * s->Npad * f->pitchK;
@@ -351,5 +455,23 @@ int mjhmc_functionals_read(mjhmc_functionals* f, int slot0, int n, double* host_
   }
   return 0;
 }
+
+#ifdef MJHMC_TEST_HOOKS
+// test build only (tools/energy_observables_bench.py): ONE half of the energy observables' work on slots [x_slot0, x_slot0
+// + n), so that the two can be timed apart -- part 0 the evaluation launches into the scratch, part 1 the reduction kernel
+// on the slot and whatever the scratch holds; no flag read-back, synchronised at the end
+int mjhmc_test_energy_observables_part(mjhmc_functionals* f, int x_slot0, int n, int out_slot0, int part) {
+  if (!f || !f->energy || !f->ring || n < 1 || x_slot0 < 0 || out_slot0 < 0 || (part != 0 && part != 1))
+    return mjhmc_fail(MJHMC_ERR_INVALID, "bad argument");
+  mjhmc_sampler* s = f->s;
+  if (f->src_gen != s->ring_gen || (int64_t)x_slot0 + n > s->ring_slots || (int64_t)out_slot0 + n > f->ring_slots)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  for (int t = 0; t < n; ++t) TRY(energy_slot(f, x_slot0 + t, out_slot0 + t, part == 0, part == 1));
+  HIPCHK(hipMemsetAsync(f->bad, 0, sizeof(int), s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return 0;
+}
+#endif
 
 }  // extern "C"

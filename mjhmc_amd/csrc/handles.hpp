@@ -226,6 +226,9 @@ int round_rows32(mjhmc_sampler* s, void* rows);   // float64 rows -> float32 val
 int wide_leapfrog(mjhmc_sampler* w, const double* X, const double* V, double* Xo, double* Vo, double* G, double* EX,
                   double* EV, double eps, int n_steps);
 
+// api.hip: E and dE/dX of a state matrix through the sampler's own evaluation kernels (no momentum, no counters)
+int sampler_eval_rows(mjhmc_sampler* s, const void* X, void* Gout, void* Eout);
+
 // lanes-per-particle / elements-per-lane selection of the elementwise kernels for ndims = D
 int pick_shape(int D, int dtype, Shape* out);
 // device staging buffer of at least `elems` float64 (host layout side of every re-tiling)

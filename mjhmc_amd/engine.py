@@ -435,6 +435,12 @@ class DeviceSampler(object):
         the device into a derived ring that the estimators read (mjhmc_functionals_*).  The ring must exist (ring_alloc)."""
         return DeviceFunctionals(self, values, stats, params)
 
+    def energy_observables(self):
+        """DeviceFunctionals whose K = 3 values of every recorded state are [E, grad_sq, virial]: the potential energy as
+        this sampler's evaluation kernel returns it, |dE/dX|^2 and x . dE/dX of the same evaluation
+        (mjhmc_functionals_create_energy).  The ring must exist (ring_alloc); a host-evaluated energy is refused."""
+        return DeviceFunctionals.energy(self)
+
     def time_grid(self, n_grid, dt):
         """The jump process of every chain sampled at t_j = j * dt, j < n_grid, into a grid ring of this sampler's slot
         layout (mjhmc_timegrid_*): a fair sample with its time order kept.  The ring must exist (ring_alloc)."""
@@ -758,19 +764,30 @@ class DeviceFunctionals(object):
     (include/mjhmc_hip.h: mjhmc_functionals_create).  ``estimator``, ``chain_stats``, ``histogram`` and ``pair_histogram`` give the sampler's
     accumulators on the derived ring: their ``x_slot0`` counts derived slots, ``w_slot0`` the sampler's dwell slots."""
 
-    def __init__(self, dev, values, stats=(), params=()):
+    def __init__(self, dev, values, stats=(), params=(), _energy=False):
         self.dev, self.lib = dev, dev.lib
         self.nparticles = dev.nparticles
         self.params = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel())
         h = ctypes.c_void_p()
-        check(self.lib.mjhmc_functionals_create(dev.handle, join_exprs(stats), join_exprs(values),
-                                                ptr(self.params) if self.params.size else None, self.params.size,
-                                                _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
+        if _energy:
+            # (its fixed scratch -- dE/dX and E of one slot, at most about two slots' bytes -- is taken here, from the 40 %
+            # of free memory that ring_budget_slots(share=0.6) leaves beside the rings)
+            check(self.lib.mjhmc_functionals_create_energy(dev.handle, ctypes.byref(h)), self.lib)
+        else:
+            check(self.lib.mjhmc_functionals_create(dev.handle, join_exprs(stats), join_exprs(values),
+                                                    ptr(self.params) if self.params.size else None, self.params.size,
+                                                    _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
         self.handle = h
         k, b = ctypes.c_int(), ctypes.c_uint64()
         check(self.lib.mjhmc_functionals_info(h, ctypes.byref(k), ctypes.byref(b)), self.lib)
         self.n_values, self.slot_bytes = int(k.value), int(b.value)
         self.ring_slots = 0
+
+    @classmethod
+    def energy(cls, dev):
+        """the energy observables [E, grad_sq, virial] of ``dev``'s recorded states (mjhmc_functionals_create_energy): the
+        same handle family, filled by the sampler's own evaluation kernels instead of compiled expressions"""
+        return cls(dev, (), _energy=True)
 
     def ring_alloc(self, n_slots):
         """at least ``n_slots`` derived slots; a ring that grows is a new ring (handles created on the old one refuse)"""

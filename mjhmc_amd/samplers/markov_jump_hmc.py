@@ -395,6 +395,43 @@ class Functionals(object):
         return (int(nparticles) + 63) // 64 * 64 * ((self.n_values + 1) // 2 * 2) * 8
 
 
+class EnergyObservables(object):
+    """What ``HMCBase.energy_observables()`` returns: the description of the K = 3 energy observables of a recorded state,
+        E = the potential energy,   grad_sq = sum_d (dE/dx_d)^2,   virial = sum_d x_d dE/dx_d
+    -- as the sampler's own device evaluation of the stored state gives them (csrc/energy_observables.hpp).  It stands
+    where a ``Functionals`` stands: pass it as ``of=`` to ``expectations()``, ``diagnostics()``, ``marginals()`` or
+    ``joint_marginals()``, whose results then have these 3 "dimensions" (``names``)."""
+
+    n_values = 3
+    names = ['E', 'grad_sq', 'virial']
+
+    def slot_bytes(self, nparticles):
+        """bytes of one slot of the derived ring: rows padded to 64, [E, grad_sq, virial, 0.0] float64"""
+        return (int(nparticles) + 63) // 64 * 64 * 4 * 8
+
+
+class Temperature(object):
+    """What ``HMCBase.temperature()`` returns: the virial thermometer of a run, from the ``Diagnostics`` of its energy
+    observables (value 0 ``E``, 1 ``grad_sq``, 2 ``virial``):
+
+      T = mean[virial] / ndims                              1 for chains that keep exp(-E)
+      stderr = sqrt(var_plus[virial] / ess[virial]) / ndims    the standard error of T (multi-chain ESS)
+      z = (T - 1) / stderr
+
+    and ``mean_energy``, ``mean_grad_sq``, ``rhat_energy`` (the R-hat of E: the ``lp__`` check), ``ndims`` and the
+    ``diagnostics`` object itself."""
+
+    def __init__(self, diagnostics, ndims):
+        self.diagnostics = d = diagnostics
+        self.ndims = ndims = int(ndims)
+        self.T = d.mean[2] / ndims
+        self.stderr = np.sqrt(d.var_plus[2] / d.ess[2]) / ndims
+        self.z = (self.T - 1) / self.stderr
+        self.mean_energy = d.mean[0]
+        self.mean_grad_sq = d.mean[1]
+        self.rhat_energy = d.rhat[0]
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -729,9 +766,46 @@ class HMCBase(object):
             raise ValueError('functionals: %s' % (msg.decode() if msg else '?'))
         return F
 
+    def energy_observables(self):
+        """The energy observables [E, grad_sq, virial] for ``expectations / diagnostics / marginals / joint_marginals
+        (..., of=EO)``: the potential energy of every recorded state, |dE/dX|^2 and x . dE/dX, evaluated on the device by
+        the sampler's own energy kernels (one gradient per recorded state, against num_leapfrog_steps per iteration) --
+        what ``functionals()`` cannot state for a coupled energy.  The run is that of ``of=None``, bit for bit, and these
+        evaluations are NOT counted in ``distribution.E_count`` / ``dEdX_count``: those price the chain and feed
+        ``ess_per_grad``; the observable is measurement, not sampling.  Returns an ``EnergyObservables``.  An energy given
+        as opaque callables has no device evaluation: ValueError, before anything runs."""
+        if self.distribution.device_energy()[0] == _lib.E_HOST:
+            raise ValueError('energy_observables: the energy is a pair of opaque Python callables, which are its only '
+                             'evaluation -- there is no device evaluation of E and dE/dX to record (sample(preserve_order=True) '
+                             'and the callables give them on the host)')
+        return EnergyObservables()
+
+    def temperature(self, n_iter, split=True, block=None):
+        """The virial thermometer: is this chain sampling exp(-E) at all?  Integration by parts gives, for every target
+        density p = exp(-E) / Z with p(x) x -> 0 at infinity,
+
+            E_p[x . dE/dX] = ndims
+
+        so ``T = mean[virial] / ndims`` is 1 for chains that keep the law, above 1 for chains that run hot and below for
+        cold ones.  Runs ``diagnostics(n_iter, split, block, of=self.energy_observables())`` -- the same run, counters and
+        weights -- and returns a ``Temperature``: ``T``, its standard error ``stderr = sqrt(var_plus / ess) / ndims`` from
+        the multi-chain ESS of the virial, ``z = (T - 1) / stderr``, ``mean_energy``, ``mean_grad_sq``, ``rhat_energy``
+        and the ``diagnostics``.  ``T`` is the POOLED statement "all chains together keep the law" (the plain average of
+        the chain means): it says nothing about a single chain, and chains that err in opposite directions can cancel --
+        ``rhat_energy`` is the per-chain check.  The condition holds for the Gaussians, the funnels, the mixtures,
+        ProductOfT and the linear models here.  It does NOT hold for SparseImageCode with the Cauchy prior at its
+        lambda = 0.01: in the n_coeffs - img_size directions the dictionary does not see, p ~ (1 + a^2)^-lambda is not
+        integrable (it would need 2 lambda > 1), each such coordinate contributes at most 2 lambda to the virial instead
+        of 1, and the thermometer reads about img_size / n_coeffs (0.26 measured at 256 / 1024) on a correct chain: there
+        T compares chains with each other (float32 against bfloat16 state), not with 1."""
+        return Temperature(self.diagnostics(n_iter, split=split, block=block, of=self.energy_observables()), self.ndims)
+
     def _open_functionals(self, of, n_slots):
         """the device side of ``of`` on this sampler's ring (which must have its final size), with a derived ring"""
-        fn = self._dev.functionals(of.values, of.stats, of.params)
+        if isinstance(of, EnergyObservables):
+            fn = self._dev.energy_observables()
+        else:
+            fn = self._dev.functionals(of.values, of.stats, of.params)
         try:
             fn.ring_alloc(n_slots)
         except Exception:
@@ -757,9 +831,10 @@ class HMCBase(object):
         reading that block twice.  The returned moments are about the true mean whatever the shift.  Sharded samplers
         sum over ranks, use rank 0's shift and the smallest ``block`` of all ranks.
 
-        ``of``: a ``Functionals`` (``functionals()``).  The run is exactly that of ``of=None``; every block is evaluated
+        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``).  The run is exactly that of ``of=None``; every block is evaluated
         into a derived ring on the device (csrc/functionals.hip) and the moments are those of the K functional values:
-        ``shift`` has K entries and the result K "dimensions"."""
+        ``shift`` has K entries and the result K "dimensions".  With an ``EnergyObservables`` the moments are accumulated
+        slot by slot, so that under a given ``shift`` the sums W, S1, S2 (and C) do not depend on ``block``."""
         n_iter = int(n_iter)
         if n_iter < 1:
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
@@ -781,16 +856,25 @@ class HMCBase(object):
             if shift is not None:
                 shift = self._checked_shift(shift, of)
                 est.set_shift(shift)
+            def accumulate(k):
+                if isinstance(of, EnergyObservables):
+                    # slot by slot, as the block was evaluated: the moment pass adds a call's sum to its running totals, so
+                    # one call per slot makes W, S1 and S2 independent of how the run is cut into blocks, bit for bit
+                    for j in range(k):
+                        est.accumulate(j, 1, w_slot0=1 + j if lead else -1)
+                else:
+                    est.accumulate(0, k, w_slot0=1 if lead else -1)
+
             for _, k in self._ring_blocks([n_iter], block):
                 if fn is not None:
                     fn.evaluate(0, k, 0)
-                est.accumulate(0, k, w_slot0=1 if lead else -1)
+                accumulate(k)
                 if shift is None:                          # the first block's own mean, then the same block again about it
                     W, S1 = self._reduce_sums(est.read())[:2]
                     shift = S1 / W
                     est.reset()
                     est.set_shift(shift)
-                    est.accumulate(0, k, w_slot0=1 if lead else -1)
+                    accumulate(k)
             self._publish()
             if lead:
                 self._read_dwell()
@@ -849,7 +933,7 @@ class HMCBase(object):
         ranks.  The per-chain sums take device memory (parts x (2 x row pitch + 1) x padded particles x 8 bytes): they
         are created before the block size is taken from what the device has left.
 
-        ``of``: a ``Functionals`` (``functionals()``): the same run, the diagnostics of the K functional values (every
+        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``): the same run, the diagnostics of the K functional values (every
         block is evaluated into a derived ring first; ``shift`` has K entries)."""
         n_iter = int(n_iter)
         if split and (n_iter < 4 or n_iter % 2):
@@ -931,7 +1015,7 @@ class HMCBase(object):
         units of 1.  Sharded samplers use rank 0's range and quantum and the smallest ``block`` of all ranks, and add
         their integer tables over ranks.
 
-        ``of``: a ``Functionals`` (``functionals()``): the same run, one histogram per functional value (every block is
+        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``): the same run, one histogram per functional value (every block is
         evaluated into a derived ring first; ``range`` entries are scalars or K-vectors, and the range=None moment pass,
         ``span`` and the quantum rule apply to the values)."""
         n_iter, bins = int(n_iter), int(bins)
@@ -1012,7 +1096,7 @@ class HMCBase(object):
         dimension has one range in every pair it appears in.  Sharded samplers use rank 0's ranges and quantum and the
         smallest ``block`` of all ranks, and add their integer tables over ranks.
 
-        ``of``: a ``Functionals`` (``functionals()``): the same run, ``pairs`` index the K functional values (every block
+        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``): the same run, ``pairs`` index the K functional values (every block
         is evaluated into a derived ring first; ``range`` entries are scalars or K-vectors)."""
         n_iter, bins = int(n_iter), int(bins)
         K = self.ndims if of is None else of.n_values
