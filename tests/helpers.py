@@ -212,6 +212,43 @@ def check_control_iteration(s, o, delta_rel, x_tol, e_rtol, tag='', max_ties=Non
     return int(diff.sum())
 
 
+def group_shape(ndims, dtype='float64'):
+    """Pure-Python restatement of pick_shape (csrc/api.hip) and of launch_jump_t's `full` (csrc/elementwise.hpp) for the
+    elementwise energies: (E, logG, full_row) -- E elements in each of the 2^logG lanes of a particle's group, and whether
+    the row's 16-byte chunks fill the group exactly (the FULLROW instances; an odd ndims still leaves one padding ELEMENT
+    in the last chunk, which only the dim_of masks keep out).  E = 0: more than 64 lanes x 8 chunks, the multi-pass path."""
+    vec = 2 if dtype == 'float64' else 4
+    chunks = (ndims + vec - 1) // vec
+    if chunks <= 1:
+        return vec, 0, chunks == 1
+    per_lane = 4
+    lanes = 1
+    while lanes * per_lane < chunks:
+        lanes *= 2
+    if lanes > 64:
+        per_lane, lanes = 8, 1
+        while lanes * per_lane < chunks:
+            lanes *= 2
+    if lanes > 64:
+        return 0, 0, False
+    return per_lane * vec, lanes.bit_length() - 1, chunks == per_lane * lanes
+
+
+def jump_instance(E, logG, full, fused, mode='mjhmc', block_decide=True):
+    """Restatement of launch_jump_t (csrc/elementwise.hpp) for the group form with the counter RNG: the instance
+    (FULLROW, WPP) of mjhmc_jump_kernel a call takes.  (The float64 funnels and mixture at logG 1 and 2 fuse in row
+    form instead: tests/test_gpu_rows_oracle.py.)"""
+    if mode != 'mjhmc' or not full:
+        return False, 0
+    if fused and block_decide and logG in (5, 6):
+        return True, 5 if logG == 6 else 6
+    if logG == 6:
+        return True, 1
+    if logG == 2:
+        return True, 3
+    return True, 0
+
+
 _HOOKS_CTX = {}
 
 

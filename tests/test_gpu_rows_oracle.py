@@ -40,6 +40,10 @@ def _energy(name, D):
         return Dm.Funnel, dict(scale=3.0), orc.FunnelNeal(3.0)
     if name == 'literal':
         return Dm.Funnel, dict(scale=1.0, literal=True), orc.FunnelLiteral(1.0)
+    if name == 'rough':
+        return Dm.RoughWell, dict(), orc.RoughWell(100, 4)
+    if name == 'coupled':                    # Neal's funnel as hipRTC coupled expressions S[k] (built in _sampler)
+        return Dm.LambdaDistribution, dict(device_params=[3.0, float(D)]), orc.FunnelNeal(3.0)
     sep = {'mm3': 3, 'mm1': 1}[name]
     return Dm.MultimodalGaussian, dict(separation=sep), orc.MultimodalGaussian(D, sep)
 
@@ -47,11 +51,13 @@ def _energy(name, D):
 def _initial_state(name, D, N):
     rs = np.random.RandomState(D * 1009 + N)
     X = rs.randn(D, N)
-    if name == 'neal':                       # the funnel's own law, x0 ~ N(0, 1.5^2)
+    if name in ('neal', 'coupled'):          # the funnel's own law, x0 ~ N(0, 1.5^2)
         X[0] *= 1.5
         X[1:] *= np.exp(X[0] / 2.)
     elif name == 'literal':                  # the literal funnel diverges: start near the origin
         X *= 0.3
+    elif name == 'rough':                    # a few periods of the cosine around the origin
+        X *= 3.0
     else:                                    # the mixture: half of the particles at each mode (+-2 sep on dimension 0)
         sep = {'mm3': 3, 'mm1': 1}[name]
         X *= 0.7
@@ -75,21 +81,33 @@ def _path(name, D, L, fused):
 
 
 def _stats(st):
-    return dict(l=st.l, f=st.f, r=st.r, n_cold=st.n_cold, E=st.E_evals, dEdX=st.dEdX_evals, nonfinite=st.nonfinite,
+    return dict(l=st.l, f=st.f, r=st.r, fl=st.fl, n_cold=st.n_cold, E=st.E_evals, dEdX=st.dEdX_evals, nonfinite=st.nonfinite,
                 L=st.L_used)
 
 
-def _sampler(name, D, N, eps, L, beta, X0, seed=SEED):
-    """the product's MarkovJumpHMC on `name`, recording the IterStats of every attempt (`attempts`) and of every committed
-    iteration (`trace`) on the way"""
-    from mjhmc_amd.samplers.markov_jump_hmc import MarkovJumpHMC
-    base, kw, _ = _energy(name, D)
+def _sampler(name, D, N, eps, L, beta, X0, seed=SEED, cls_name='MarkovJumpHMC', dtype='float64', hooks=False):
+    """the product's sampler `cls_name` (MarkovJumpHMC) on `name`, recording the IterStats of every attempt (`attempts`)
+    and of every committed iteration (`trace`) on the way.  `dtype`: the state type; `hooks`: the energy is bound to the
+    test-hooks library (tests.helpers.hooks_context), the only one that reads the MJHMC_NO_* switches"""
+    from mjhmc_amd.samplers import markov_jump_hmc as M
+    base, kw, en = _energy(name, D)
 
     class Fixed(base):
+        state_dtype = dtype
+
         def init_X(self):
             self.Xinit = X0
 
-    class Recording(MarkovJumpHMC):
+        if hooks:
+            def bind(self, device=0):
+                from mjhmc_amd import engine
+                from tests.helpers import hooks_context
+                if self._dev is None:
+                    kind, params = self.device_energy()
+                    self._dev = engine.DeviceEnergy(hooks_context(device), kind, self.ndims, params)
+                return self._dev
+
+    class Recording(getattr(M, cls_name)):
         def _account(self, st):
             self.attempts.append(_stats(st))
             super(Recording, self)._account(st)
@@ -98,8 +116,15 @@ def _sampler(name, D, N, eps, L, beta, X0, seed=SEED):
             self.trace.append(_stats(st))
             super(Recording, self)._commit(st)
 
-    s = Recording(distribution=Fixed(ndims=D, nbatch=N, **kw), epsilon=eps, beta=beta, num_leapfrog_steps=L, seed=seed,
-                  resample=False)
+    if name == 'coupled':
+        from tests.test_gpu_parity import FUNNEL_EXPR
+        assert dtype == 'float64' and not hooks
+        d = base(energy_func=en.E_val, energy_grad_func=en.dEdX_val, init=X0, name='funnel as expressions',
+                 device_expr=FUNNEL_EXPR, **kw)
+    else:
+        d = Fixed(ndims=D, nbatch=N, **kw)
+    extra = dict(resample=False) if cls_name in ('MarkovJumpHMC', 'ContinuousTimeHMC') else {}
+    s = Recording(distribution=d, epsilon=eps, beta=beta, num_leapfrog_steps=L, seed=seed, **extra)
     s.attempts, s.trace = [], []
     return s
 
@@ -117,11 +142,12 @@ def _columns(N):
     return np.array(sorted(cols))
 
 
-def _oracle(name, D, X0, eps, L, beta, cols):
+def _oracle(name, D, X0, eps, L, beta, cols, cls_name='MarkovJumpHMC', state_rounding=None):
     _, _, en = _energy(name, D)
     ids = np.arange(X0.shape[1]) if cols is None else cols
-    return orc.MarkovJumpHMC(en, X0[:, ids], epsilon=eps, beta=beta, num_leapfrog_steps=L, resample=False,
-                             rng=orc.PhiloxRNG(SEED, ids))
+    extra = dict(resample=False) if cls_name in ('MarkovJumpHMC', 'ContinuousTimeHMC') else {}
+    return getattr(orc, cls_name)(en, X0[:, ids], epsilon=eps, beta=beta, num_leapfrog_steps=L,
+                                  rng=orc.PhiloxRNG(SEED, ids), state_rounding=state_rounding, **extra)
 
 
 def _near(a, b, rtol):
@@ -189,20 +215,24 @@ def _check_after_call(s, o, cols, tag, cmp):
     cmp('dwelling times', s.dwelling_times[sel], o.dwelling_times, tag)
 
 
-def _run_and_compare(name, D, L, N, n_iter, p_r=None, calls=3, fused=True, rtol=RTOL):
+def _run_and_compare(name, D, L, N, n_iter, p_r=None, calls=3, fused=True, rtol=RTOL, eps=None, path=None, hooks=False):
     """`calls` calls of n_iter iterations (fused: sample(n_iter); else n_iter sampling_iteration() calls), each iteration
-    compared with the oracle; returns the largest relative difference met per compared quantity"""
-    eps = _eps(name, L)
+    compared with the oracle; returns the largest relative difference met per compared quantity.  `eps`: the step size
+    (default: _eps); `path`: the launch path for the messages (default: _path, which knows the row range only); `hooks`:
+    the sampler runs on the test-hooks library"""
+    eps = _eps(name, L) if eps is None else eps
     X0 = _initial_state(name, D, N)
-    s = _sampler(name, D, N, eps, L, BETA, X0)
+    s = _sampler(name, D, N, eps, L, BETA, X0, hooks=hooks)
     cols = _columns(N)
     sel = slice(None) if cols is None else cols
     o = _oracle(name, D, X0, eps, L, BETA, cols)
     if p_r is not None:
         s.p_r = o.p_r = p_r
     assert close(s.state.V[:, sel], o.state.V), 'tick-0 momenta'
-    path = _path(name, D, L, fused)
-    if not fused and N >= 16384:
+    explicit_path, path = path, _path(name, D, L, fused)
+    if explicit_path is not None:
+        path = explicit_path
+    elif not fused and N >= 16384:
         path = 'single iteration (row trajectory + jump process)' if 9 <= D <= 32 else 'single iteration (compacted group form)'
     n_cold_expected = N
     cmp = _Compare(rtol)
