@@ -522,6 +522,40 @@ int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo
 int mjhmc_pairhist_create_on(mjhmc_functionals* f, int n_pairs, const int32_t* pairs, int n_bins, const double* lo,
                              const double* hi, double quantum, mjhmc_pairhist** out);
 
+/* Kernel Stein discrepancy of one recorded ensemble against exp(-E), on the device (csrc/stein.hip, csrc/stein.hpp):
+ * the one question the accumulators above leave open -- is the ensemble a sample of the target? -- answered from the
+ * states and dE/dX at the states alone, with no normaliser and no reference sample (Gorham & Mackey 2017).  The base
+ * kernel is the inverse multiquadric with exponent -1/2, k(x,y) = (c^2 + |x-y|^2)^(-1/2); the score is -G, G = dE/dX.
+ * With r2 = sum_d (x_d-y_d)^2, dd = sum_d (Gx_d-Gy_d)(x_d-y_d), gg = sum_d Gx_d*Gy_d, q = c^2 + r2, t = 1/sqrt(q):
+ *     k_p(x,y) = gg*t - t^3*dd + ndims*t^3 - 3*t^5*r2
+ * every sum over d < ndims taken in ascending d from the differences themselves, in float64 (every state and gradient
+ * type widened exactly), every product rounded before its sum; only + - * / sqrt, so the result is IEEE-rounded
+ * throughout.  The exponent is fixed.
+ * A handle belongs to the sampler it was created on (mjhmc_sampler_destroy frees every one still alive, and the handle
+ * is INVALID from then on) and to the sample ring of that moment (a re-allocated ring invalidates it).  It owns one
+ * dE/dX matrix and one E vector in the layout the energy family writes, and one (S, Sd) partial per 64 x 64 tile of
+ * pairs, sized for N at create.
+ * MJHMC_ERR_INVALID: NULL arguments, c not finite or <= 0 (both before the sampler is touched), no sample ring yet;
+ * MJHMC_ERR_UNSUPPORTED: a host-evaluated energy (MJHMC_E_HOST has no device evaluation of dE/dX). */
+typedef struct mjhmc_stein mjhmc_stein;
+int mjhmc_stein_create(mjhmc_sampler* s, double c, mjhmc_stein** out);
+/* The pass on ring slot x_slot, particles p < n_use, weights w_p of dwell-ring slot w_slot (w_slot == -1: unit weights;
+ * the pairing of mjhmc_estimator_accumulate, so a jump sampler takes w_slot = x_slot + 1):
+ *     out[0] = W  = sum_p w_p                        out[2] = S  = sum_{i,j} w_i w_j k_p(x_i, x_j)
+ *     out[1] = W2 = sum_p w_p^2                      out[3] = Sd = sum_i w_i^2 k_p(x_i, x_i)
+ * V = S / W^2 is the V-statistic (>= 0 up to rounding), U = (S - Sd) / (W^2 - W2) the unbiased one (mean zero under the
+ * target).  On the sampler's stream: the sampler's own evaluation kernels on the slot (as the energy observables; not
+ * counted, no sampler state, counter or random stream touched), the pair kernel, the finish kernel, ONE read-back.
+ * Rows p >= n_use are selected out, never multiplied by zero: they may hold anything.  No floating-point atomic; the
+ * order of every addition is a function of (ndims, n_use, state type, pitch) alone, so out[] is bit-identical from run
+ * to run and does not depend on how the run was cut into blocks.
+ * MJHMC_ERR_INVALID: NULL arguments, slots outside the ring, n_use outside [1, N], a ring re-allocated since create.
+ * MJHMC_ERR_NONFINITE: a weight, a state or a gradient of a row p < n_use is not finite (or, all of them finite, a sum
+ * overflows); the message says which, and out[] is left as it was. */
+int mjhmc_stein_evaluate(mjhmc_stein* k, int x_slot, int w_slot, int64_t n_use, double out[4]);
+/* frees the handle's device memory (NULL: nothing) */
+int mjhmc_stein_destroy(mjhmc_stein* k);
+
 /* Fair sample paths on a uniform time grid, kept on the device (csrc/timegrid.hip): the one result the weighted
  * accumulators above cannot give -- a fair sample with its time order kept.  The reference's sample(resample=True)
  * (markov_jump_hmc.py:293-338) pools particles and steps into one weighted draw ("preserve_order has no effect if

@@ -131,6 +131,9 @@ PROTOTYPES = {
     'mjhmc_estimator_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
     'mjhmc_chainstats_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
     'mjhmc_histogram_create_on': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_stein_create': (ctypes.c_int, [_P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_stein_evaluate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    'mjhmc_stein_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_timegrid_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -1066,6 +1066,7 @@ int mjhmc_sampler_destroy(mjhmc_sampler* s) {
   histogram_free_all(s);
   pairhist_free_all(s);
   timegrid_free_all(s);
+  stein_free_all(s);
   void* ptrs[] = {s->flf_list, s->call_block, s->Hpre, s->Hwork, s->cold_list, s->pot64_scratch, s->Hspec[0], s->Hspec[1], s->Hspec_dump, s->Gbuf[0], s->Gbuf[1], s->Xbuf[0], s->Xbuf[1], s->Vbuf[0],  s->Vbuf[1], s->EX[0],     s->EX[1],  s->EV[0],
                   s->EV[1],   s->Hflf[0], s->Hflf[1],  s->dwell,  s->dwell_scratch,  s->trans,
                   s->ring,     s->dwell_ring, s->stage,  s->noise,  s->rexp,

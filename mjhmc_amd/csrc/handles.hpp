@@ -92,6 +92,7 @@ struct mjhmc_histogram;  // weighted marginal histograms over ring blocks (histo
 struct mjhmc_pairhist;   // weighted joint histograms of pairs of dimensions over ring blocks (pairhist.hip)
 struct mjhmc_functionals;  // caller expressions g(x) evaluated into a derived ring (functionals.hip)
 struct mjhmc_timegrid;   // the jump process sampled on a uniform time grid, in a grid ring of its own (timegrid.hip)
+struct mjhmc_stein;      // kernel Stein discrepancy of one recorded ensemble (stein.hip)
 struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (api.hip)
 struct HostTraj;  // proposal workspace of a host-energy sampler (host_energy.hip)
 
@@ -161,6 +162,7 @@ struct mjhmc_sampler {
   std::vector<mjhmc_pairhist*> pairhists;     // pair-histogram accumulators created on this sampler (pairhist.hip); freed with it
   std::vector<mjhmc_functionals*> functionals;   // functionals created on this sampler (functionals.hip); freed with it, BEFORE the four lists above
   std::vector<mjhmc_timegrid*> timegrids;     // time grids created on this sampler (timegrid.hip); freed with it
+  std::vector<mjhmc_stein*> steins;           // Stein-discrepancy handles created on this sampler (stein.hip); freed with it
   double* stage = nullptr;  // device staging, float64 host layout
   size_t stage_elems = 0;
   void* noise = nullptr;    // replay normals, particle-major
@@ -214,6 +216,9 @@ void functionals_free_all(mjhmc_sampler* s);
 
 // timegrid.hip
 void timegrid_free_all(mjhmc_sampler* s);
+
+// stein.hip
+void stein_free_all(mjhmc_sampler* s);
 
 // host_energy.hip
 void host_traj_free(mjhmc_sampler* s);

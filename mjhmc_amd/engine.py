@@ -446,6 +446,12 @@ class DeviceSampler(object):
         layout (mjhmc_timegrid_*): a fair sample with its time order kept.  The ring must exist (ring_alloc)."""
         return DeviceTimeGrid(self, n_grid, dt)
 
+    def stein(self, c):
+        """The kernel Stein discrepancy of one recorded ensemble against exp(-E) (mjhmc_stein_*): IMQ base kernel
+        (c^2 + |x-y|^2)^(-1/2), pair pass on the device.  The ring must exist (ring_alloc); a host-evaluated energy is
+        refused."""
+        return DeviceStein(self, c)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -689,6 +695,38 @@ class DeviceTimeGrid(object):
     def close(self):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
             self.lib.mjhmc_timegrid_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceStein(object):
+    """``evaluate`` returns (W, W2, S, Sd) of one ring slot: W = sum w, W2 = sum w^2, S = sum_ij w_i w_j k_p(x_i, x_j), Sd its
+    diagonal, k_p the Stein kernel of the IMQ base kernel with scale ``c`` (include/mjhmc_hip.h: mjhmc_stein_evaluate).
+    Float64 throughout, no floating-point atomics: bit-identical from run to run."""
+
+    def __init__(self, dev, c):
+        self.dev, self.lib, self.c = dev, dev.lib, float(c)
+        h = ctypes.c_void_p()
+        check_args(self.lib.mjhmc_stein_create(dev.handle, self.c, ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def evaluate(self, x_slot, w_slot=-1, n_use=None):
+        """The first ``n_use`` particles (default: all) of ring slot ``x_slot`` with the weights of dwell slot ``w_slot`` (-1:
+        unit weights; a jump sampler takes w_slot = x_slot + 1).  A weight, state or gradient that is not finite raises
+        EngineError (status -5) with a message that says which."""
+        n_use = self.dev.nparticles if n_use is None else int(n_use)
+        out = np.empty(4, dtype=np.float64)
+        check_args(self.lib.mjhmc_stein_evaluate(self.handle, int(x_slot), int(w_slot), n_use, ptr(out)), self.lib)
+        return tuple(float(v) for v in out)
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
+            self.lib.mjhmc_stein_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

@@ -432,6 +432,36 @@ class Temperature(object):
         self.rhat_energy = d.rhat[0]
 
 
+class SteinDiscrepancy(object):
+    """What ``HMCBase.stein_discrepancy()`` returns: the kernel Stein discrepancy of the ensemble against exp(-E) at every
+    evaluated recorded state, from the four device sums of each (include/mjhmc_hip.h: mjhmc_stein_evaluate).  Arrays of
+    one entry per evaluated state:
+
+      ``iterations``  index of the recorded state within the run (0, every, 2 every, ...)
+      ``W, W2, S, Sd``  sum w, sum w^2, sum_ij w_i w_j k_p(x_i, x_j) and its diagonal sum_i w_i^2 k_p(x_i, x_i)
+      ``v = S / W^2``   the V-statistic (>= 0 up to rounding);  ``ksd = sqrt(max(v, 0))``
+      ``u = (S - Sd) / (W^2 - W2)``  the U-statistic: unbiased, mean zero under the target; NaN where W^2 == W2 (one particle)
+
+    and ``n_particles``, ``c`` (the IMQ scale) and ``mean_u`` (the mean of ``u`` over the evaluated states, NaN-aware)."""
+
+    def __init__(self, iterations, W, W2, S, Sd, n_particles, c):
+        self.iterations = np.asarray(iterations, dtype=np.int64).reshape(-1)
+        self.W, self.W2, self.S, self.Sd = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (W, W2, S, Sd))
+        self.n_particles, self.c = int(n_particles), float(c)
+        WW = self.W * self.W
+        self.v = self.S / WW
+        self.ksd = np.sqrt(np.maximum(self.v, 0.0))
+        den = WW - self.W2
+        ok = den != 0
+        self.u = np.full(self.W.shape, np.nan)
+        self.u[ok] = (self.S[ok] - self.Sd[ok]) / den[ok]
+
+    @property
+    def mean_u(self):
+        ok = ~np.isnan(self.u)
+        return float(np.mean(self.u[ok])) if ok.any() else float('nan')
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -799,6 +829,68 @@ class HMCBase(object):
         of 1, and the thermometer reads about img_size / n_coeffs (0.26 measured at 256 / 1024) on a correct chain: there
         T compares chains with each other (float32 against bfloat16 state), not with 1."""
         return Temperature(self.diagnostics(n_iter, split=split, block=block, of=self.energy_observables()), self.ndims)
+
+    def stein_discrepancy(self, n_iter, every=1, particles=None, c=None, block=None):
+        """Is the ensemble a sample of exp(-E)?  The kernel Stein discrepancy of the particles at every ``every``-th of
+        ``n_iter`` recorded states, against the sampler's own target, on the device (csrc/stein.hpp): the supremum of the
+        Stein identity over the unit ball of the IMQ kernel (c^2 + |x-y|^2)^(-1/2) (Gorham & Mackey 2017).  It needs the
+        states and dE/dX at the states only -- no normaliser, no reference sample, no closed-form moments -- and with this
+        kernel it vanishes in the limit for the target alone.  Returns a ``SteinDiscrepancy``: a burn-in curve
+        (``ksd`` / ``u`` against ``iterations``) and a scalar (``mean_u``) that compares samplers on one target.
+
+        The run is that of ``expectations(n_iter)``: the same iterations in blocks of ``block`` states, the same weights
+        (holding times for the jump samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the same
+        counters, ``dwelling_times`` and final state, bit for bit.  The gradient evaluations of the pass are NOT counted in
+        ``E_count`` / ``dEdX_count`` (measurement, not sampling).  The results do not depend on ``block``.
+
+        ``particles``: the pass is quadratic, so it takes the first ``particles`` particles (default min(nbatch, 8192));
+        particle columns are exchangeable, so a prefix is a fair subsample.  ``c``: the kernel scale, default sqrt(ndims)
+        (c = 1 loses a scale error at ndims = 512; pass c = 1.0 for the literature's default).  ValueError, before anything
+        runs: n_iter < 1, every < 1, particles outside [1, nbatch], c not finite or <= 0, an energy given as opaque
+        callables (no device evaluation of dE/dX), a sharded sampler (pairs across ranks are not formed)."""
+        n_iter, every = int(n_iter), int(every)
+        if n_iter < 1:
+            raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        if every < 1:
+            raise ValueError('every must be >= 1, got %d' % every)
+        particles = min(int(self.nbatch), 8192) if particles is None else int(particles)
+        if particles < 1 or particles > int(self.nbatch):
+            raise ValueError('particles must be in [1, nbatch = %d], got %d' % (int(self.nbatch), particles))
+        c = float(np.sqrt(self.ndims)) if c is None else float(c)
+        if not np.isfinite(c) or c <= 0:
+            raise ValueError('the kernel scale c must be finite and > 0, got %r' % c)
+        if self.distribution.device_energy()[0] == _lib.E_HOST:
+            raise ValueError('stein_discrepancy: the energy is a pair of opaque Python callables, which are its only '
+                             'evaluation -- there is no device evaluation of dE/dX to form the Stein kernel from')
+        if self._comm is not None:
+            raise ValueError('stein_discrepancy: a sharded sampler (comm set) is not supported -- pairs of particles '
+                             'across ranks are not formed')
+        lead = 1 if self._dwell_weighted else 0
+        if block is None:
+            # the handle's dE/dX matrix is at most two slots (float32 gradient of a bfloat16 state); the partials are small
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False,
+                                                reserve_bytes=2 * self._dev.ring_slot_bytes()) - lead
+        block = max(1, min(int(block), n_iter))
+        self._dev.ring_alloc(block + lead)
+        st = None
+        its, rows = [], []
+        try:
+            st = self._dev.stein(c)
+            done = 0
+            for _, k in self._ring_blocks([n_iter], block):
+                for j in range(k):
+                    if (done + j) % every == 0:
+                        its.append(done + j)
+                        rows.append(st.evaluate(j, 1 + j if lead else -1, particles))
+                done += k
+            self._publish()
+            if lead:
+                self._read_dwell()
+        finally:
+            if st is not None:
+                st.close()
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+        return SteinDiscrepancy(its, rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], particles, c)
 
     def _open_functionals(self, of, n_slots):
         """the device side of ``of`` on this sampler's ring (which must have its final size), with a derived ring"""
