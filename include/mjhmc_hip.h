@@ -499,6 +499,27 @@ int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* va
  * functionals.  MJHMC_ERR_INVALID: NULL arguments, no sample ring yet; MJHMC_ERR_UNSUPPORTED: a host-evaluated energy
  * (MJHMC_E_HOST: the caller's callables are its only evaluation). */
 int mjhmc_functionals_create_energy(mjhmc_sampler* s, mjhmc_functionals** out);
+/* Linear projections: a functionals whose K values of every recorded state are
+ *     u[k] = b[k] + sum_{d < ndims} A[k][d] * x[d]        g[k] = link(u[k], k; p)        1 <= K <= 512
+ * -- R-hat and ESS along principal axes, the read-outs of a linear model, sliced marginals: directions that are not
+ * coordinate axes, up to 512 of them at once, which the J <= 8 lane sums of mjhmc_functionals_create cannot state.  A is
+ * (K, ndims) float64 in C order, b has K entries or is NULL (zeros).  link_expr is NULL (the identity: the kernel is in the
+ * library and hipRTC is not touched) or ONE C expression of `u` (float64), `k` (the value's index, int) and `p[m]` (the
+ * nparams float64 parameters), e.g. "1.0 / (1.0 + exp(-u))"; it is compiled with hipRTC around csrc/projections.hpp with
+ * the library's own flags.  The handle keeps device copies of A, b and p, freed with it and by mjhmc_sampler_destroy.
+ * Arithmetic (csrc/projections.hpp): an accumulator starts at b[k] and adds the products in ascending d, each product
+ * rounded before its sum (no contraction), no value split over lanes and no float atomics -- a value is a function of
+ * (A, b, x) alone, bit-identical for every block, state type (rows are widened exactly) and tile, and equal to the NumPy
+ * loop `u = b.copy(); for d: u = u + A[:, d, None] * X[d]` bit for bit.  _info, _ring_alloc, _evaluate, _read, _destroy
+ * and every _create_on work as on any functionals; a value that is not finite is reported by _evaluate, the message naming
+ * the lowest such value index.  Only the ring is read: host-evaluated energies are accepted.
+ * MJHMC_ERR_INVALID with a message: K outside [1, 512], NULL s, A or out, an entry of A, b or p that is not finite (the
+ * first is named), no sample ring yet, a link that does not compile (the hipRTC log is the message). */
+int mjhmc_functionals_create_linear(mjhmc_sampler* s, int n_values, const double* A, const double* b, const char* link_expr,
+                                    const double* params, size_t nparams, const char* include_dir, mjhmc_functionals** out);
+/* the checks of mjhmc_functionals_create_linear that need no device: the range of K, and the compile of link_expr (NULL:
+ * nothing to compile) for float64 rows; keeps nothing */
+int mjhmc_projections_check(int n_values, const char* link_expr, const char* include_dir);
 int mjhmc_functionals_destroy(mjhmc_functionals* f);
 /* K, and the bytes of one slot of the derived ring (Npad * pitchK * 8) */
 int mjhmc_functionals_info(mjhmc_functionals* f, int* n_values, uint64_t* slot_bytes);

@@ -123,6 +123,9 @@ PROTOTYPES = {
     'mjhmc_functionals_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, _P, ctypes.c_size_t, ctypes.c_char_p,
                                                 ctypes.POINTER(_P)]),
     'mjhmc_functionals_create_energy': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
+    'mjhmc_functionals_create_linear': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_char_p, _P, ctypes.c_size_t,
+                                                       ctypes.c_char_p, ctypes.POINTER(_P)]),
+    'mjhmc_projections_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_functionals_destroy': (ctypes.c_int, [_P]),
     'mjhmc_functionals_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
     'mjhmc_functionals_ring_alloc': (ctypes.c_int, [_P, ctypes.c_int]),

@@ -11,6 +11,10 @@
 // A second kind of handle (mjhmc_functionals_create_energy) fills the same derived ring with the ENERGY OBSERVABLES
 // [E, grad_sq, virial] of every recorded state: no expressions and no hipRTC -- per slot the sampler's own evaluation
 // (api.hip: sampler_eval_rows) into scratch of the handle, then energy_observables_kernel (energy_observables.hpp).
+//
+// A third kind (mjhmc_functionals_create_linear) fills it with LINEAR PROJECTIONS g = link(A x + b) of every recorded state:
+// K <= 512 caller-chosen directions through the small-GEMM kernel of projections.hpp -- the library's own instantiation for
+// the identity link, a hipRTC build around the caller's link expression otherwise (projections.hip).
 #include "functionals.hpp"
 
 #include <algorithm>
@@ -24,6 +28,7 @@
 #include "../../include/mjhmc_hip.h"
 #include "energy_observables.hpp"
 #include "handles.hpp"
+#include "projections.hpp"
 #include "ring_source.hpp"
 #include "user_expr.hpp"
 
@@ -44,6 +49,11 @@ struct mjhmc_functionals {
   bool energy = false;
   void* eo_G = nullptr;         // [Npad][pitch] float64 (float64 state) or float32
   void* eo_E = nullptr;         // [Npad] of the same type
+  // the linear projections: device copies of A (transposed, zero-padded) and b; module / fn only with a link expression
+  bool linear = false;
+  double* lin_At = nullptr;     // [Dpad][Kpad], At[d][k] = A[k][d]
+  double* lin_b = nullptr;      // [Kpad]
+  int lin_Kpad = 0;
   size_t slot_bytes() const { return (size_t)s->Npad * pitchK * sizeof(double); }
 };
 
@@ -154,7 +164,7 @@ void functionals_free(mjhmc_functionals* f) {
   chainstats_free_owned(s, f);
   histogram_free_owned(s, f);
   pairhist_free_owned(s, f);
-  for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring, f->eo_G, f->eo_E})
+  for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring, f->eo_G, f->eo_E, (void*)f->lin_At, (void*)f->lin_b})
     if (p) (void)hipFree(p);
   if (f->module) (void)hipModuleUnload(f->module);
   delete f;
@@ -210,6 +220,59 @@ int energy_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out_slot0) {
                                                std::to_string(out_slot0 + n) + ")");
   }
   return 0;
+}
+
+// the projections of slots [x_slot0, x_slot0 + n): ONE launch of projections_kernel on the sampler's stream (blockIdx.y
+// strides over the slots) and one flag read-back
+int linear_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out_slot0) {
+  mjhmc_sampler* s = f->s;
+  mjhmc::ProjArgs a;
+  a.src = (const char*)s->ring + (size_t)x_slot0 * mat_bytes(s);
+  a.dst = f->ring + (size_t)out_slot0 * s->Npad * f->pitchK;
+  a.At = f->lin_At;
+  a.b = f->lin_b;
+  a.Npad = s->Npad;
+  a.N = s->N;
+  a.n = n;
+  a.D = s->D;
+  a.chunks = f->chunks;
+  a.K = f->K;
+  a.pitchK = f->pitchK;
+  a.Kpad = f->lin_Kpad;
+  a.bad = f->bad;
+  const int64_t gx = (s->N + mjhmc::kProjRows - 1) / mjhmc::kProjRows;
+  if (gx > 0x7FFFFFFFll) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "too many particles for one launch of the projections pass");
+  if (f->fn) {
+    struct {
+      const double* p;
+    } link{f->dparams};
+    void* params[] = {&a, &link};
+    HIPCHK(hipModuleLaunchKernel(f->fn, (unsigned)gx, (unsigned)std::min(n, 1024), 1, 256, 1, 1, 0, s->stream, params, nullptr));
+  } else {
+    if (!mjhmc::projections_launch(a, s->dtype, s->stream))
+      return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "no projections kernel for this state type");
+    HIPCHK(hipGetLastError());
+  }
+  int bad = mjhmc::kProjNoBad;
+  HIPCHK(hipMemcpyAsync(&bad, f->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (bad != mjhmc::kProjNoBad) {
+    const int no_bad = mjhmc::kProjNoBad;
+    HIPCHK(hipMemcpyAsync(f->bad, &no_bad, sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return mjhmc_fail(MJHMC_ERR_NONFINITE, "value " + std::to_string(bad) + " of the projections is not finite for a state in slots [" +
+                                               std::to_string(x_slot0) + ", " + std::to_string(x_slot0 + n) +
+                                               "): do not accumulate derived slots [" + std::to_string(out_slot0) + ", " +
+                                               std::to_string(out_slot0 + n) + ")");
+  }
+  return 0;
+}
+
+// the first entry of v[0 .. n) that is not finite, or -1
+int64_t first_nonfinite(const double* v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return (int64_t)i;
+  return -1;
 }
 
 }  // namespace
@@ -346,6 +409,77 @@ int mjhmc_functionals_create_energy(mjhmc_sampler* s, mjhmc_functionals** out) {
   return 0;
 }
 
+int mjhmc_functionals_create_linear(mjhmc_sampler* s, int n_values, const double* A, const double* b, const char* link_expr,
+                                    const double* params, size_t nparams, const char* include_dir, mjhmc_functionals** out) {
+  if (!s || !A || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (link_expr && !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (nparams && !params) return mjhmc_fail(MJHMC_ERR_INVALID, "params is NULL");
+  const int K = n_values;
+  if (K < 1 || K > mjhmc::kProjMaxValues)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "the number of values K must be in [1, " + std::to_string(mjhmc::kProjMaxValues) +
+                                             "], got " + std::to_string(K));
+  if (!s->ring) return mjhmc_fail(MJHMC_ERR_INVALID, "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  const int D = s->D;
+  int64_t at = first_nonfinite(A, (size_t)K * D);
+  if (at >= 0)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "A[" + std::to_string(at / D) + "][" + std::to_string(at % D) + "] is not finite");
+  if (b && (at = first_nonfinite(b, (size_t)K)) >= 0) return mjhmc_fail(MJHMC_ERR_INVALID, "b[" + std::to_string(at) + "] is not finite");
+  if ((at = first_nonfinite(params, nparams)) >= 0) return mjhmc_fail(MJHMC_ERR_INVALID, "p[" + std::to_string(at) + "] is not finite");
+  const int vec = s->dtype == MJHMC_F64 ? 2 : (s->dtype == MJHMC_F32 ? 4 : 8);
+  if (s->sh.esize * vec != 16 || s->sh.pitch % vec != 0)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
+  Shape shK;
+  TRY(pick_shape(K, MJHMC_F64, &shK));
+  if (shK.pitch != (K + 1) / 2 * 2) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "unexpected row pitch of the derived ring");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  const void* image = nullptr;
+  const char* lowered = nullptr;
+  if (link_expr) {
+    std::string err;
+    const int rc = mjhmc::projections_link_compile(link_expr, s->dtype, K, include_dir, &image, &lowered, &err);
+    if (rc) return mjhmc_fail(rc, err);
+  }
+  // A transposed and zero-padded to whole tiles and d chunks (projections.hpp: ProjArgs), b padded with zeros
+  const int Kpad = (K + 63) / 64 * 64, Dpad = (D + 63) / 64 * 64;
+  std::vector<double> At((size_t)Dpad * Kpad, 0.0), bp((size_t)Kpad, 0.0);
+  for (int k = 0; k < K; ++k) {
+    for (int d = 0; d < D; ++d) At[(size_t)d * Kpad + k] = A[(size_t)k * D + d];
+    if (b) bp[(size_t)k] = b[k];
+  }
+  mjhmc_functionals* f = new mjhmc_functionals();
+  f->s = s;
+  f->linear = true;
+  f->K = K;
+  f->pitchK = shK.pitch;
+  f->lin_Kpad = Kpad;
+  f->src_gen = s->ring_gen;
+  row_geometry(s->sh.pitch, vec, &f->chunks, &f->cw, &f->log_cw, &f->wide);
+  const int no_bad = mjhmc::kProjNoBad;
+  hipError_t e = hipSuccess;
+  if (image) {
+    e = hipModuleLoadData(&f->module, image);
+    if (e == hipSuccess) e = hipModuleGetFunction(&f->fn, f->module, lowered);
+  }
+  if (e == hipSuccess) e = hipMalloc((void**)&f->lin_At, At.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&f->lin_b, bp.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&f->dparams, (nparams ? nparams : 1) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&f->bad, sizeof(int));
+  if (e == hipSuccess) e = hipMemcpyAsync(f->lin_At, At.data(), At.size() * sizeof(double), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(f->lin_b, bp.data(), bp.size() * sizeof(double), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess && nparams)
+    e = hipMemcpyAsync(f->dparams, params, nparams * sizeof(double), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(f->bad, &no_bad, sizeof(int), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);   // (the host copies live for the duration of the call only)
+  if (e != hipSuccess) {
+    functionals_free(f);
+    (void)hipGetLastError();
+    return mjhmc_fail(MJHMC_ERR_HIP, std::string("projections: ") + hipGetErrorString(e));
+  }
+  s->functionals.push_back(f);
+  *out = f;
+  return 0;
+}
+
 int mjhmc_functionals_destroy(mjhmc_functionals* f) {
   if (!f) return 0;
   mjhmc_sampler* s = f->s;
@@ -406,6 +540,7 @@ int mjhmc_functionals_evaluate(mjhmc_functionals* f, int x_slot0, int n, int out
                                              ") are outside the derived ring of " + std::to_string(f->ring_slots));
   HIPCHK(hipSetDevice(s->ctx->device));
   if (f->energy) return energy_evaluate(f, x_slot0, n, out_slot0);
+  if (f->linear) return linear_evaluate(f, x_slot0, n, out_slot0);
   mjhmc::FunctionalsArgs a;
   a.src = (const char*)s->ring + (size_t)x_slot0 * mat_bytes(s);
   a.dst = f->ring + (size_t)out_slot0 * s->Npad * f->pitchK;

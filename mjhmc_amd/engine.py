@@ -441,6 +441,12 @@ class DeviceSampler(object):
         (mjhmc_functionals_create_energy).  The ring must exist (ring_alloc); a host-evaluated energy is refused."""
         return DeviceFunctionals.energy(self)
 
+    def projections(self, A, b=None, link=None, params=()):
+        """DeviceFunctionals whose K values of every recorded state are g = link(A x + b): ``A`` (K, ndims) float64, ``b``
+        (K,) or None, ``link`` one C expression of ``u``, ``k`` and ``p[m]`` or None for the identity, ``params`` the float64
+        ``p`` (mjhmc_functionals_create_linear; 1 <= K <= 512).  The ring must exist (ring_alloc)."""
+        return DeviceFunctionals.linear(self, A, b, link, params)
+
     def time_grid(self, n_grid, dt):
         """The jump process of every chain sampled at t_j = j * dt, j < n_grid, into a grid ring of this sampler's slot
         layout (mjhmc_timegrid_*): a fair sample with its time order kept.  The ring must exist (ring_alloc)."""
@@ -802,12 +808,23 @@ class DeviceFunctionals(object):
     (include/mjhmc_hip.h: mjhmc_functionals_create).  ``estimator``, ``chain_stats``, ``histogram`` and ``pair_histogram`` give the sampler's
     accumulators on the derived ring: their ``x_slot0`` counts derived slots, ``w_slot0`` the sampler's dwell slots."""
 
-    def __init__(self, dev, values, stats=(), params=(), _energy=False):
+    def __init__(self, dev, values, stats=(), params=(), _energy=False, _linear=None):
         self.dev, self.lib = dev, dev.lib
         self.nparticles = dev.nparticles
         self.params = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel())
         h = ctypes.c_void_p()
-        if _energy:
+        if _linear is not None:
+            A, b, link = _linear
+            A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+            if A.ndim != 2 or A.shape[1] != dev.ndims:
+                raise ValueError('A must be (K, ndims = %d), got %r' % (dev.ndims, A.shape))
+            if b is not None:
+                b = np.ascontiguousarray(np.broadcast_to(np.asarray(b, dtype=np.float64), (A.shape[0],)))
+            check_args(self.lib.mjhmc_functionals_create_linear(dev.handle, A.shape[0], ptr(A), ptr(b),
+                                                                None if link is None else str(link).encode(),
+                                                           ptr(self.params) if self.params.size else None, self.params.size,
+                                                           _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
+        elif _energy:
             # (its fixed scratch -- dE/dX and E of one slot, at most about two slots' bytes -- is taken here, from the 40 %
             # of free memory that ring_budget_slots(share=0.6) leaves beside the rings)
             check(self.lib.mjhmc_functionals_create_energy(dev.handle, ctypes.byref(h)), self.lib)
@@ -826,6 +843,12 @@ class DeviceFunctionals(object):
         """the energy observables [E, grad_sq, virial] of ``dev``'s recorded states (mjhmc_functionals_create_energy): the
         same handle family, filled by the sampler's own evaluation kernels instead of compiled expressions"""
         return cls(dev, (), _energy=True)
+
+    @classmethod
+    def linear(cls, dev, A, b=None, link=None, params=()):
+        """the linear projections g = link(A x + b) of ``dev``'s recorded states (mjhmc_functionals_create_linear): the
+        same handle family, filled by the small-GEMM kernel of csrc/projections.hpp"""
+        return cls(dev, (), params=params, _linear=(A, b, link))
 
     def ring_alloc(self, n_slots):
         """at least ``n_slots`` derived slots; a ring that grows is a new ring (handles created on the old one refuse)"""

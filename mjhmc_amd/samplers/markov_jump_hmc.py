@@ -410,6 +410,83 @@ class EnergyObservables(object):
         return (int(nparticles) + 63) // 64 * 64 * 4 * 8
 
 
+class Projections(object):
+    """What ``HMCBase.projections()`` returns: the description of K linear read-outs of the state,
+        u[k] = b[k] + sum_d A[k][d] x_d,   g[k] = link(u[k], k; p)
+    -- ``A`` (K, ndims) float64, ``b`` (K,) float64, ``link`` (one C expression of ``u``, ``k`` and ``p[m]``, or None for
+    g = u), ``params`` (float64), ``names`` (K strings, default 'u0', 'u1', ...) and ``n_values`` = K <= 512 -- checked
+    for shape and finiteness, bound to no device.  It stands where a ``Functionals`` stands: pass it as ``of=`` to
+    ``expectations()``, ``diagnostics()``, ``marginals()`` or ``joint_marginals()``, whose results then have K
+    "dimensions".  ``Projections.principal`` builds the principal axes of a measured covariance."""
+
+    MAX_VALUES = 512
+
+    def __init__(self, A, b=None, link=None, params=(), names=None, ndims=None):
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim == 1:
+            A = A.reshape(1, -1)
+        if A.ndim != 2 or A.shape[1] < 1:
+            raise ValueError('A must be (K, ndims) or (ndims,), got an array of shape %r' % (A.shape,))
+        if ndims is not None and A.shape[1] != int(ndims):
+            raise ValueError('A must have ndims = %d columns, got %d' % (int(ndims), A.shape[1]))
+        K = A.shape[0]
+        if not 1 <= K <= self.MAX_VALUES:
+            raise ValueError('the number of values K must be in [1, %d], got %d' % (self.MAX_VALUES, K))
+        if b is None:
+            b = np.zeros(K)
+        else:
+            b = np.asarray(b, dtype=np.float64)
+            if b.size not in (1, K) or b.ndim > 1:
+                raise ValueError('b must be a scalar or have K = %d entries, got shape %r' % (K, b.shape))
+            b = np.broadcast_to(b.reshape(-1), (K,))
+        params = np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel()
+        for what, v in (('A', A), ('b', b), ('params', params)):
+            if not np.all(np.isfinite(v)):
+                raise ValueError('%s must be finite' % what)
+        if link is not None and (not isinstance(link, str) or not link.strip() or ';' in link):
+            raise ValueError('link must be one C expression of u, k and p[m] (a non-empty string without semicolons), got %r' % (link,))
+        self.A, self.b, self.params = np.ascontiguousarray(A), np.ascontiguousarray(b), np.ascontiguousarray(params)
+        self.link = link
+        self.n_values = K
+        self.names = ['u%d' % k for k in range(K)] if names is None else [str(n) for n in names]
+        if len(self.names) != K:
+            raise ValueError('names must have one entry per value (%d), got %d' % (K, len(self.names)))
+
+    def slot_bytes(self, nparticles):
+        """bytes of one slot of the derived ring: rows padded to 64, values to an even count, float64"""
+        return (int(nparticles) + 63) // 64 * 64 * ((self.n_values + 1) // 2 * 2) * 8
+
+    @classmethod
+    def principal(cls, expectations, k=None, whiten=False, names=None):
+        """The principal axes of a measured covariance as projections: from an ``Expectations`` with a ``cov``
+        (``expectations(n, cov=True)``), row i of ``A`` is the eigenvector of ``cov`` with the i-th largest eigenvalue
+        (``numpy.linalg.eigh``), its sign fixed so that its largest-magnitude entry is positive, and ``b = -A mean``: the
+        values are the centred coordinates of the state along the widest axes.  ``k``: keep the first k axes (default
+        all).  ``whiten``: divide row i by sqrt(eigenvalue_i), so that the values have unit variance under the measured
+        covariance.  ValueError: ``cov`` is None; ``whiten`` with an eigenvalue <= 0; k outside [1, ndims]."""
+        cov = getattr(expectations, 'cov', None)
+        if cov is None:
+            raise ValueError('principal axes need a covariance: take the Expectations with cov=True')
+        cov = np.asarray(cov, dtype=np.float64)
+        mean = np.asarray(expectations.mean, dtype=np.float64).reshape(-1)
+        D = mean.size
+        if cov.shape != (D, D):
+            raise ValueError('cov must be (%d, %d), got %r' % (D, D, cov.shape))
+        k = D if k is None else int(k)
+        if not 1 <= k <= D:
+            raise ValueError('k must be in [1, ndims = %d], got %d' % (D, k))
+        lam, vec = np.linalg.eigh(0.5 * (cov + cov.T))
+        order = np.argsort(lam)[::-1][:k]
+        lam, A = lam[order], vec[:, order].T.copy()
+        big = np.argmax(np.abs(A), axis=1)
+        A *= np.where(A[np.arange(k), big] < 0, -1.0, 1.0)[:, None]
+        if whiten:
+            if np.any(lam <= 0):
+                raise ValueError('whiten needs positive eigenvalues, the smallest kept is %g' % lam.min())
+            A /= np.sqrt(lam)[:, None]
+        return cls(A, -A.dot(mean), names=names)
+
+
 class Temperature(object):
     """What ``HMCBase.temperature()`` returns: the virial thermometer of a run, from the ``Diagnostics`` of its energy
     observables (value 0 ``E``, 1 ``grad_sq``, 2 ``virial``):
@@ -796,6 +873,25 @@ class HMCBase(object):
             raise ValueError('functionals: %s' % (msg.decode() if msg else '?'))
         return F
 
+    def projections(self, A, b=None, link=None, params=(), names=None):
+        """K linear read-outs of the state for ``expectations / diagnostics / marginals / joint_marginals (..., of=P)``:
+            u[k] = b[k] + sum_d A[k][d] x_d,   g[k] = link(u[k], k; p)
+        ``A``: (K, ndims), or (ndims,) for one direction, 1 <= K <= 512; ``b``: a scalar or (K,), default 0; ``link``: None
+        (g = u) or one C expression of ``u`` (float64), ``k`` (int) and ``p[m]``, e.g. ``'1.0 / (1.0 + exp(-u))'``;
+        ``params``: the float64 ``p``.  The values are formed on the device by a small GEMM over the recorded states
+        (csrc/projections.hpp): an accumulator starts at b[k] and adds the products in ascending d, nothing fused, so a
+        value equals the NumPy loop ``u = b.copy(); for d: u = u + A[:, d, None] * X[d]`` bit for bit, whatever the state
+        type and the blocks.  Shapes, finiteness and the range of K are checked and the link is compiled here (no device
+        needed): ValueError, with the compiler's message for a link that does not compile.  Returns a ``Projections``;
+        ``Projections.principal(expectations)`` builds one from a measured covariance."""
+        P = Projections(A, b, link, params, names, ndims=self.ndims)
+        lib = _lib.load()
+        rc = lib.mjhmc_projections_check(P.n_values, None if P.link is None else P.link.encode(), _lib.KERNEL_HEADERS.encode())
+        if rc != 0:
+            msg = lib.mjhmc_last_error()
+            raise ValueError('projections: %s' % (msg.decode() if msg else '?'))
+        return P
+
     def energy_observables(self):
         """The energy observables [E, grad_sq, virial] for ``expectations / diagnostics / marginals / joint_marginals
         (..., of=EO)``: the potential energy of every recorded state, |dE/dX|^2 and x . dE/dX, evaluated on the device by
@@ -896,6 +992,8 @@ class HMCBase(object):
         """the device side of ``of`` on this sampler's ring (which must have its final size), with a derived ring"""
         if isinstance(of, EnergyObservables):
             fn = self._dev.energy_observables()
+        elif isinstance(of, Projections):
+            fn = self._dev.projections(of.A, of.b, of.link, of.params)
         else:
             fn = self._dev.functionals(of.values, of.stats, of.params)
         try:
@@ -904,6 +1002,11 @@ class HMCBase(object):
             fn.close()
             raise
         return fn
+
+    def _check_of(self, of):
+        """what of ``of`` can be refused before the run starts"""
+        if isinstance(of, Projections) and of.A.shape[1] != self.ndims:
+            raise ValueError('the projections have %d columns, the sampler has ndims = %d' % (of.A.shape[1], self.ndims))
 
     def _extra_slot_bytes(self, of):
         return 0 if of is None else of.slot_bytes(self._dev.nparticles)
@@ -923,7 +1026,7 @@ class HMCBase(object):
         reading that block twice.  The returned moments are about the true mean whatever the shift.  Sharded samplers
         sum over ranks, use rank 0's shift and the smallest ``block`` of all ranks.
 
-        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``).  The run is exactly that of ``of=None``; every block is evaluated
+        ``of``: a ``Functionals`` (``functionals()``), ``Projections`` (``projections()``) or ``EnergyObservables`` (``energy_observables()``).  The run is exactly that of ``of=None``; every block is evaluated
         into a derived ring on the device (csrc/functionals.hip) and the moments are those of the K functional values:
         ``shift`` has K entries and the result K "dimensions".  With an ``EnergyObservables`` the moments are accumulated
         slot by slot, so that under a given ``shift`` the sums W, S1, S2 (and C) do not depend on ``block``."""
@@ -932,6 +1035,7 @@ class HMCBase(object):
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
         if of is not None and shift is not None and np.size(shift) != of.n_values:
             raise ValueError('shift must have n_values = %d entries' % of.n_values)
+        self._check_of(of)
         lead = 1 if self._dwell_weighted else 0
         if block is None:
             block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
@@ -1025,7 +1129,7 @@ class HMCBase(object):
         ranks.  The per-chain sums take device memory (parts x (2 x row pitch + 1) x padded particles x 8 bytes): they
         are created before the block size is taken from what the device has left.
 
-        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``): the same run, the diagnostics of the K functional values (every
+        ``of``: a ``Functionals`` (``functionals()``), ``Projections`` (``projections()``) or ``EnergyObservables`` (``energy_observables()``): the same run, the diagnostics of the K functional values (every
         block is evaluated into a derived ring first; ``shift`` has K entries)."""
         n_iter = int(n_iter)
         if split and (n_iter < 4 or n_iter % 2):
@@ -1037,6 +1141,7 @@ class HMCBase(object):
                 raise ValueError('shift must have n_values = %d entries' % of.n_values)
         elif shift is not None and np.size(shift) != self.ndims:
             raise ValueError('shift must have ndims = %d entries' % self.ndims)
+        self._check_of(of)
         lead = 1 if self._dwell_weighted else 0
         segments = [n_iter // 2, n_iter // 2] if split else [n_iter]
         grad0 = self.distribution.dEdX_count
@@ -1107,7 +1212,7 @@ class HMCBase(object):
         units of 1.  Sharded samplers use rank 0's range and quantum and the smallest ``block`` of all ranks, and add
         their integer tables over ranks.
 
-        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``): the same run, one histogram per functional value (every block is
+        ``of``: a ``Functionals`` (``functionals()``), ``Projections`` (``projections()``) or ``EnergyObservables`` (``energy_observables()``): the same run, one histogram per functional value (every block is
         evaluated into a derived ring first; ``range`` entries are scalars or K-vectors, and the range=None moment pass,
         ``span`` and the quantum rule apply to the values)."""
         n_iter, bins = int(n_iter), int(bins)
@@ -1127,6 +1232,7 @@ class HMCBase(object):
                 raise ValueError('range needs finite lo < hi in every dimension')
         elif not span > 0:
             raise ValueError('span must be positive')
+        self._check_of(of)
         lead = 1 if self._dwell_weighted else 0
         if block is None:
             block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
@@ -1188,7 +1294,7 @@ class HMCBase(object):
         dimension has one range in every pair it appears in.  Sharded samplers use rank 0's ranges and quantum and the
         smallest ``block`` of all ranks, and add their integer tables over ranks.
 
-        ``of``: a ``Functionals`` (``functionals()``) or ``EnergyObservables`` (``energy_observables()``): the same run, ``pairs`` index the K functional values (every block
+        ``of``: a ``Functionals`` (``functionals()``), ``Projections`` (``projections()``) or ``EnergyObservables`` (``energy_observables()``): the same run, ``pairs`` index the K functional values (every block
         is evaluated into a derived ring first; ``range`` entries are scalars or K-vectors)."""
         n_iter, bins = int(n_iter), int(bins)
         K = self.ndims if of is None else of.n_values
@@ -1214,6 +1320,7 @@ class HMCBase(object):
                 raise ValueError('range needs finite lo < hi in every dimension')
         elif not span > 0:
             raise ValueError('span must be positive')
+        self._check_of(of)
         lead = 1 if self._dwell_weighted else 0
         if block is None:
             block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
