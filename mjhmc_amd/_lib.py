@@ -181,6 +181,8 @@ TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_timegrid_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
     'mjhmc_test_functionals_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
     'mjhmc_test_energy_observables_part': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_test_device_math': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_int64, _P, _P]),
+    'mjhmc_test_normal_pairs': (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P]),
 }
 
 _lib = None

@@ -142,17 +142,22 @@ __device__ __forceinline__ int dense_control(float H0, float HL, double p_r, dou
   return (accept ? 1 : 0) | (flip ? 2 : 0);
 }
 
+// float32 Box-Muller on two uniforms of u53() rounded to float32 (u2 may round to 1.0: the angle 2 pi)
+__device__ __forceinline__ void box_muller_f32(float u1, float u2, float& z0, float& z1) {
+  const float r = sqrtf(-2.0f * logf(u1 > 0.f ? u1 : 1e-38f));
+  float s, c;
+  sincospif(2.0f * u2, &s, &c);
+  z0 = r * c;
+  z1 = r * s;
+}
+
 // float32 Box-Muller pair from the same Philox words as normal_pair (the float64 version costs ~4x
 // the instructions; for float32 / bfloat16 state its extra digits are rounded away anyway)
 __device__ __forceinline__ void normal_pair_f32(const RngKey& k, uint32_t pid, uint32_t pair, float& z0, float& z1) {
   const u32x4 w = philox4x32_10(pid, k.tick_lo, k.tick_hi, pair, k.k0, k.k1);
   const float u1 = (float)u53(w.w0, w.w1);
   const float u2 = (float)u53(w.w2, w.w3);
-  const float r = sqrtf(-2.0f * logf(u1 > 0.f ? u1 : 1e-38f));
-  float s, c;
-  sincospif(2.0f * u2, &s, &c);
-  z0 = r * c;
-  z1 = r * s;
+  box_muller_f32(u1, u2, z0, z1);
 }
 
 // ndims == nbasis > 512 (the reference takes any square size, distributions.py:379-406): the pre-scaled matrices as

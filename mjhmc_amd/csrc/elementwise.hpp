@@ -1137,7 +1137,7 @@ __device__ __forceinline__ void refresh_stash(typename VecOf<T>::type (*st)[64],
 }
 
 // exp(h) for |h| < 708 (normal result, no special cases): the library's range reduction and degree-11 polynomial
-// without its overflow / underflow / NaN handling.  Within 1 ulp of libm (tools/check_device_math.hip).
+// without its overflow / underflow / NaN handling.  Measured 0.83 ulp against long double, gated at 2 (tests/test_gpu_device_math.py).
 // p = r * p + c with the constant c in a scalar register pair: one VOP3 instruction.  hipcc's own form of a Horner
 // step is v_mov x2 (the 64-bit literal into the accumulator VGPR) + v_fmac: three vector instructions.
 __device__ __forceinline__ double horner_sc(double r, double p, double c) {

@@ -48,9 +48,11 @@ struct RngKey {
   uint32_t tick_lo, tick_hi;
 };
 
-// -log(u) for u in (0, 1), the unit exponential behind draw_from (utils.py:42): fdlibm's e_log.c scheme
-// (error < 1 ulp) without its special cases -- u53() never returns 0 or 1 and its smallest value 2^-54 is a
-// normal number.  About half the vector instructions and half the dependent-chain length of the library log
+// -log(u) for u in (0, 1], the unit exponential behind draw_from (utils.py:42): fdlibm's e_log.c scheme (measured
+// 0.72 ulp against long double, gated at 2: tests/test_gpu_device_math.py) without its special cases -- u53() returns
+// the multiples of 2^-53 in (0, 1]: never 0, its smallest value 2^-53 is a normal number, and 1.0 is reachable (both
+// words all ones) and gives +0.0: a zero waiting time, a zero Box-Muller radius, never a negative one.
+// About half the vector instructions and half the dependent-chain length of the library log
 // (which carries double-double intermediates).  (Feeding the coefficients from scalar registers through inline
 // asm saved more instructions but cost ~30 VGPRs and an occupancy step: measured slower.)
 __device__ __forceinline__ double neg_log_unit(double u) {
@@ -85,7 +87,8 @@ __device__ __forceinline__ double neg_log_unit(double u) {
 
 
 // sin(pi t), cos(pi t) for t in [0, 2]: the quadrant reduction is exact (t is a multiple of 2^-52), then fdlibm's
-// k_sin.c / k_cos.c polynomials on |x| <= pi/4 (error ~1 ulp; tools/check_device_math.hip).  About a third of
+// k_sin.c / k_cos.c polynomials on |x| <= pi/4 (absolute error measured 1.33 x 2^-53, gated at 1.5 x 2^-53; exact at
+// t = 0, 1/2, 1, 3/2, 2: tests/test_gpu_device_math.py).  About a third of
 // the library sincospi's vector instructions: no argument classes to tell apart.
 __device__ __forceinline__ void sincospi_unit(double t, double& s, double& c) {
   const double n = __builtin_rint(2.0 * t);                                   // 0 .. 4
@@ -112,16 +115,21 @@ __device__ __forceinline__ void sincospi_unit(double t, double& s, double& c) {
   c = ((q + 1) & 2) ? -cc : cc;
 }
 
-// Box-Muller pair for dims (2*pair, 2*pair+1) of particle pid: sqrt(-2 log u1) * (cos, sin)(2 pi u2), as oracle/philox.py
-__device__ inline void normal_pair(const RngKey& k, uint32_t pid, uint32_t pair, double& z0, double& z1) {
-  const u32x4 w = philox4x32_10(pid, k.tick_lo, k.tick_hi, pair, k.k0, k.k1);
-  const double u1 = u53(w.w0, w.w1);
-  const double u2 = u53(w.w2, w.w3);
+// Box-Muller on two uniforms of u53(): sqrt(-2 log u1) * (cos, sin)(2 pi u2)
+__device__ __forceinline__ void box_muller(double u1, double u2, double& z0, double& z1) {
   const double r = sqrt(2.0 * neg_log_unit(u1));
   double s, c;
   sincospi_unit(2.0 * u2, s, c);
   z0 = r * c;
   z1 = r * s;
+}
+
+// Box-Muller pair for dims (2*pair, 2*pair+1) of particle pid, as oracle/philox.py
+__device__ inline void normal_pair(const RngKey& k, uint32_t pid, uint32_t pair, double& z0, double& z1) {
+  const u32x4 w = philox4x32_10(pid, k.tick_lo, k.tick_hi, pair, k.k0, k.k1);
+  const double u1 = u53(w.w0, w.w1);
+  const double u2 = u53(w.w2, w.w3);
+  box_muller(u1, u2, z0, z1);
 }
 
 }  // namespace mjhmc

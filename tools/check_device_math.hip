@@ -1,4 +1,6 @@
-// Accuracy check of the hand-written transcendental kernels of the jump kernel against host libm.
+// Accuracy exploration of the hand-written transcendental kernels of the jump kernel against host libm: a stand-alone
+// tool for trying a changed chain quickly.  The gate is the suite -- tests/test_gpu_device_math.py pins the same functions
+// (and exp_neg, exp_neg_k, the scalar-constant forms and both Box-Muller functions) to long double at their edges.
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -DMJHMC_JUMP_WAVES=1 -I mjhmc_amd/csrc tools/check_device_math.hip -o /tmp/cdm && /tmp/cdm
 #include <hip/hip_runtime.h>
 
@@ -47,8 +49,8 @@ int main() {
     const double v = ((double)(st >> 11) + 0.5) * 0x1p-53;
     u.push_back(u.size() % 5 == 0 ? v * 0x1p-30 : (u.size() % 7 == 0 ? 1.0 - v * 0x1p-20 : v));
   }
-  u[0] = 0x1p-54;
-  u[1] = 1.0 - 0x1p-54;
+  u[0] = 0x1p-53;   // the two ends of u53()'s range (0, 1]: its smallest value, and 1.0 (-> +0.0)
+  u[1] = 1.0;
   const int n = (int)dH.size();
   double *d_dH, *d_u, *d_r, *d_l, *d_e;
   hipMalloc(&d_e, n * 8);
