@@ -17,6 +17,7 @@
 #include "autocor.hpp"
 #include "lagcov.hpp"
 #include "handles.hpp"
+#include "ring_source.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // error plumbing
@@ -61,12 +62,6 @@ static int zero_call(mjhmc_sampler* s, int rows) {
   return 0;
 }
 
-static int pow2ceil(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 // The A/B switches of the measurement tools and of the launch-strategy tests (MJHMC_NO_FUSE, MJHMC_NO_COMPACT,
 // MJHMC_NO_SPLIT, MJHMC_SPLIT_PARTS, MJHMC_NO_FSPEC, MJHMC_NO_ROWS, MJHMC_NO_LIST_CARRY, MJHMC_FUSE_BELOW, MJHMC_NO_BLOCK_DECIDE, MJHMC_NO_WPP, MJHMC_NO_QUAD, MJHMC_CHUNKS_PER_LANE,
 // MJHMC_SIC_COPIES) and the failure-placing hook MJHMC_DEBUG_POISON exist only in libmjhmc_hip_test.so (built with
@@ -88,12 +83,6 @@ static int ab_flags() {
 static RngKey rng_key(const mjhmc_sampler* s, uint64_t tick) {
   return RngKey{(uint32_t)(s->seed & 0xFFFFFFFFu), (uint32_t)(s->seed >> 32), (uint32_t)(tick & 0xFFFFFFFFu),
                 (uint32_t)(tick >> 32)};
-}
-
-static int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
 }
 
 // lanes-per-particle / elements-per-lane selection (see elementwise.hpp header comment)
@@ -1061,10 +1050,7 @@ int mjhmc_sampler_destroy(mjhmc_sampler* s) {
   (void)hipSetDevice(s->ctx->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   functionals_free_all(s);   // (and the handles created on them)
-  estimator_free_all(s);
-  chainstats_free_all(s);
-  histogram_free_all(s);
-  pairhist_free_all(s);
+  accumulators_free_all(s);
   timegrid_free_all(s);
   stein_free_all(s);
   void* ptrs[] = {s->flf_list, s->call_block, s->Hpre, s->Hwork, s->cold_list, s->pot64_scratch, s->Hspec[0], s->Hspec[1], s->Hspec_dump, s->Gbuf[0], s->Gbuf[1], s->Xbuf[0], s->Xbuf[1], s->Vbuf[0],  s->Vbuf[1], s->EX[0],     s->EX[1],  s->EV[0],

@@ -9,8 +9,8 @@
 // ([Npad][pitch] float64), so one index serves the state and both accumulators.
 //
 // Chain pass: one launch per accumulate, HBM-bound.  A slot is a contiguous [Npad][pitch] matrix and a lane owns 16 bytes
-// of it (2 / 4 / 8 elements of one chain's row): lane g of the launch takes bytes [16 g, 16 g + 16) of every slot of the
-// block, so a wave instruction reads 1 KB of consecutive memory.  The lane reads the stored sums of its elements into
+// of it (ring_rows.hpp; 2 / 4 / 8 elements of one chain's row): lane g of the launch takes bytes [16 g, 16 g + 16) of
+// every slot of the block, so a wave instruction reads 1 KB of consecutive memory.  The lane reads the stored sums of its elements into
 // registers, walks the block's slots for them (kSlotsInFlight loads issued before the first is used) and writes the
 // sums back once.  No cross-lane reduction, no atomics, no LDS.  The operation order per element is part of the contract:
 //   t = x - c;  u = w * t;  a1 = a1 + u;  a2 = a2 + u * t;     k ascending, from the stored a1, a2;  a0 = a0 + w
@@ -35,48 +35,10 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "ring_rows.hpp"
 #include "ring_source.hpp"
 
 namespace {
-
-// 16 bytes of a row, as loaded, and their exact widening to VEC doubles
-template <typename T>
-struct Chunk;
-template <>
-struct Chunk<double> {
-  static constexpr int VEC = 2;
-  typedef double2 Raw;
-  __device__ static void widen(const Raw& q, double* v) {
-    v[0] = q.x;
-    v[1] = q.y;
-  }
-};
-template <>
-struct Chunk<float> {
-  static constexpr int VEC = 4;
-  typedef float4 Raw;
-  __device__ static void widen(const Raw& q, double* v) {
-    v[0] = (double)q.x;
-    v[1] = (double)q.y;
-    v[2] = (double)q.z;
-    v[3] = (double)q.w;
-  }
-};
-template <>
-struct Chunk<__bf16> {
-  static constexpr int VEC = 8;
-  typedef uint4 Raw;
-  __device__ static void widen(const Raw& q, double* v) {
-    const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = (double)__uint_as_float(u[j] << 16);
-      v[2 * j + 1] = (double)__uint_as_float(u[j] & 0xFFFF0000u);
-    }
-  }
-};
-
-constexpr int kSlotsInFlight = 4;   // 16-byte loads a lane issues before it uses the first
 
 // any non-finite weight among w[k * Npad + p], k < n, p < N
 __global__ __launch_bounds__(256) void cs_check_kernel(const double* __restrict__ w, int64_t Npad, int64_t N, int n,
@@ -85,7 +47,7 @@ __global__ __launch_bounds__(256) void cs_check_kernel(const double* __restrict_
   for (int k = blockIdx.y; k < n; k += gridDim.y) {
     const double* wk = w + (size_t)k * Npad;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < N; p += (int64_t)gridDim.x * 256)
-      if (!(fabs(wk[p]) <= 1.7976931348623157e308)) nonfinite = 1;
+      if (!finite_f64(wk[p])) nonfinite = 1;
   }
   if (nonfinite) *bad = 1;
 }
@@ -97,8 +59,7 @@ __global__ __launch_bounds__(256) void cs_chain_kernel(const T* __restrict__ bas
                                                        int pitch, int chunks, double* __restrict__ a0,
                                                        double* __restrict__ a1, double* __restrict__ a2,
                                                        const int* __restrict__ bad) {
-  constexpr int VEC = Chunk<T>::VEC;
-  typedef typename Chunk<T>::Raw Raw;
+  constexpr int VEC = ChunkOf<T>::VEC;
   if (*bad) return;
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = N * chunks;
@@ -125,13 +86,13 @@ __global__ __launch_bounds__(256) void cs_chain_kernel(const T* __restrict__ bas
   const T* const x0 = base + (size_t)g * VEC;
   const double* const w0 = w ? w + p : nullptr;
   for (int k0 = 0; k0 < n; k0 += kSlotsInFlight) {
-    Raw q[kSlotsInFlight];
+    uint4 q[kSlotsInFlight];
     double wt[kSlotsInFlight];
 #pragma unroll
     for (int u = 0; u < kSlotsInFlight; ++u) {
       wt[u] = 1.0;
       if (k0 + u < n) {
-        q[u] = *reinterpret_cast<const Raw*>(x0 + (size_t)(k0 + u) * slot_elems);
+        q[u] = *reinterpret_cast<const uint4*>(x0 + (size_t)(k0 + u) * slot_elems);
         if (w0) wt[u] = w0[(size_t)(k0 + u) * Npad];
       }
     }
@@ -139,7 +100,7 @@ __global__ __launch_bounds__(256) void cs_chain_kernel(const T* __restrict__ bas
     for (int u = 0; u < kSlotsInFlight; ++u) {
       if (k0 + u < n) {
         double x[VEC];
-        Chunk<T>::widen(q[u], x);
+        ChunkOf<T>::widen(q[u], x);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
           const double t = x[j] - cs[j];
@@ -255,19 +216,12 @@ __global__ void cs_to_dim_major(const double* __restrict__ src, double* __restri
   }
 }
 
-int pow2ceil_i(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 }  // namespace
 
 ChainFoldPlan chain_fold_plan(const RingView& r) {
   ChainFoldPlan pl;
-  pl.cw = std::min(256, pow2ceil_i(r.D));
-  pl.log_cw = 0;
-  while ((1 << pl.log_cw) < pl.cw) ++pl.log_cw;
+  pl.cw = std::min(256, pow2ceil(r.D));
+  pl.log_cw = ilog2(pl.cw);
   pl.gy = (r.D + pl.cw - 1) / pl.cw;
   const int rw = 256 / pl.cw;
   // about four workgroups per compute unit, each row lane with at least four chains
@@ -288,16 +242,11 @@ int chain_accumulate(hipStream_t st, const RingView& r, int n, const double* w, 
   const int chunks = r.pitch / vec;   // (a row is whole 16-byte chunks: pick_shape, shape_for)
   const int64_t lanes = r.N * chunks;
   const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-#define MJHMC_CS_LAUNCH(T)                                                                                              \
-  hipLaunchKernelGGL(cs_chain_kernel<T>, grid, block, 0, st, (const T*)r.base, w, c, r.Npad, r.N, n, r.D, r.pitch, chunks, \
-                     a0, a1, a2, bad)
-  if (r.dtype == MJHMC_F64)
-    MJHMC_CS_LAUNCH(double);
-  else if (r.dtype == MJHMC_F32)
-    MJHMC_CS_LAUNCH(float);
-  else
-    MJHMC_CS_LAUNCH(__bf16);
-#undef MJHMC_CS_LAUNCH
+  dispatch_dtype(r.dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(cs_chain_kernel<T>, grid, block, 0, st, (const T*)r.base, w, c, r.Npad, r.N, n, r.D, r.pitch, chunks,
+                       a0, a1, a2, bad);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     err = std::string("chain pass: ") + hipGetErrorString(e);
@@ -326,46 +275,22 @@ int chain_fold(hipStream_t st, const RingView& r, const ChainFoldPlan& pl, const
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kChainMaxParts = 2;
 
-struct mjhmc_chainstats {
-  mjhmc_sampler* s = nullptr;
-  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
+struct mjhmc_chainstats : RingAccumulator {   // (ring_gen: the sums have that ring's row layout)
+  using RingAccumulator::RingAccumulator;
   int D = 0, pitch = 0;       // dimensions and row pitch of a state of that ring
   int n_parts = 1;
-  uint64_t ring_gen = 0;      // that ring at create: the sums have its row layout
   ChainFoldPlan plan;
   double* acc = nullptr;      // [n_parts] x { a0 [Npad], a1 [Npad][pitch], a2 [Npad][pitch] }
   double* shift = nullptr;    // [D]
   double* fpart = nullptr;    // the fold's per-workgroup partials
   double* fout = nullptr;     // [1 + 3 D]
-  int* bad = nullptr;
+  ~mjhmc_chainstats() override { free_device({acc, shift, fpart, fout}); }
   int64_t n_slots[kChainMaxParts] = {0, 0};   // states per chain added to each part
   size_t part_elems() const { return (size_t)(2 * pitch + 1) * s->Npad; }
   double* a0(int h) const { return acc + (size_t)h * part_elems(); }
   double* a1(int h) const { return a0(h) + s->Npad; }
   double* a2(int h) const { return a1(h) + (size_t)s->Npad * pitch; }
 };
-
-static void chainstats_free(mjhmc_chainstats* cs) {
-  for (void* p : {(void*)cs->acc, (void*)cs->shift, (void*)cs->fpart, (void*)cs->fout, (void*)cs->bad})
-    if (p) (void)hipFree(p);
-  delete cs;
-}
-
-void chainstats_free_all(mjhmc_sampler* s) {
-  for (mjhmc_chainstats* cs : s->chainstats) chainstats_free(cs);
-  s->chainstats.clear();
-}
-
-void chainstats_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
-  std::vector<mjhmc_chainstats*> keep;
-  for (mjhmc_chainstats* cs : s->chainstats) {
-    if (cs->fn == f)
-      chainstats_free(cs);
-    else
-      keep.push_back(cs);
-  }
-  s->chainstats.swap(keep);
-}
 
 static int chain_check_part(const mjhmc_chainstats* cs, int part) {
   if (!cs) return mjhmc_fail(MJHMC_ERR_INVALID, "chainstats is NULL");
@@ -377,21 +302,16 @@ static int chain_check_part(const mjhmc_chainstats* cs, int part) {
 static int chainstats_create_on_source(mjhmc_sampler* s, const mjhmc_functionals* fn, int n_parts, mjhmc_chainstats** out) {
   if (n_parts < 1 || n_parts > kChainMaxParts) return mjhmc_fail(MJHMC_ERR_INVALID, "n_parts must be 1 or 2");
   const RingSource src = ring_source(s, fn);
-  if (!src.base)
-    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
-                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  if (!src.base) return acc_no_ring(fn);
   // the chain pass addresses a slot in 16-byte chunks of the state's own type: rows must be whole chunks of it
   const int vec = src.dtype == MJHMC_F64 ? 2 : (src.dtype == MJHMC_F32 ? 4 : 8);
   if (src.esize * vec != 16 || src.pitch % vec != 0)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
   HIPCHK(hipSetDevice(s->ctx->device));
-  mjhmc_chainstats* cs = new mjhmc_chainstats();
-  cs->s = s;
-  cs->fn = fn;
+  mjhmc_chainstats* cs = new mjhmc_chainstats("chainstats", "one", s, fn, src);
   cs->D = src.D;
   cs->pitch = src.pitch;
   cs->n_parts = n_parts;
-  cs->ring_gen = src.gen;
   cs->plan = chain_fold_plan(ring_source_view(s, src, 0));
   const size_t D = (size_t)src.D, acc_bytes = (size_t)n_parts * cs->part_elems() * sizeof(double);
   hipError_t e = hipMalloc((void**)&cs->acc, acc_bytes);
@@ -404,16 +324,14 @@ static int chainstats_create_on_source(mjhmc_sampler* s, const mjhmc_functionals
   if (e == hipSuccess) e = hipMemsetAsync(cs->bad, 0, sizeof(int), s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   if (e != hipSuccess) {
-    chainstats_free(cs);
+    delete cs;
     (void)hipGetLastError();
     char msg[256];
     std::snprintf(msg, sizeof(msg), "chain statistics buffers (%.3f GB of per-chain sums): %s", acc_bytes / 1e9,
                   hipGetErrorString(e));
     return mjhmc_fail(MJHMC_ERR_HIP, msg);
   }
-  s->chainstats.push_back(cs);
-  *out = cs;
-  return 0;
+  return acc_created(cs, out);
 }
 
 extern "C" {
@@ -428,15 +346,7 @@ int mjhmc_chainstats_create_on(mjhmc_functionals* f, int n_parts, mjhmc_chainsta
   return chainstats_create_on_source(functionals_sampler(f), f, n_parts, out);
 }
 
-int mjhmc_chainstats_destroy(mjhmc_chainstats* cs) {
-  if (!cs) return 0;
-  mjhmc_sampler* s = cs->s;
-  (void)hipSetDevice(s->ctx->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  s->chainstats.erase(std::remove(s->chainstats.begin(), s->chainstats.end(), cs), s->chainstats.end());
-  chainstats_free(cs);
-  return 0;
-}
+int mjhmc_chainstats_destroy(mjhmc_chainstats* cs) { return acc_destroy(cs); }
 
 int mjhmc_chainstats_reset(mjhmc_chainstats* cs) {
   if (!cs) return mjhmc_fail(MJHMC_ERR_INVALID, "chainstats is NULL");
@@ -470,33 +380,18 @@ int mjhmc_chainstats_set_shift(mjhmc_chainstats* cs, const double* c) {
 int mjhmc_chainstats_accumulate(mjhmc_chainstats* cs, int part, int x_slot0, int w_slot0, int n) {
   TRY(chain_check_part(cs, part));
   mjhmc_sampler* s = cs->s;
-  const RingSource src = ring_source(s, cs->fn);
-  if (cs->ring_gen != src.gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_chainstats_create: create a new one");
-  if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(src.slots));
-  if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
-    return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots) +
-                                             " (-1 asks for unit weights)");
+  RingSource src;
+  TRY(acc_begin(cs, x_slot0, w_slot0, n, &src));
   HIPCHK(hipSetDevice(s->ctx->device));
-  const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
+  const double* w = acc_weights(cs, w_slot0);
   std::string err;
   const int rc = chain_accumulate(s->stream, ring_source_view(s, src, x_slot0), n, w, cs->shift, cs->a0(part), cs->a1(part),
                                   cs->a2(part), cs->bad, err);
   if (rc) return mjhmc_fail(rc, err);
   if (w) {   // (unit weights raise no flag: nothing to wait for)
     int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, cs->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (bad) {
-      HIPCHK(hipMemsetAsync(cs->bad, 0, sizeof(int), s->stream));
-      return mjhmc_fail(MJHMC_ERR_NONFINITE, "a dwelling time in dwell slots [" + std::to_string(w_slot0) + ", " +
-                                                 std::to_string(w_slot0 + n) +
-                                                 ") is not finite (a state whose total jump rate is zero): nothing of this block was added");
-    }
+    TRY(acc_take_flag(cs, &bad));
+    if (bad) return acc_nonfinite_dwell(w_slot0, n);
   }
   cs->n_slots[part] += n;
   return 0;

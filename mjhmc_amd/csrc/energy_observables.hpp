@@ -44,8 +44,8 @@ struct EnergyObsArgs {
 // the G elements that match one 16-byte chunk of X: VEC elements of GT (0 float64, 1 float32) = NQ 16-byte loads
 template <int DT, int GT>
 struct EoGrad {
-  static constexpr int VEC = FnChunk<DT>::VEC;
-  static constexpr int GVEC = FnChunk<GT>::VEC;
+  static constexpr int VEC = RowChunk<DT>::VEC;
+  static constexpr int GVEC = RowChunk<GT>::VEC;
   static_assert(GT == 0 || GT == 1, "dE/dX is float64 or float32");
   static_assert(VEC % GVEC == 0, "a chunk of X must cover whole 16-byte chunks of dE/dX");
   static constexpr int NQ = VEC / GVEC;
@@ -59,7 +59,7 @@ struct EoGrad {
   }
   __device__ static __forceinline__ void widen(const uint4* q, double* g) {
 #pragma unroll
-    for (int i = 0; i < NQ; ++i) FnChunk<GT>::widen(q[i], g + i * GVEC);
+    for (int i = 0; i < NQ; ++i) RowChunk<GT>::widen(q[i], g + i * GVEC);
   }
 };
 
@@ -73,9 +73,9 @@ __device__ __forceinline__ double eo_energy(const void* __restrict__ E, long lon
 // chunk c of a row: its elements d < D, in ascending d, into the lane's two partials
 template <int DT, int GT>
 __device__ __forceinline__ void eo_add_chunk(const uint4& qx, const uint4* qg, int c, int D, double& gs, double& vr) {
-  constexpr int VEC = FnChunk<DT>::VEC;
+  constexpr int VEC = RowChunk<DT>::VEC;
   double x[VEC], g[VEC];
-  FnChunk<DT>::widen(qx, x);
+  RowChunk<DT>::widen(qx, x);
   EoGrad<DT, GT>::widen(qg, g);
 #pragma unroll
   for (int e = 0; e < VEC; ++e) {
@@ -96,9 +96,9 @@ __device__ __forceinline__ void eo_finish(double e, double gs, double vr, int cx
   vr = fn_group_sum(vr, cw);
   if (cx != 0) return;
   int nf = 0;
-  if (!(fabs(e) <= 1.7976931348623157e308)) nf |= 1;
-  if (!(fabs(gs) <= 1.7976931348623157e308)) nf |= 2;
-  if (!(fabs(vr) <= 1.7976931348623157e308)) nf |= 4;
+  if (!finite_f64(e)) nf |= 1;
+  if (!finite_f64(gs)) nf |= 2;
+  if (!finite_f64(vr)) nf |= 4;
   double2* o = reinterpret_cast<double2*>(out);
   o[0] = make_double2(e, gs);
   o[1] = make_double2(vr, 0.0);

@@ -16,8 +16,8 @@
 // passes w_slot0 = x_slot0 + 1.  (Read from the sources named above, all five writers; the definition test then checks
 // the pairing numerically against ring_read / ring_read_dwell.)
 //
-// Moment pass: HBM-bound, one read of the block.  A lane owns 16 bytes of a row (2 / 4 / 8 elements) and walks the
-// particles with a stride; float64 partial sums per lane, summed over the row lanes of the workgroup through LDS, one
+// Moment pass: HBM-bound, one read of the block.  A lane owns 16 bytes of a row (ring_rows.hpp) and walks the
+// particles with a stride, kRowsInFlight loads issued before the first is used; float64 partial sums per lane, summed over the row lanes of the workgroup through LDS, one
 // partial vector per workgroup in a scratch buffer, and a second small kernel that adds the workgroups' partials in
 // index order to the running sums.  No floating-point atomics: the result does not depend on the schedule.
 //
@@ -37,61 +37,12 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "ring_rows.hpp"
 #include "ring_source.hpp"
 
 namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline double bf16_bits_to_f64(uint32_t hi16) { return (double)__uint_as_float(hi16 << 16); }
-
-// 16 bytes of a row -> VEC doubles
-template <typename T>
-struct Chunk;
-template <>
-struct Chunk<double> {
-  static constexpr int VEC = 2;
-  __device__ static void load(const double* p, double* v) {
-    const double2 q = *reinterpret_cast<const double2*>(p);
-    v[0] = q.x;
-    v[1] = q.y;
-  }
-};
-template <>
-struct Chunk<float> {
-  static constexpr int VEC = 4;
-  __device__ static void load(const float* p, double* v) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = (double)q.x;
-    v[1] = (double)q.y;
-    v[2] = (double)q.z;
-    v[3] = (double)q.w;
-  }
-};
-template <>
-struct Chunk<__bf16> {
-  static constexpr int VEC = 8;
-  __device__ static void load(const __bf16* p, double* v) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p);
-    const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = bf16_bits_to_f64(u[j] & 0xFFFFu);
-      v[2 * j + 1] = bf16_bits_to_f64(u[j] >> 16);
-    }
-  }
-};
-
-template <typename T>
-__device__ inline double widen(const T* p) {
-  return (double)*p;
-}
-template <>
-__device__ inline double widen<__bf16>(const __bf16* p) {
-  return bf16_bits_to_f64(*reinterpret_cast<const uint16_t*>(p));
-}
-
-constexpr int kRowsInFlight = 4;   // 16-byte loads a lane issues before it uses the first
 
 // partial[(bx * 2 + m) * pitch + col] = the workgroup's sum of w (x - c)^(m + 1), partial_w[bx] = its sum of w
 template <typename T>
@@ -99,7 +50,7 @@ __global__ __launch_bounds__(256) void est_moments_kernel(const T* __restrict__ 
                                                           const double* __restrict__ c, int64_t Npad, int64_t N, int n, int D,
                                                           int pitch, int cw, int log_cw, double* __restrict__ partial,
                                                           double* __restrict__ partial_w, int* __restrict__ bad) {
-  constexpr int VEC = Chunk<T>::VEC;
+  constexpr int VEC = ChunkOf<T>::VEC;
   __shared__ double sm[256][2 * VEC + 1];
   const int tid = threadIdx.x;
   const int cx = tid & (cw - 1), ry = tid >> log_cw, rw = 256 >> log_cw;
@@ -126,14 +77,14 @@ __global__ __launch_bounds__(256) void est_moments_kernel(const T* __restrict__ 
         wt[u] = 0.0;
         if (p < N) {
           wt[u] = wk ? wk[p] : 1.0;
-          if (active) Chunk<T>::load(slot + (size_t)p * pitch, x[u]);
+          if (active) ChunkOf<T>::widen(*reinterpret_cast<const uint4*>(slot + (size_t)p * pitch), x[u]);
         }
       }
 #pragma unroll
       for (int u = 0; u < kRowsInFlight; ++u) {
         const int64_t p = p0 + u * stride;
         if (p < N) {
-          if (!(fabs(wt[u]) <= 1.7976931348623157e308)) nonfinite = 1;
+          if (!finite_f64(wt[u])) nonfinite = 1;
           wsum += wt[u];
           if (active) {
 #pragma unroll
@@ -209,6 +160,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void est_cov_kernel(const T* __restrict__ base, const double* __restrict__ w,
                                                       const double* __restrict__ c, int64_t Npad, int64_t N, int n, int D,
                                                       int pitch, int nb, int splits, double* __restrict__ partial) {
+  typedef typename ElemBits<T>::type Bits;   // (bfloat16 is loaded as its 16 bits)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int split = blockIdx.y * 4 + wave;
   // blockIdx.x -> (I, J), I <= J < nb, row-major over the upper triangle
@@ -253,11 +205,11 @@ __global__ __launch_bounds__(256) void est_cov_kernel(const T* __restrict__ base
     const int64_t p = fst * 4 + lk;
     const bool live = p < N;
     wgt = live ? (w ? w[(size_t)fk * Npad + p] : 1.0) : 0.0;
-    const T* row = base + ((size_t)fk * Npad + (live ? p : 0)) * pitch;
+    const Bits* row = reinterpret_cast<const Bits*>(base) + ((size_t)fk * Npad + (live ? p : 0)) * pitch;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      a[t] = (live && colA[t] < D) ? widen<T>(row + colA[t]) : cA[t];
-      if (!diag) b[t] = (live && colB[t] < D) ? widen<T>(row + colB[t]) : cB[t];
+      a[t] = (live && colA[t] < D) ? elem_to_f64(row[colA[t]]) : cA[t];
+      if (!diag) b[t] = (live && colB[t] < D) ? elem_to_f64(row[colB[t]]) : cB[t];
     }
     fst += splits;
     if (fst >= nst) {
@@ -326,21 +278,14 @@ __global__ __launch_bounds__(256) void est_fold_cov_kernel(const double* __restr
   C[(size_t)e * D + d] = v;
 }
 
-int pow2ceil_i(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 }  // namespace
 
 EstimatorPlan estimator_plan(const RingView& r, bool want_cov) {
   EstimatorPlan pl;
   pl.vec = r.dtype == MJHMC_F64 ? 2 : (r.dtype == MJHMC_F32 ? 4 : 8);
   const int chunks = (r.pitch + pl.vec - 1) / pl.vec;
-  pl.cw = std::min(256, pow2ceil_i(chunks));
-  pl.log_cw = 0;
-  while ((1 << pl.log_cw) < pl.cw) ++pl.log_cw;
+  pl.cw = std::min(256, pow2ceil(chunks));
+  pl.log_cw = ilog2(pl.cw);
   pl.gy = (chunks + pl.cw - 1) / pl.cw;
   const int rw = 256 / pl.cw;
   // about four workgroups per compute unit, each with at least kRowsInFlight rows per row lane
@@ -365,16 +310,11 @@ int estimator_moments(hipStream_t st, const RingView& r, int n, const double* w,
                       double* partial, double* acc, int* bad, std::string& err) {
   double* partial_w = partial + (size_t)pl.gx * 2 * r.pitch;
   const dim3 grid(pl.gx, pl.gy), block(256);
-#define MJHMC_EST_LAUNCH(T)                                                                                              \
-  hipLaunchKernelGGL(est_moments_kernel<T>, grid, block, 0, st, (const T*)r.base, w, c, r.Npad, r.N, n, r.D, r.pitch, pl.cw, \
-                     pl.log_cw, partial, partial_w, bad)
-  if (r.dtype == MJHMC_F64)
-    MJHMC_EST_LAUNCH(double);
-  else if (r.dtype == MJHMC_F32)
-    MJHMC_EST_LAUNCH(float);
-  else
-    MJHMC_EST_LAUNCH(__bf16);
-#undef MJHMC_EST_LAUNCH
+  dispatch_dtype(r.dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(est_moments_kernel<T>, grid, block, 0, st, (const T*)r.base, w, c, r.Npad, r.N, n, r.D, r.pitch, pl.cw,
+                       pl.log_cw, partial, partial_w, bad);
+  });
   hipLaunchKernelGGL(est_fold_moments_kernel, dim3((2 * r.D + 1 + 15) / 16), dim3(256), 0, st, partial, partial_w, pl.gx,
                      r.D, r.pitch, acc, bad);
   const hipError_t e = hipGetLastError();
@@ -393,16 +333,11 @@ int estimator_cov(hipStream_t st, const RingView& r, int n, const double* w, con
     return MJHMC_ERR_INVALID;
   }
   const dim3 grid(pl.pairs, pl.splits / 4), block(256);
-#define MJHMC_EST_LAUNCH(T)                                                                                          \
-  hipLaunchKernelGGL(est_cov_kernel<T>, grid, block, 0, st, (const T*)r.base, w, c, r.Npad, r.N, n, r.D, r.pitch, pl.nb, \
-                     pl.splits, partial)
-  if (r.dtype == MJHMC_F64)
-    MJHMC_EST_LAUNCH(double);
-  else if (r.dtype == MJHMC_F32)
-    MJHMC_EST_LAUNCH(float);
-  else
-    MJHMC_EST_LAUNCH(__bf16);
-#undef MJHMC_EST_LAUNCH
+  dispatch_dtype(r.dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(est_cov_kernel<T>, grid, block, 0, st, (const T*)r.base, w, c, r.Npad, r.N, n, r.D, r.pitch, pl.nb,
+                       pl.splits, partial);
+  });
   hipLaunchKernelGGL(est_fold_cov_kernel, dim3((unsigned)(((size_t)pl.pairs * 4096 + 255) / 256)), dim3(256), 0, st, partial,
                      pl.nb, pl.pairs, pl.splits, r.D, C, bad);
   const hipError_t e = hipGetLastError();
@@ -416,60 +351,29 @@ int estimator_cov(hipStream_t st, const RingView& r, int n, const double* w, con
 // ---------------------------------------------------------------------------------------------------------------------
 // The accumulator handle of the C ABI (include/mjhmc_hip.h: mjhmc_estimator_*)
 // ---------------------------------------------------------------------------------------------------------------------
-struct mjhmc_estimator {
-  mjhmc_sampler* s = nullptr;
-  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
+struct mjhmc_estimator : RingAccumulator {
+  using RingAccumulator::RingAccumulator;
   int D = 0;                  // dimensions of a state of that ring
   bool want_cov = false;
-  uint64_t ring_gen = 0;      // that ring at create: the plan and the scratch buffers are sized for it
   EstimatorPlan plan;
   double* acc = nullptr;      // [1 + 2 D]: W, S1, S2
   double* C = nullptr;        // [D][D]
   double* shift = nullptr;    // [D]
   double* mpart = nullptr;
   double* cpart = nullptr;
-  int* bad = nullptr;
-  int64_t n_states = 0;
+  ~mjhmc_estimator() override { free_device({acc, C, shift, mpart, cpart}); }
 };
-
-
-static void estimator_free(mjhmc_estimator* est) {
-  for (void* p : {(void*)est->acc, (void*)est->C, (void*)est->shift, (void*)est->mpart, (void*)est->cpart, (void*)est->bad})
-    if (p) (void)hipFree(p);
-  delete est;
-}
-
-void estimator_free_all(mjhmc_sampler* s) {
-  for (mjhmc_estimator* est : s->estimators) estimator_free(est);
-  s->estimators.clear();
-}
-
-void estimator_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
-  std::vector<mjhmc_estimator*> keep;
-  for (mjhmc_estimator* est : s->estimators) {
-    if (est->fn == f)
-      estimator_free(est);
-    else
-      keep.push_back(est);
-  }
-  s->estimators.swap(keep);
-}
 
 static int estimator_create_on_source(mjhmc_sampler* s, const mjhmc_functionals* fn, int want_cov, mjhmc_estimator** out) {
   const RingSource src = ring_source(s, fn);
-  if (!src.base)
-    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
-                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  if (!src.base) return acc_no_ring(fn);
   if (want_cov && src.D > kEstimatorMaxCovDims)
     return mjhmc_fail(MJHMC_ERR_INVALID, "the covariance pass takes at most " + std::to_string(kEstimatorMaxCovDims) +
                                              " dims (ndims = " + std::to_string(src.D) + "): ask for the moments only");
   HIPCHK(hipSetDevice(s->ctx->device));
-  mjhmc_estimator* est = new mjhmc_estimator();
-  est->s = s;
-  est->fn = fn;
+  mjhmc_estimator* est = new mjhmc_estimator("estimator", "estimator", s, fn, src);
   est->D = src.D;
   est->want_cov = want_cov != 0;
-  est->ring_gen = src.gen;
   est->plan = estimator_plan(ring_source_view(s, src, 0), est->want_cov);
   const size_t D = (size_t)src.D;
   hipError_t e = hipMalloc((void**)&est->acc, (1 + 2 * D) * sizeof(double));
@@ -484,13 +388,11 @@ static int estimator_create_on_source(mjhmc_sampler* s, const mjhmc_functionals*
   if (e == hipSuccess && est->want_cov) e = hipMemsetAsync(est->C, 0, D * D * sizeof(double), s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   if (e != hipSuccess) {
-    estimator_free(est);
+    delete est;
     (void)hipGetLastError();
     return mjhmc_fail(MJHMC_ERR_HIP, std::string("estimator buffers: ") + hipGetErrorString(e));
   }
-  s->estimators.push_back(est);
-  *out = est;
-  return 0;
+  return acc_created(est, out);
 }
 
 extern "C" {
@@ -505,15 +407,7 @@ int mjhmc_estimator_create_on(mjhmc_functionals* f, int want_cov, mjhmc_estimato
   return estimator_create_on_source(functionals_sampler(f), f, want_cov, out);
 }
 
-int mjhmc_estimator_destroy(mjhmc_estimator* est) {
-  if (!est) return 0;
-  mjhmc_sampler* s = est->s;
-  (void)hipSetDevice(s->ctx->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  s->estimators.erase(std::remove(s->estimators.begin(), s->estimators.end(), est), s->estimators.end());
-  estimator_free(est);
-  return 0;
-}
+int mjhmc_estimator_destroy(mjhmc_estimator* est) { return acc_destroy(est); }
 
 int mjhmc_estimator_reset(mjhmc_estimator* est) {
   if (!est) return mjhmc_fail(MJHMC_ERR_INVALID, "estimator is NULL");
@@ -548,35 +442,16 @@ int mjhmc_estimator_set_shift(mjhmc_estimator* est, const double* c) {
 int mjhmc_estimator_accumulate(mjhmc_estimator* est, int x_slot0, int w_slot0, int n) {
   if (!est) return mjhmc_fail(MJHMC_ERR_INVALID, "estimator is NULL");
   mjhmc_sampler* s = est->s;
-  const RingSource src = ring_source(s, est->fn);
-  if (est->ring_gen != src.gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_estimator_create: create a new estimator");
-  if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(src.slots));
-  if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
-    return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots) +
-                                             " (-1 asks for unit weights)");
+  RingSource src;
+  TRY(acc_begin(est, x_slot0, w_slot0, n, &src));
   HIPCHK(hipSetDevice(s->ctx->device));
   const RingView view = ring_source_view(s, src, x_slot0);
-  const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
+  const double* w = acc_weights(est, w_slot0);
   std::string err;
   int rc = estimator_moments(s->stream, view, n, w, est->shift, est->plan, est->mpart, est->acc, est->bad, err);
   if (!rc && est->want_cov) rc = estimator_cov(s->stream, view, n, w, est->shift, est->plan, est->cpart, est->C, est->bad, err);
   if (rc) return mjhmc_fail(rc, err);
-  int bad = 0;
-  HIPCHK(hipMemcpyAsync(&bad, est->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (bad) {
-    HIPCHK(hipMemsetAsync(est->bad, 0, sizeof(int), s->stream));
-    return mjhmc_fail(MJHMC_ERR_NONFINITE, "a dwelling time in dwell slots [" + std::to_string(w_slot0) + ", " +
-                                               std::to_string(w_slot0 + n) +
-                                               ") is not finite (a state whose total jump rate is zero): nothing of this block was added");
-  }
-  est->n_states += (int64_t)n * s->N;
-  return 0;
+  return acc_end(est, n, [&](int) { return acc_nonfinite_dwell(w_slot0, n); });
 }
 
 int mjhmc_estimator_read(mjhmc_estimator* est, double* W, double* S1, double* S2, double* C, int64_t* n_states) {

@@ -160,10 +160,7 @@ void row_geometry(int pitch, int vec, int* chunks, int* cw, int* log_cw, bool* w
 
 void functionals_free(mjhmc_functionals* f) {
   mjhmc_sampler* s = f->s;
-  estimator_free_owned(s, f);
-  chainstats_free_owned(s, f);
-  histogram_free_owned(s, f);
-  pairhist_free_owned(s, f);
+  accumulators_free_owned(s, f);
   for (void* p : {(void*)f->dparams, (void*)f->bad, (void*)f->ring, f->eo_G, f->eo_E, (void*)f->lin_At, (void*)f->lin_b})
     if (p) (void)hipFree(p);
   if (f->module) (void)hipModuleUnload(f->module);
@@ -294,7 +291,7 @@ RingSource functionals_ring_source(const mjhmc_functionals* f) {
 mjhmc_sampler* functionals_sampler(const mjhmc_functionals* f) { return f->s; }
 
 void functionals_free_all(mjhmc_sampler* s) {
-  // (each takes its handles out of the sampler's lists)
+  // (each takes its handles out of the sampler's list)
   for (mjhmc_functionals* f : s->functionals) functionals_free(f);
   s->functionals.clear();
 }

@@ -4,11 +4,11 @@
 // layout [Npad][pitchK]; every estimator of the sample ring then runs on the derived ring unchanged.
 //
 // This header is what hipRTC compiles around the caller's expressions (functionals.hip: functionals_source); it holds
-// device code only and includes nothing of the project.  It is compiled by rtc_compile (user_expr.hip) with the library's
-// own flags, -ffp-contract=off among them: no product is fused into a sum, so an expression built from + - * /,
+// device code only and includes nothing of the project but ring_rows.hpp, which is of the same kind.  It is compiled by
+// rtc_compile (user_expr.hip) with the library's own flags, -ffp-contract=off among them: no product is fused into a sum, so an expression built from + - * /,
 // comparisons and ?: rounds operation by operation, as the same NumPy expression does.  Keep that flag for this kernel.
 //
-// Access shape (that of the moment pass, estimators.hip): a lane owns 16 bytes of a row (2 / 4 / 8 elements); cw = 2^m
+// Access shape (ring_rows.hpp: a lane owns 16 bytes of a row, 2 / 4 / 8 elements, widened by RowChunk<DT>); cw = 2^m
 // <= 64 column lanes form a row group inside one wave.
 //   narrow rows (a row is at most 64 chunks of 16 bytes): one chunk per lane, cw = pow2ceil(chunks); a lane keeps
 //     kFnInFlight rows of its row group in flight (kFnInFlight loads issued before the first is used);
@@ -27,10 +27,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #endif
+#include "ring_rows.hpp"
 
 namespace mjhmc {
 
-constexpr int kFnInFlight = 4;   // 16-byte loads a lane issues before it uses the first
 constexpr int kFnMaxStats = 8;
 constexpr int kFnMaxValues = 16;
 
@@ -41,40 +41,6 @@ struct FunctionalsArgs {
   int n, D, pitch, chunks;   // chunks = pitch / (elements per 16 bytes)
   int cw, log_cw;            // narrow rows: column lanes of a row group
   int* bad;
-};
-
-// 16 bytes of a row -> VEC doubles, widened exactly.  DT: 0 float64, 1 float32, 2 bfloat16 (the MJHMC_* dtype codes)
-template <int DT>
-struct FnChunk;
-template <>
-struct FnChunk<0> {
-  static constexpr int VEC = 2;
-  __device__ static __forceinline__ void widen(const uint4& q, double* v) {
-    v[0] = __longlong_as_double((long long)(((unsigned long long)q.y << 32) | (unsigned long long)q.x));
-    v[1] = __longlong_as_double((long long)(((unsigned long long)q.w << 32) | (unsigned long long)q.z));
-  }
-};
-template <>
-struct FnChunk<1> {
-  static constexpr int VEC = 4;
-  __device__ static __forceinline__ void widen(const uint4& q, double* v) {
-    v[0] = (double)__uint_as_float(q.x);
-    v[1] = (double)__uint_as_float(q.y);
-    v[2] = (double)__uint_as_float(q.z);
-    v[3] = (double)__uint_as_float(q.w);
-  }
-};
-template <>
-struct FnChunk<2> {
-  static constexpr int VEC = 8;
-  __device__ static __forceinline__ void widen(const uint4& q, double* v) {
-    const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = (double)__uint_as_float(u[j] << 16);
-      v[2 * j + 1] = (double)__uint_as_float(u[j] & 0xFFFF0000u);
-    }
-  }
 };
 
 // the butterfly over the cw lanes of a row group (cw a power of two <= 64, groups aligned inside the wave)
@@ -97,7 +63,7 @@ __device__ __forceinline__ void fn_finish(const F& f, double* S, int cx, int cw,
   int nf = 0;
 #pragma unroll
   for (int k = 0; k < K; ++k)
-    if (!(fabs(g[k]) <= 1.7976931348623157e308)) nf |= 1 << k;
+    if (!finite_f64(g[k])) nf |= 1 << k;
 #pragma unroll
   for (int e = 0; e < PK; ++e)
     if ((e & (cw - 1)) == cx) out[e] = g[e];
@@ -108,7 +74,7 @@ __device__ __forceinline__ void fn_finish(const F& f, double* S, int cx, int cw,
 //      void values(const double* S, double* g) const; } -- generated around the caller's expressions
 template <int DT, typename F, bool WIDE>
 __global__ __launch_bounds__(256) void functionals_eval_kernel(FunctionalsArgs a, F f) {
-  constexpr int VEC = FnChunk<DT>::VEC;
+  constexpr int VEC = RowChunk<DT>::VEC;
   constexpr int JS = F::J > 0 ? F::J : 1;
   constexpr int PK = (F::K + 1) / 2 * 2;
   const int tid = threadIdx.x;
@@ -135,7 +101,7 @@ __global__ __launch_bounds__(256) void functionals_eval_kernel(FunctionalsArgs a
         for (int j = 0; j < JS; ++j) S[j] = 0.0;
         if (active) {
           double x[VEC];
-          FnChunk<DT>::widen(q[u], x);
+          RowChunk<DT>::widen(q[u], x);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
             const int d = cx * VEC + e;
@@ -165,7 +131,7 @@ __global__ __launch_bounds__(256) void functionals_eval_kernel(FunctionalsArgs a
           const int c = c0 + 64 * u;
           if (c < a.chunks) {
             double x[VEC];
-            FnChunk<DT>::widen(q[u], x);
+            RowChunk<DT>::widen(q[u], x);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               const int d = c * VEC + e;

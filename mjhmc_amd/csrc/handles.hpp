@@ -86,10 +86,7 @@ struct Shape {
 
 constexpr int kMaxDenseParts = 4;   // free-running parts of a dense batch (iterate_t)
 
-struct mjhmc_estimator;  // weighted-moment accumulator over ring blocks (estimators.hip)
-struct mjhmc_chainstats; // per-chain weighted sums over ring blocks (chainstats.hip)
-struct mjhmc_histogram;  // weighted marginal histograms over ring blocks (histograms.hip)
-struct mjhmc_pairhist;   // weighted joint histograms of pairs of dimensions over ring blocks (pairhist.hip)
+struct RingAccumulator;  // base of the accumulators over ring blocks: mjhmc_estimator, _chainstats, _histogram, _pairhist (ring_source.hpp)
 struct mjhmc_functionals;  // caller expressions g(x) evaluated into a derived ring (functionals.hip)
 struct mjhmc_timegrid;   // the jump process sampled on a uniform time grid, in a grid ring of its own (timegrid.hip)
 struct mjhmc_stein;      // kernel Stein discrepancy of one recorded ensemble (stein.hip)
@@ -156,11 +153,8 @@ struct mjhmc_sampler {
   double* dwell_ring = nullptr;
   int ring_slots = 0;
   uint64_t ring_gen = 0;                      // counts the (re-)allocations of the ring: what an estimator was sized for
-  std::vector<mjhmc_estimator*> estimators;   // accumulators created on this sampler (estimators.hip); freed with it
-  std::vector<mjhmc_chainstats*> chainstats;  // per-chain accumulators created on this sampler (chainstats.hip); freed with it
-  std::vector<mjhmc_histogram*> histograms;   // histogram accumulators created on this sampler (histograms.hip); freed with it
-  std::vector<mjhmc_pairhist*> pairhists;     // pair-histogram accumulators created on this sampler (pairhist.hip); freed with it
-  std::vector<mjhmc_functionals*> functionals;   // functionals created on this sampler (functionals.hip); freed with it, BEFORE the four lists above
+  std::vector<RingAccumulator*> accumulators;   // accumulators created on this sampler or on its functionals (ring_source.hpp); freed with it
+  std::vector<mjhmc_functionals*> functionals;   // functionals created on this sampler (functionals.hip); freed with it, BEFORE the list above
   std::vector<mjhmc_timegrid*> timegrids;     // time grids created on this sampler (timegrid.hip); freed with it
   std::vector<mjhmc_stein*> steins;           // Stein-discrepancy handles created on this sampler (stein.hip); freed with it
   double* stage = nullptr;  // device staging, float64 host layout
@@ -199,19 +193,7 @@ inline size_t ssize(const mjhmc_sampler* s) { return s->dtype == MJHMC_F64 ? 8 :
 inline size_t mat_bytes(const mjhmc_sampler* s) { return (size_t)s->Npad * row_bytes(s); }
 
 
-// estimators.hip
-void estimator_free_all(mjhmc_sampler* s);
-
-// chainstats.hip
-void chainstats_free_all(mjhmc_sampler* s);
-
-// histograms.hip
-void histogram_free_all(mjhmc_sampler* s);
-
-// pairhist.hip
-void pairhist_free_all(mjhmc_sampler* s);
-
-// functionals.hip (frees the accumulator handles created on each, too: call it before the four above)
+// functionals.hip (frees the accumulator handles created on each, too: call it before accumulators_free_all, ring_source.hpp)
 void functionals_free_all(mjhmc_sampler* s);
 
 // timegrid.hip

@@ -20,9 +20,9 @@
 //                       otherwise -- and only when no flag is up -- commits W_units += the block's units
 //   hist_kernel         the pass; returns at its top when a flag is up, so a refused block adds nothing
 //
-// The pass reads the block once with the access shape of the moment pass (estimators.hip): a lane owns 16 bytes of a row
-// (2 / 4 / 8 elements), a workgroup is cw column lanes x 256 / cw row lanes, rows are strided over the workgroups of a
-// strip and kRowsInFlight loads are issued before the first is used.  A workgroup covers a strip of dimensions whose
+// The pass reads the block once with the access shape of the moment pass (ring_rows.hpp: a lane owns 16 bytes of a row):
+// a workgroup is cw column lanes x 256 / cw row lanes, rows are strided over the workgroups of a strip and kRowsInFlight
+// loads are issued before the first is used.  A workgroup covers a strip of dimensions whose
 // private tables -- mass u64 [strip][B + 2], then count u32 [strip][B + 2] -- live in LDS; the strip is the largest power
 // of two whose tables fit kLdsBudget (32 KB: four to five workgroups per compute unit), so 32 dimensions at B = 64, 8 at
 // B = 256, 2 at B = 1024.  Binning is one ds_add_u32 and, for weighted blocks, one ds_add_u64 per element, neither
@@ -41,54 +41,17 @@
 
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
+#include "ring_rows.hpp"
 #include "ring_source.hpp"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kRowsInFlight = 4;          // 16-byte loads a lane issues before it uses the first
 constexpr size_t kLdsBudget = 32768;      // bytes of LDS tables per workgroup
 constexpr int kCheckMaxGy = 64;           // slots the weight check spreads over workgroups
 constexpr u64 kUnitsLimit = 1ull << 63;   // W_units stays below this
 constexpr double kTwo53 = 9007199254740992.0;
-
-// 16 bytes of a row -> VEC doubles, exactly
-template <typename T>
-struct Chunk;
-template <>
-struct Chunk<double> {
-  static constexpr int VEC = 2;
-  typedef double2 Raw;
-  __device__ static void widen(const Raw& q, double* v) {
-    v[0] = q.x;
-    v[1] = q.y;
-  }
-};
-template <>
-struct Chunk<float> {
-  static constexpr int VEC = 4;
-  typedef float4 Raw;
-  __device__ static void widen(const Raw& q, double* v) {
-    v[0] = (double)q.x;
-    v[1] = (double)q.y;
-    v[2] = (double)q.z;
-    v[3] = (double)q.w;
-  }
-};
-template <>
-struct Chunk<__bf16> {
-  static constexpr int VEC = 8;
-  typedef uint4 Raw;
-  __device__ static void widen(const Raw& q, double* v) {
-    const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = (double)__uint_as_float(u[j] << 16);
-      v[2 * j + 1] = (double)__uint_as_float(u[j] & 0xFFFF0000u);
-    }
-  }
-};
 
 __device__ inline u64 add_clamped(u64 a, u64 b) {   // a, b <= 2^63
   const u64 s = a + b;
@@ -105,7 +68,7 @@ __global__ __launch_bounds__(256) void hist_check_kernel(const double* __restric
     const double* wk = w + (size_t)k * Npad;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < N; p += (int64_t)gridDim.x * 256) {
       const double v = wk[p];
-      if (!(v >= 0.0 && v <= 1.7976931348623157e308)) {
+      if (!(v >= 0.0 && finite_f64(v))) {
         flags |= kHistBadNonfinite;
       } else {
         const double r = v * inv_q;   // (= v / q exactly: q is a power of two)
@@ -154,8 +117,7 @@ __global__ __launch_bounds__(256) void hist_kernel(const T* __restrict__ base, c
                                                    int64_t Npad, int64_t N, int n, int D, int pitch, int B, int strip, int cw,
                                                    int log_cw, u64* __restrict__ gcount, u64* __restrict__ gmass,
                                                    const int* __restrict__ bad) {
-  constexpr int VEC = Chunk<T>::VEC;
-  typedef typename Chunk<T>::Raw Raw;
+  constexpr int VEC = ChunkOf<T>::VEC;
   extern __shared__ u64 hist_lds[];
   if (*bad) return;
   const int nb = B + 2, cells = strip * nb;
@@ -189,14 +151,14 @@ __global__ __launch_bounds__(256) void hist_kernel(const T* __restrict__ base, c
     const T* slot = base + (size_t)k * Npad * pitch + col0;
     const double* wk = w ? w + (size_t)k * Npad : nullptr;
     for (int64_t p0 = (int64_t)blockIdx.x * rw + ry; p0 < N; p0 += stride * kRowsInFlight) {
-      Raw q[kRowsInFlight];
+      uint4 q[kRowsInFlight];
       double wt[kRowsInFlight];
 #pragma unroll
       for (int u = 0; u < kRowsInFlight; ++u) {
         const int64_t p = p0 + u * stride;
         wt[u] = 1.0;
         if (p < N && active) {
-          q[u] = *reinterpret_cast<const Raw*>(slot + (size_t)p * pitch);
+          q[u] = *reinterpret_cast<const uint4*>(slot + (size_t)p * pitch);
           if (wk) wt[u] = wk[p];
         }
       }
@@ -205,7 +167,7 @@ __global__ __launch_bounds__(256) void hist_kernel(const T* __restrict__ base, c
         const int64_t p = p0 + u * stride;
         if (p < N && active) {
           double x[VEC];
-          Chunk<T>::widen(q[u], x);
+          ChunkOf<T>::widen(q[u], x);
           const u64 units = wk ? (u64)rint(wt[u] * inv_q) : 0;   // (the check passed: 0 <= w / q < 2^53)
 #pragma unroll
           for (int j = 0; j < VEC; ++j) {
@@ -240,12 +202,6 @@ int pow2floor_i(int64_t v) {
   return p;
 }
 
-int pow2ceil_i(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 }  // namespace
 
 HistogramPlan histogram_plan(const RingView& r, int bins) {
@@ -254,10 +210,9 @@ HistogramPlan histogram_plan(const RingView& r, int bins) {
   pl.bins = bins;
   const size_t per_dim = (size_t)(bins + 2) * (sizeof(u64) + sizeof(uint32_t));
   pl.strip = pow2floor_i(std::max<int64_t>(1, (int64_t)(kLdsBudget / per_dim)));   // (B = 1024: 12 312 bytes per dimension, 2)
-  pl.strip = std::min(pl.strip, std::min(256 * pl.vec, pow2ceil_i(r.D)));
+  pl.strip = std::min(pl.strip, std::min(256 * pl.vec, pow2ceil(r.D)));
   pl.cw = std::max(1, pl.strip / pl.vec);
-  pl.log_cw = 0;
-  while ((1 << pl.log_cw) < pl.cw) ++pl.log_cw;
+  pl.log_cw = ilog2(pl.cw);
   pl.gy = (r.D + pl.strip - 1) / pl.strip;
   const int rw = 256 / pl.cw;
   // about four workgroups per compute unit, each with at least kRowsInFlight rows per row lane
@@ -320,16 +275,11 @@ int histogram_accumulate(hipStream_t st, const RingView& r, int n, const double*
     const int nk = std::min(per_launch, n - k0);
     const char* base = (const char*)r.base + (size_t)k0 * slot_bytes;
     const double* wk = w ? w + (size_t)k0 * r.Npad : nullptr;
-#define MJHMC_HIST_LAUNCH(T)                                                                                               \
-  hipLaunchKernelGGL(hist_kernel<T>, grid, block, pl.lds_bytes, st, (const T*)base, wk, lo, inv, inv_q, r.Npad, r.N, nk, r.D, \
-                     r.pitch, pl.bins, pl.strip, pl.cw, pl.log_cw, count, mass, bad)
-    if (r.dtype == MJHMC_F64)
-      MJHMC_HIST_LAUNCH(double);
-    else if (r.dtype == MJHMC_F32)
-      MJHMC_HIST_LAUNCH(float);
-    else
-      MJHMC_HIST_LAUNCH(__bf16);
-#undef MJHMC_HIST_LAUNCH
+    dispatch_dtype(r.dtype, [&](auto tag) {
+      typedef typename decltype(tag)::type T;
+      hipLaunchKernelGGL(hist_kernel<T>, grid, block, pl.lds_bytes, st, (const T*)base, wk, lo, inv, inv_q, r.Npad, r.N, nk, r.D,
+                         r.pitch, pl.bins, pl.strip, pl.cw, pl.log_cw, count, mass, bad);
+    });
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -342,46 +292,21 @@ int histogram_accumulate(hipStream_t st, const RingView& r, int n, const double*
 // ---------------------------------------------------------------------------------------------------------------------
 // The accumulator handle of the C ABI (include/mjhmc_hip.h: mjhmc_histogram_*)
 // ---------------------------------------------------------------------------------------------------------------------
-struct mjhmc_histogram {
-  mjhmc_sampler* s = nullptr;
-  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
+struct mjhmc_histogram : RingAccumulator {
+  using RingAccumulator::RingAccumulator;
   int D = 0;                  // dimensions of a state of that ring
-  uint64_t ring_gen = 0;      // that ring at create: the plan is sized for it
   HistogramPlan plan;
   double inv_q = 1.0;
   double* range = nullptr;    // [2][D]: lo, inv
   u64* tables = nullptr;      // count [D][B + 2], mass [D][B + 2], W_units
   u64* partial = nullptr;     // the weight check's per-workgroup units
-  int* bad = nullptr;
-  int64_t n_states = 0;
+  ~mjhmc_histogram() override { free_device({range, tables, partial}); }
   size_t cells() const { return (size_t)D * (plan.bins + 2); }
   u64* count() const { return tables; }
   u64* mass() const { return tables + cells(); }
   u64* W_units() const { return tables + 2 * cells(); }
   size_t table_bytes() const { return (2 * cells() + 1) * sizeof(u64); }
 };
-
-static void histogram_free(mjhmc_histogram* h) {
-  for (void* p : {(void*)h->range, (void*)h->tables, (void*)h->partial, (void*)h->bad})
-    if (p) (void)hipFree(p);
-  delete h;
-}
-
-void histogram_free_all(mjhmc_sampler* s) {
-  for (mjhmc_histogram* h : s->histograms) histogram_free(h);
-  s->histograms.clear();
-}
-
-void histogram_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
-  std::vector<mjhmc_histogram*> keep;
-  for (mjhmc_histogram* h : s->histograms) {
-    if (h->fn == f)
-      histogram_free(h);
-    else
-      keep.push_back(h);
-  }
-  s->histograms.swap(keep);
-}
 
 // have: the sampler or the functionals handle was given (s itself is looked at only after the argument checks that need none)
 static int histogram_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_functionals* fn, int n_bins, const double* lo,
@@ -410,19 +335,14 @@ static int histogram_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_f
     range[d] = lo[d];
     range[(size_t)D + d] = inv;
   }
-  if (!src.base)
-    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
-                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  if (!src.base) return acc_no_ring(fn);
   // the pass addresses a row in 16-byte chunks of the state's own type: rows must be whole chunks of it
   const int vec = src.dtype == MJHMC_F64 ? 2 : (src.dtype == MJHMC_F32 ? 4 : 8);
   if (src.esize * vec != 16 || src.pitch % vec != 0)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows are not whole 16-byte chunks of its state type");
   HIPCHK(hipSetDevice(s->ctx->device));
-  mjhmc_histogram* h = new mjhmc_histogram();
-  h->s = s;
-  h->fn = fn;
+  mjhmc_histogram* h = new mjhmc_histogram("histogram", "histogram", s, fn, src);
   h->D = D;
-  h->ring_gen = src.gen;
   h->inv_q = inv_q;
   h->plan = histogram_plan(ring_source_view(s, src, 0), n_bins);
   const size_t partial_bytes = (size_t)h->plan.check_gx * h->plan.check_gy * sizeof(u64);
@@ -436,13 +356,11 @@ static int histogram_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_f
   if (e == hipSuccess) e = hipMemsetAsync(h->bad, 0, sizeof(int), s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);   // (range is this call's)
   if (e != hipSuccess) {
-    histogram_free(h);
+    delete h;
     (void)hipGetLastError();
     return mjhmc_fail(MJHMC_ERR_HIP, std::string("histogram buffers: ") + hipGetErrorString(e));
   }
-  s->histograms.push_back(h);
-  *out = h;
-  return 0;
+  return acc_created(h, out);
 }
 
 extern "C" {
@@ -457,15 +375,7 @@ int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo
   return histogram_create_on_source(f != nullptr, nullptr, f, n_bins, lo, hi, quantum, out);
 }
 
-int mjhmc_histogram_destroy(mjhmc_histogram* h) {
-  if (!h) return 0;
-  mjhmc_sampler* s = h->s;
-  (void)hipSetDevice(s->ctx->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  s->histograms.erase(std::remove(s->histograms.begin(), s->histograms.end(), h), s->histograms.end());
-  histogram_free(h);
-  return 0;
-}
+int mjhmc_histogram_destroy(mjhmc_histogram* h) { return acc_destroy(h); }
 
 int mjhmc_histogram_reset(mjhmc_histogram* h) {
   if (!h) return mjhmc_fail(MJHMC_ERR_INVALID, "histogram is NULL");
@@ -480,34 +390,17 @@ int mjhmc_histogram_reset(mjhmc_histogram* h) {
 int mjhmc_histogram_accumulate(mjhmc_histogram* h, int x_slot0, int w_slot0, int n) {
   if (!h) return mjhmc_fail(MJHMC_ERR_INVALID, "histogram is NULL");
   mjhmc_sampler* s = h->s;
-  const RingSource src = ring_source(s, h->fn);
-  if (h->ring_gen != src.gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_histogram_create: create a new histogram");
-  if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(src.slots));
-  if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
-    return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots) +
-                                             " (-1 asks for unit weights)");
+  RingSource src;
+  TRY(acc_begin(h, x_slot0, w_slot0, n, &src));
   if (w_slot0 < 0 && !(h->inv_q < kTwo53))
     return mjhmc_fail(MJHMC_ERR_INVALID, "a unit weight is 2^53 quanta or more: w / quantum must stay below 2^53");
   HIPCHK(hipSetDevice(s->ctx->device));
-  const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
+  const double* w = acc_weights(h, w_slot0);
   std::string err;
   const int rc = histogram_accumulate(s->stream, ring_source_view(s, src, x_slot0), n, w, h->range, h->range + h->D, h->inv_q, h->plan,
                                       h->partial, h->count(), h->mass(), h->W_units(), h->bad, err);
   if (rc) return mjhmc_fail(rc, err);
-  int bad = 0;
-  HIPCHK(hipMemcpyAsync(&bad, h->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (bad) {
-    HIPCHK(hipMemsetAsync(h->bad, 0, sizeof(int), s->stream));
-    return histogram_refusal(bad, w_slot0, n);
-  }
-  h->n_states += (int64_t)n * s->N;
-  return 0;
+  return acc_end(h, n, [&](int bad) { return histogram_refusal(bad, w_slot0, n); });
 }
 
 int mjhmc_histogram_read(mjhmc_histogram* h, uint64_t* count, uint64_t* mass, uint64_t* W_units, int64_t* n_states) {

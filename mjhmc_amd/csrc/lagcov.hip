@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/mjhmc_hip.h"
+#include "ring_source.hpp"   // dispatch_dtype
 
 namespace {
 
@@ -222,9 +223,9 @@ int lagcov_from_ring(hipStream_t st, const RingView& r, int n, int K, const doub
   for (int k0 = 0; k0 <= K; k0 += kBand) {
     const bool first = k0 == 0;
     const dim3 grid((unsigned)gx, (unsigned)gy);
-    if (r.dtype == MJHMC_F64) launch_pass<double>(st, grid, first, r, n, k0, dpw_log2, (const double*)dshift.p, (double*)partial.p, Dp);
-    else if (r.dtype == MJHMC_F32) launch_pass<float>(st, grid, first, r, n, k0, dpw_log2, (const double*)dshift.p, (double*)partial.p, Dp);
-    else launch_pass<__bf16>(st, grid, first, r, n, k0, dpw_log2, (const double*)dshift.p, (double*)partial.p, Dp);
+    dispatch_dtype(r.dtype, [&](auto tag) {
+      launch_pass<typename decltype(tag)::type>(st, grid, first, r, n, k0, dpw_log2, (const double*)dshift.p, (double*)partial.p, Dp);
+    });
     LCHK(hipGetLastError());
     const int nk = std::min(kBand, K + 1 - k0);
     const int cells = (nk + (first ? 1 : 0)) * r.D;

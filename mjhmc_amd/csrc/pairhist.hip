@@ -39,6 +39,7 @@
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
 #include "histograms.hpp"
+#include "ring_rows.hpp"
 #include "ring_source.hpp"
 
 namespace {
@@ -47,11 +48,6 @@ typedef unsigned long long u64;
 
 constexpr int kStatesInFlight = 4;        // states of a row whose loads a lane issues before it uses the first
 constexpr double kTwo53 = 9007199254740992.0;
-
-// a stored element -> float64, exactly
-__device__ inline double widen(double v) { return v; }
-__device__ inline double widen(float v) { return (double)v; }
-__device__ inline double widen(uint16_t v) { return (double)__uint_as_float((uint32_t)v << 16); }   // bfloat16
 
 __device__ inline int pairhist_bin(double x, double lo, double inv, int B, double Bd) {
   const double d = x - lo;
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(256) void pairhist_kernel(const S* __restrict__ bas
 #pragma unroll
         for (int u = 0; u < kStatesInFlight; ++u) {
           if (k0 + u < n) {
-            const int c = pairhist_cell(widen(xi[u]), widen(xj[u]), lo0, inv0, lo1, inv1, B, Bd);
+            const int c = pairhist_cell(elem_to_f64(xi[u]), elem_to_f64(xj[u]), lo0, inv0, lo1, inv1, B, Bd);
             const u64 units = w ? (u64)rint(wt[u] * inv_q) : unit;   // (the check passed: 0 <= w / q < 2^53)
             if (LDS) {
               atomicAdd(&lcount[g * cells + c], 1u);
@@ -174,24 +170,12 @@ int pairhist_accumulate(hipStream_t st, const RingView& r, int n, const double* 
     const int nk = std::min(per_launch, n - k0);
     const char* base = (const char*)r.base + (size_t)k0 * slot_bytes;
     const double* wk = w ? w + (size_t)k0 * r.Npad : nullptr;
-#define MJHMC_PAIRHIST_LAUNCH(S, LDS)                                                                                     \
-  hipLaunchKernelGGL((pairhist_kernel<S, LDS>), grid, block, pl.lds_bytes, st, (const S*)base, wk, pairs, range, inv_q,  \
-                     r.Npad, r.N, nk, r.pitch, pl.bins, pl.n_pairs, pl.group, count, mass, bad)
-#define MJHMC_PAIRHIST_FORM(S) \
-  do {                         \
-    if (pl.lds)                \
-      MJHMC_PAIRHIST_LAUNCH(S, true);  \
-    else                       \
-      MJHMC_PAIRHIST_LAUNCH(S, false); \
-  } while (0)
-    if (r.dtype == MJHMC_F64)
-      MJHMC_PAIRHIST_FORM(double);
-    else if (r.dtype == MJHMC_F32)
-      MJHMC_PAIRHIST_FORM(float);
-    else
-      MJHMC_PAIRHIST_FORM(uint16_t);
-#undef MJHMC_PAIRHIST_FORM
-#undef MJHMC_PAIRHIST_LAUNCH
+    dispatch_dtype(r.dtype, [&](auto tag) {
+      typedef typename ElemBits<typename decltype(tag)::type>::type S;   // (bfloat16 is loaded as its 16 bits)
+      const auto kernel = pl.lds ? pairhist_kernel<S, true> : pairhist_kernel<S, false>;
+      hipLaunchKernelGGL(kernel, grid, block, pl.lds_bytes, st, (const S*)base, wk, pairs, range, inv_q, r.Npad, r.N, nk,
+                         r.pitch, pl.bins, pl.n_pairs, pl.group, count, mass, bad);
+    });
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -204,46 +188,21 @@ int pairhist_accumulate(hipStream_t st, const RingView& r, int n, const double* 
 // ---------------------------------------------------------------------------------------------------------------------
 // The accumulator handle of the C ABI (include/mjhmc_hip.h: mjhmc_pairhist_*)
 // ---------------------------------------------------------------------------------------------------------------------
-struct mjhmc_pairhist {
-  mjhmc_sampler* s = nullptr;
-  const mjhmc_functionals* fn = nullptr;   // whose derived ring the states come from; nullptr: the sampler's own ring
-  uint64_t ring_gen = 0;      // that ring at create: the pairs were checked against its dimensions
+struct mjhmc_pairhist : RingAccumulator {   // (ring_gen: the pairs were checked against that ring's dimensions)
+  using RingAccumulator::RingAccumulator;
   PairhistPlan plan;
   double inv_q = 1.0;
   int32_t* pairs = nullptr;   // [P][2]
   double* range = nullptr;    // [P][4]: lo_i, inv_i, lo_j, inv_j
   u64* tables = nullptr;      // count [P][B + 2][B + 2], mass [P][B + 2][B + 2], W_units
   u64* partial = nullptr;     // the weight check's per-workgroup units
-  int* bad = nullptr;
-  int64_t n_states = 0;
+  ~mjhmc_pairhist() override { free_device({pairs, range, tables, partial}); }
   size_t cells() const { return (size_t)plan.n_pairs * plan.cells; }
   u64* count() const { return tables; }
   u64* mass() const { return tables + cells(); }
   u64* W_units() const { return tables + 2 * cells(); }
   size_t table_bytes() const { return (2 * cells() + 1) * sizeof(u64); }
 };
-
-static void pairhist_free(mjhmc_pairhist* h) {
-  for (void* p : {(void*)h->pairs, (void*)h->range, (void*)h->tables, (void*)h->partial, (void*)h->bad})
-    if (p) (void)hipFree(p);
-  delete h;
-}
-
-void pairhist_free_all(mjhmc_sampler* s) {
-  for (mjhmc_pairhist* h : s->pairhists) pairhist_free(h);
-  s->pairhists.clear();
-}
-
-void pairhist_free_owned(mjhmc_sampler* s, const mjhmc_functionals* f) {
-  std::vector<mjhmc_pairhist*> keep;
-  for (mjhmc_pairhist* h : s->pairhists) {
-    if (h->fn == f)
-      pairhist_free(h);
-    else
-      keep.push_back(h);
-  }
-  s->pairhists.swap(keep);
-}
 
 // have: the sampler or the functionals handle was given (s itself is looked at only after the argument checks that need none)
 static int pairhist_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_functionals* fn, int n_pairs, const int32_t* pairs,
@@ -282,19 +241,14 @@ static int pairhist_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_fu
       range[4 * (size_t)p + 2 * a + 1] = inv;
     }
   }
-  if (!src.base)
-    return mjhmc_fail(MJHMC_ERR_INVALID, fn ? "the functionals have no derived ring yet (call mjhmc_functionals_ring_alloc first)"
-                                            : "the sampler has no sample ring yet (call mjhmc_ring_alloc first)");
+  if (!src.base) return acc_no_ring(fn);
   // the pass loads single elements of the state's own type
   if (src.esize != (src.dtype == MJHMC_F64 ? 8 : (src.dtype == MJHMC_F32 ? 4 : 2)) || src.pitch < D)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the ring's rows do not store elements of its state type");
   if (s->N >= (1ll << 32))
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the pair-histogram pass counts a workgroup's states per cell in 32 bits: fewer than 2^32 particles");
   HIPCHK(hipSetDevice(s->ctx->device));
-  mjhmc_pairhist* h = new mjhmc_pairhist();
-  h->s = s;
-  h->fn = fn;
-  h->ring_gen = src.gen;
+  mjhmc_pairhist* h = new mjhmc_pairhist("pairhist", "pair histogram", s, fn, src);
   h->inv_q = inv_q;
   h->plan = pairhist_plan(s->N, n_bins, n_pairs);
   const size_t partial_bytes = (size_t)h->plan.check_gx * h->plan.check_gy * sizeof(u64);
@@ -311,13 +265,11 @@ static int pairhist_create_on_source(bool have, mjhmc_sampler* s, const mjhmc_fu
   if (e == hipSuccess) e = hipMemsetAsync(h->bad, 0, sizeof(int), s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);   // (pairs and range are this call's)
   if (e != hipSuccess) {
-    pairhist_free(h);
+    delete h;
     (void)hipGetLastError();
     return mjhmc_fail(MJHMC_ERR_HIP, std::string("pair-histogram buffers: ") + hipGetErrorString(e));
   }
-  s->pairhists.push_back(h);
-  *out = h;
-  return 0;
+  return acc_created(h, out);
 }
 
 extern "C" {
@@ -332,15 +284,7 @@ int mjhmc_pairhist_create_on(mjhmc_functionals* f, int n_pairs, const int32_t* p
   return pairhist_create_on_source(f != nullptr, nullptr, f, n_pairs, pairs, n_bins, lo, hi, quantum, out);
 }
 
-int mjhmc_pairhist_destroy(mjhmc_pairhist* h) {
-  if (!h) return 0;
-  mjhmc_sampler* s = h->s;
-  (void)hipSetDevice(s->ctx->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  s->pairhists.erase(std::remove(s->pairhists.begin(), s->pairhists.end(), h), s->pairhists.end());
-  pairhist_free(h);
-  return 0;
-}
+int mjhmc_pairhist_destroy(mjhmc_pairhist* h) { return acc_destroy(h); }
 
 int mjhmc_pairhist_reset(mjhmc_pairhist* h) {
   if (!h) return mjhmc_fail(MJHMC_ERR_INVALID, "pair histogram is NULL");
@@ -355,34 +299,17 @@ int mjhmc_pairhist_reset(mjhmc_pairhist* h) {
 int mjhmc_pairhist_accumulate(mjhmc_pairhist* h, int x_slot0, int w_slot0, int n) {
   if (!h) return mjhmc_fail(MJHMC_ERR_INVALID, "pair histogram is NULL");
   mjhmc_sampler* s = h->s;
-  const RingSource src = ring_source(s, h->fn);
-  if (h->ring_gen != src.gen)
-    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + src.name() + " was re-allocated after mjhmc_pairhist_create: create a new pair histogram");
-  if (n < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "n must be >= 1");
-  if (x_slot0 < 0 || (int64_t)x_slot0 + n > src.slots)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "state slots [" + std::to_string(x_slot0) + ", " + std::to_string((int64_t)x_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(src.slots));
-  if (w_slot0 < -1 || (w_slot0 >= 0 && (int64_t)w_slot0 + n > s->ring_slots))
-    return mjhmc_fail(MJHMC_ERR_INVALID, "dwell slots [" + std::to_string(w_slot0) + ", " + std::to_string((int64_t)w_slot0 + n) +
-                                             ") are outside the ring of " + std::to_string(s->ring_slots) +
-                                             " (-1 asks for unit weights)");
+  RingSource src;
+  TRY(acc_begin(h, x_slot0, w_slot0, n, &src));
   if (w_slot0 < 0 && !(h->inv_q < kTwo53))
     return mjhmc_fail(MJHMC_ERR_INVALID, "a unit weight is 2^53 quanta or more: w / quantum must stay below 2^53");
   HIPCHK(hipSetDevice(s->ctx->device));
-  const double* w = w_slot0 >= 0 ? s->dwell_ring + (size_t)w_slot0 * s->Npad : nullptr;
+  const double* w = acc_weights(h, w_slot0);
   std::string err;
   const int rc = pairhist_accumulate(s->stream, ring_source_view(s, src, x_slot0), n, w, h->pairs, h->range, h->inv_q, h->plan,
                                      h->partial, h->count(), h->mass(), h->W_units(), h->bad, err);
   if (rc) return mjhmc_fail(rc, err);
-  int bad = 0;
-  HIPCHK(hipMemcpyAsync(&bad, h->bad, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (bad) {
-    HIPCHK(hipMemsetAsync(h->bad, 0, sizeof(int), s->stream));
-    return histogram_refusal(bad, w_slot0, n);
-  }
-  h->n_states += (int64_t)n * s->N;
-  return 0;
+  return acc_end(h, n, [&](int bad) { return histogram_refusal(bad, w_slot0, n); });
 }
 
 int mjhmc_pairhist_read(mjhmc_pairhist* h, uint64_t* count, uint64_t* mass, uint64_t* W_units, int64_t* n_states) {

@@ -2,7 +2,7 @@
 //     u[p][k] = b[k] + sum_{d < ndims} A[k][d] * x[p][d]        g[p][k] = link(u[p][k], k; params)   (identity: g = u)
 // written as rows of the DERIVED ring of a mjhmc_functionals (functionals.hip), so that every accumulator of the sample
 // ring runs on them unchanged.  projections_kernel below is a small GEMM over ring slots: n slots x N particles x K
-// values, the rows float64, float32 or bfloat16 and widened exactly with FnChunk<DT> (functionals.hpp).
+// values, the rows float64, float32 or bfloat16 and widened exactly with RowChunk<DT> (ring_rows.hpp).
 //
 // This header is also what hipRTC compiles around a caller's link expression (projections.hip: link_source): device code
 // only, nothing of the project but functionals.hpp.  It is compiled with the library's own flags, -ffp-contract=off among
@@ -72,7 +72,7 @@ __host__ __device__ constexpr int proj_lane_values(int K) { return K <= 16 ? 1 :
 // L: { const double* p; double apply(double u, int k) const; } -- ProjIdentity, or generated around the caller's expression
 template <int DT, int KV, typename L>
 __global__ __launch_bounds__(256) void projections_kernel(ProjArgs a, L link) {
-  constexpr int VEC = FnChunk<DT>::VEC;
+  constexpr int VEC = RowChunk<DT>::VEC;
   constexpr int DC = 8 * VEC;                       // elements of a d chunk: 128 bytes of a row
   constexpr int TK = 16 * KV;
   constexpr int XS = kProjRows + kProjRowPad;
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void projections_kernel(ProjArgs a, L link) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           double v[VEC];
-          FnChunk<DT>::widen(qx[h], v);
+          RowChunk<DT>::widen(qx[h], v);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) Xs[(lc * VEC + e) * XS + lr + 32 * h] = v[e];
         }
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void projections_kernel(ProjArgs a, L link) {
           g[j] = 0.0;
           if (k < a.K) {
             g[j] = link.apply(acc[i][j], k);
-            if (!(fabs(g[j]) <= 1.7976931348623157e308) && k < badk) badk = k;
+            if (!finite_f64(g[j]) && k < badk) badk = k;
           }
         }
         double* row = out + (size_t)p * a.pitchK + k0 + tx * KV;

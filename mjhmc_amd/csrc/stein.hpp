@@ -42,6 +42,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ring_rows.hpp"
+
 namespace mjhmc {
 
 constexpr int kSteinTile = 64;      // particles per tile side
@@ -91,15 +93,13 @@ __device__ __forceinline__ void stein_load4(const void* __restrict__ base, long 
     const unsigned short* r = reinterpret_cast<const unsigned short*>(base) + (size_t)row * pitch;
     if (d0 < D) {
       const uint2 q = *reinterpret_cast<const uint2*>(r + d0);
-      v[0] = (double)__uint_as_float(q.x << 16);
-      if (d0 + 1 < D) v[1] = (double)__uint_as_float(q.x & 0xFFFF0000u);
-      if (d0 + 2 < D) v[2] = (double)__uint_as_float(q.y << 16);
-      if (d0 + 3 < D) v[3] = (double)__uint_as_float(q.y & 0xFFFF0000u);
+      v[0] = bf16_to_f64(q.x & 0xFFFFu);
+      if (d0 + 1 < D) v[1] = bf16_to_f64(q.x >> 16);
+      if (d0 + 2 < D) v[2] = bf16_to_f64(q.y & 0xFFFFu);
+      if (d0 + 3 < D) v[3] = bf16_to_f64(q.y >> 16);
     }
   }
 }
-
-__device__ __forceinline__ bool stein_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 #pragma clang fp contract(off)
 // wave butterfly, then the four wave totals through LDS, added in order; every thread passes its value and gets the total
@@ -163,8 +163,8 @@ __global__ __launch_bounds__(256) void stein_pair_kernel(SteinArgs a) {
     if (diag) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (!stein_finite(nx[0][e])) nf |= kSteinBadState;
-        if (!stein_finite(nx[1][e])) nf |= kSteinBadGrad;
+        if (!finite_f64(nx[0][e])) nf |= kSteinBadState;
+        if (!finite_f64(nx[1][e])) nf |= kSteinBadGrad;
       }
     }
     __syncthreads();
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void stein_finish_kernel(SteinArgs a) {
   int nf = 0;
   for (long long p = tid; p < a.n_use; p += 256) {
     const double w = a.w ? a.w[p] : 1.0;
-    if (!stein_finite(w)) nf |= kSteinBadWeight;
+    if (!finite_f64(w)) nf |= kSteinBadWeight;
     w1 = w1 + w;
     w2 = w2 + w * w;
   }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void stein_finish_kernel(SteinArgs a) {
   w1 = stein_block_sum(w1, red);
   w2 = stein_block_sum(w2, red);
   if (tid == 0) {
-    if (!stein_finite(s) || !stein_finite(sd) || !stein_finite(w2)) nf |= kSteinBadSum;
+    if (!finite_f64(s) || !finite_f64(sd) || !finite_f64(w2)) nf |= kSteinBadSum;
     a.out[0] = w1;
     a.out[1] = w2;
     a.out[2] = s;

@@ -43,10 +43,9 @@
 #include "../../include/mjhmc_hip.h"
 #include "handles.hpp"
 #include "lagcov.hpp"
+#include "ring_rows.hpp"
 
 namespace {
-
-constexpr int kSlotsInFlight = 4;   // 16-byte loads a lane issues before it uses the first
 
 // any weight among w[k * Npad + p], k < n, p < N that is not finite or is negative
 __global__ __launch_bounds__(256) void tg_check_kernel(const double* __restrict__ w, int64_t Npad, int64_t N, int n,
@@ -56,7 +55,7 @@ __global__ __launch_bounds__(256) void tg_check_kernel(const double* __restrict_
     const double* wk = w + (size_t)k * Npad;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < N; p += (int64_t)gridDim.x * 256) {
       const double v = wk[p];
-      if (!(v >= 0.0 && v <= 1.7976931348623157e308)) flag = 1;
+      if (!(v >= 0.0 && finite_f64(v))) flag = 1;
     }
   }
   if (flag) *bad = 1;

@@ -482,21 +482,60 @@ class DeviceSampler(object):
             pass
 
 
-class DeviceEstimator(object):
+class _RingAccumulator(object):
+    """What DeviceEstimator, DeviceChainStats, DeviceHistogram and DevicePairHistogram share: the handle created on the
+    sampler's ring or, with ``on``, on the derived ring of a DeviceFunctionals, ``reset`` and ``close``.  ``_kind`` names
+    the mjhmc_<kind>_* entry points."""
+    _kind = None
+
+    def _create(self, dev, on, *args):
+        """mjhmc_<kind>_create(dev, *args, &handle), or mjhmc_<kind>_create_on(on, *args, &handle)"""
+        self.dev, self.lib, self.on = dev, dev.lib, on
+        h = ctypes.c_void_p()
+        create = getattr(self.lib, 'mjhmc_%s_create%s' % (self._kind, '' if on is None else '_on'))
+        check(create((dev if on is None else on).handle, *(args + (ctypes.byref(h),))), self.lib)
+        self.handle = h
+
+    def _call(self, name, *args):
+        check(getattr(self.lib, 'mjhmc_%s_%s' % (self._kind, name))(self.handle, *args), self.lib)
+
+    def reset(self):
+        self._call('reset')
+
+    def close(self):
+        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
+                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
+            getattr(self.lib, 'mjhmc_%s_destroy' % self._kind)(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _RingHistogram(_RingAccumulator):
+    """accumulate of the two histogram handles"""
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A refused block (a weight that is not finite, negative
+        or too large for the quantum) raises and adds nothing."""
+        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
+
+
+class DeviceEstimator(_RingAccumulator):
     """W = sum w, S1 = sum w (x - c), S2 = sum w (x - c)^2 and, with ``want_cov``, C = sum w (x - c)(x - c)^T over the
     (slot, particle) states of the ring blocks given to ``accumulate``; float64 throughout, bit-identical from run to run."""
+    _kind = 'estimator'
 
     def __init__(self, dev, want_cov=False, on=None):
         """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (its K values are the
         dimensions; x_slot0 then counts derived slots, w_slot0 still the sampler's dwell slots)"""
-        self.dev, self.lib, self.want_cov, self.on = dev, dev.lib, bool(want_cov), on
+        self.want_cov = bool(want_cov)
         self.ndims = dev.ndims if on is None else on.n_values
-        h = ctypes.c_void_p()
-        if on is None:
-            check(self.lib.mjhmc_estimator_create(dev.handle, 1 if want_cov else 0, ctypes.byref(h)), self.lib)
-        else:
-            check(self.lib.mjhmc_estimator_create_on(on.handle, 1 if want_cov else 0, ctypes.byref(h)), self.lib)
-        self.handle = h
+        self._create(dev, on, 1 if want_cov else 0)
 
     def set_shift(self, c=None):
         c = None if c is None else as_f64(np.asarray(c, dtype=np.float64).reshape(-1), (self.ndims,))
@@ -516,37 +555,18 @@ class DeviceEstimator(object):
         check(self.lib.mjhmc_estimator_read(self.handle, ctypes.byref(W), ptr(S1), ptr(S2), ptr(C), ctypes.byref(n)), self.lib)
         return W.value, S1, S2, C, int(n.value)
 
-    def reset(self):
-        check(self.lib.mjhmc_estimator_reset(self.handle), self.lib)
 
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
-                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
-            self.lib.mjhmc_estimator_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceChainStats(object):
+class DeviceChainStats(_RingAccumulator):
     """Per chain (particle) p and part h: a0 = sum_k w, a1 = sum_k w (x - c), a2 = sum_k w (x - c)^2 over the states
     of the ring blocks given to ``accumulate``, in float64 and in a fixed operation order (include/mjhmc_hip.h:
     mjhmc_chainstats_accumulate): bit-identical to the same float64 operations on the host, whatever the blocks."""
+    _kind = 'chainstats'
 
     def __init__(self, dev, n_parts=1, on=None):
         """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
-        self.dev, self.lib, self.n_parts, self.on = dev, dev.lib, int(n_parts), on
+        self.n_parts = int(n_parts)
         self.ndims, self.nparticles = (dev.ndims if on is None else on.n_values), dev.nparticles
-        h = ctypes.c_void_p()
-        if on is None:
-            check(self.lib.mjhmc_chainstats_create(dev.handle, self.n_parts, ctypes.byref(h)), self.lib)
-        else:
-            check(self.lib.mjhmc_chainstats_create_on(on.handle, self.n_parts, ctypes.byref(h)), self.lib)
-        self.handle = h
+        self._create(dev, on, self.n_parts)
 
     def set_shift(self, c=None):
         c = None if c is None else as_f64(np.asarray(c, dtype=np.float64).reshape(-1), (self.ndims,))
@@ -575,48 +595,20 @@ class DeviceChainStats(object):
         check(self.lib.mjhmc_chainstats_read_chains(self.handle, int(part), ptr(a0), ptr(a1), ptr(a2)), self.lib)
         return a0, a1, a2
 
-    def reset(self):
-        check(self.lib.mjhmc_chainstats_reset(self.handle), self.lib)
 
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
-                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
-            self.lib.mjhmc_chainstats_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceHistogram(object):
+class DeviceHistogram(_RingHistogram):
     """Per dimension d and bin b: count[d][b] states and mass[d][b] = sum of rint(w / quantum) over the (slot, particle)
     states of the ring blocks given to ``accumulate`` whose element x_d falls into bin b -- b = 0 below ``lo`` (and NaN),
     bins + 1 from ``hi`` on, 1 + int((x - lo) * (bins / (hi - lo))) between (include/mjhmc_hip.h: mjhmc_histogram_create).
     Integer sums: bit-identical from run to run, whatever the blocks."""
+    _kind = 'histogram'
 
     def __init__(self, dev, bins, lo, hi, quantum=1.0, on=None):
         """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
-        self.dev, self.lib, self.on = dev, dev.lib, on
         self.ndims, self.bins, self.quantum = (dev.ndims if on is None else on.n_values), int(bins), float(quantum)
         self.lo = as_f64(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.ndims,)))
         self.hi = as_f64(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.ndims,)))
-        h = ctypes.c_void_p()
-        if on is None:
-            check(self.lib.mjhmc_histogram_create(dev.handle, self.bins, ptr(self.lo), ptr(self.hi), self.quantum,
-                                                  ctypes.byref(h)), self.lib)
-        else:
-            check(self.lib.mjhmc_histogram_create_on(on.handle, self.bins, ptr(self.lo), ptr(self.hi), self.quantum,
-                                                     ctypes.byref(h)), self.lib)
-        self.handle = h
-
-    def accumulate(self, x_slot0, n, w_slot0=-1):
-        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A refused block (a weight that is not finite, negative
-        or too large for the quantum) raises and adds nothing."""
-        check(self.lib.mjhmc_histogram_accumulate(self.handle, int(x_slot0), int(w_slot0), int(n)), self.lib)
+        self._create(dev, on, self.bins, ptr(self.lo), ptr(self.hi), self.quantum)
 
     def read(self):
         """(count (D, bins + 2) uint64, mass (D, bins + 2) uint64 in units of the quantum, W_units, n_states)"""
@@ -625,21 +617,6 @@ class DeviceHistogram(object):
         W, n = ctypes.c_uint64(), ctypes.c_int64()
         check(self.lib.mjhmc_histogram_read(self.handle, ptr(count), ptr(mass), ctypes.byref(W), ctypes.byref(n)), self.lib)
         return count, mass, int(W.value), int(n.value)
-
-    def reset(self):
-        check(self.lib.mjhmc_histogram_reset(self.handle), self.lib)
-
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
-                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
-            self.lib.mjhmc_histogram_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DeviceTimeGrid(object):
@@ -742,31 +719,21 @@ class DeviceStein(object):
             pass
 
 
-class DevicePairHistogram(object):
+class DevicePairHistogram(_RingHistogram):
     """Per pair p = (i, j) and cell (b_j, b_i): count[p][b_j][b_i] states and mass[p][b_j][b_i] = sum of rint(w / quantum)
     over the (slot, particle) states of the ring blocks given to ``accumulate`` whose elements x_i, x_j fall into bins b_i,
     b_j of their axes -- per axis the bins of DeviceHistogram (include/mjhmc_hip.h: mjhmc_pairhist_create).  Integer sums:
     bit-identical from run to run, whatever the blocks."""
+    _kind = 'pairhist'
 
     def __init__(self, dev, pairs, bins, lo, hi, quantum=1.0, on=None):
         """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
-        self.dev, self.lib, self.on = dev, dev.lib, on
         self.ndims, self.bins, self.quantum = (dev.ndims if on is None else on.n_values), int(bins), float(quantum)
         self.pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
         self.n_pairs = P = self.pairs.shape[0]
         self.lo = as_f64(np.broadcast_to(np.asarray(lo, dtype=np.float64), (P, 2)))
         self.hi = as_f64(np.broadcast_to(np.asarray(hi, dtype=np.float64), (P, 2)))
-        h = ctypes.c_void_p()
-        create, src = (self.lib.mjhmc_pairhist_create, dev) if on is None else (self.lib.mjhmc_pairhist_create_on, on)
-        check(create(src.handle, P, ptr(self.pairs), self.bins, ptr(self.lo), ptr(self.hi), self.quantum, ctypes.byref(h)),
-              self.lib)
-        self.handle = h
-
-    def accumulate(self, x_slot0, n, w_slot0=-1):
-        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A refused block (a weight that is not finite, negative
-        or too large for the quantum) raises and adds nothing."""
-        check(self.lib.mjhmc_pairhist_accumulate(self.handle, int(x_slot0), int(w_slot0), int(n)), self.lib)
+        self._create(dev, on, P, ptr(self.pairs), self.bins, ptr(self.lo), ptr(self.hi), self.quantum)
 
     def read(self):
         """(count (P, bins + 2, bins + 2) uint64, mass likewise in units of the quantum, W_units, n_states); the last
@@ -776,21 +743,6 @@ class DevicePairHistogram(object):
         W, n = ctypes.c_uint64(), ctypes.c_int64()
         check(self.lib.mjhmc_pairhist_read(self.handle, ptr(count), ptr(mass), ctypes.byref(W), ctypes.byref(n)), self.lib)
         return count, mass, int(W.value), int(n.value)
-
-    def reset(self):
-        check(self.lib.mjhmc_pairhist_reset(self.handle), self.lib)
-
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
-                (getattr(self, 'on', None) is None or self.on.handle):   # (a closed sampler or functionals freed it already)
-            self.lib.mjhmc_pairhist_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def join_exprs(exprs):
