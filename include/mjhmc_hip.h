@@ -577,6 +577,60 @@ int mjhmc_stein_evaluate(mjhmc_stein* k, int x_slot, int w_slot, int64_t n_use, 
 /* frees the handle's device memory (NULL: nothing) */
 int mjhmc_stein_destroy(mjhmc_stein* k);
 
+/* Device control variates: the sums from which variance-reduced expectations are formed (csrc/crossmoments.hip).  With
+ * g = dE/dX, integration by parts gives E_p[g] = 0 for every target p = exp(-E) / Z that vanishes at infinity, so g is a
+ * vector of ndims control variates of known mean zero (the first-order zero-variance control variates of Mira, Solgi and
+ * Imparato 2013): f - beta^T g with beta = Cov(g,g)^-1 Cov(g,f) has the expectation of f and the variance of the residual
+ * of a linear regression of f on g.  For states x[k][p][:] (sample-ring slot x_slot0 + k, particle p < N), their gradients
+ * g[k][p][:] (ndims values each, from the sampler's own evaluation kernels), the values b[k][p][:] of the same slot and
+ * particle in the handle's ring (K values each: the sample ring itself, K = ndims, or the derived ring of a functionals),
+ * weights w[k][p] and a shift vector cb of K doubles, the handle keeps on the device
+ *   W = sum w,   Sg_d = sum w g_d,   S2g_d = sum w g_d^2,   Cgg_de = sum w g_d g_e        (the gradient about 0, its known mean)
+ *   Sb_k = sum w (b_k - cb_k),   S2b_k = sum w (b_k - cb_k)^2,   Cgb_dk = sum w g_d (b_k - cb_k)
+ * all in float64, every state, gradient and ring element widened exactly, no floating-point atomic; every slot is added to
+ * the running totals separately and in a fixed order, so the sums are bit-identical from run to run on one device and do
+ * not depend on how a run is cut into calls.  W, Sg, S2g, Cgg and Sb, S2b are the sums of mjhmc_estimator_accumulate on the
+ * gradient matrix and on the ring; Cgb is a matrix-core pass of its own (64 x 64 blocks over the ndims x K rectangle).
+ * The handle owns one dE/dX matrix and one E vector in the layout the energy family writes (as mjhmc_stein) and the
+ * partials of the passes.  Ownership as for mjhmc_estimator: it belongs to the sampler (and to the functionals) it was
+ * created on, mjhmc_sampler_destroy frees every one still alive and the handle is INVALID from then on; a re-allocated
+ * sample ring or derived ring invalidates it.  The gradient evaluations are measurement, not sampling: no sampler state,
+ * counter or random stream is touched.
+ * MJHMC_ERR_INVALID: NULL arguments (before the sampler is touched), no sample ring yet, ndims > 512.
+ * MJHMC_ERR_UNSUPPORTED: a host-evaluated energy (MJHMC_E_HOST has no device evaluation of dE/dX), a wide (multi-pass)
+ * energy. */
+typedef struct mjhmc_crossmoments mjhmc_crossmoments;
+int mjhmc_crossmoments_create(mjhmc_sampler* s, mjhmc_crossmoments** out);
+/* mjhmc_crossmoments_create with b the K values of the functionals' derived ring (which must exist): the sums W, Sg, S2g,
+ * Cgg of the sampler's gradients, Sb, S2b of the K values and Cgb (ndims x K) between them; x_slot0 then counts slots of
+ * BOTH rings (derived slot j holds the values of sample-ring slot j).  MJHMC_ERR_INVALID also for K > 512 and for a
+ * functionals without a derived ring. */
+int mjhmc_crossmoments_create_on(mjhmc_functionals* f, mjhmc_crossmoments** out);
+/* cb: K finite doubles, NULL = zero (the state at create); the shift of the sums Sb, S2b and Cgb (the gradient sums Sg,
+ * S2g, Cgg are about 0 always).  Only while the handle is empty (MJHMC_ERR_INVALID after an accumulate; reset first). */
+int mjhmc_crossmoments_set_shift(mjhmc_crossmoments* h, const double* cb);
+/* Adds the n states of slots [x_slot0, x_slot0 + n) to the sums W, Sg, S2g, Sb, S2b, Cgg, Cgb with the weights of dwell-ring
+ * slots [w_slot0, w_slot0 + n), or unit weights for w_slot0 == -1: the pairing of mjhmc_estimator_accumulate (a jump
+ * sampler takes w_slot0 = x_slot0 + 1).  The call's n * N weights are checked first; then, slot by slot, the evaluation of
+ * dE/dX, the moment and covariance passes on it, the moment pass on the ring slot and the cross pass.  One read-back (one
+ * synchronisation) per call.  Rows p >= N are never read.
+ * MJHMC_ERR_INVALID: slots outside either ring, n < 1, a ring re-allocated since create.
+ * MJHMC_ERR_NONFINITE: a weight that is not finite -- nothing of the call has been added; or a state, a gradient or an
+ * energy of a row p < N that is not finite -- the message names the slot, the sums may hold the value, and the handle
+ * refuses every further accumulate (MJHMC_ERR_INVALID) until mjhmc_crossmoments_reset. */
+int mjhmc_crossmoments_accumulate(mjhmc_crossmoments* h, int x_slot0, int w_slot0, int n);
+/* The only download, none of the pointers NULL: the sums W, Sg[ndims], S2g[ndims], Sb[K], S2b[K], Cgg[ndims * ndims]
+ * (row-major, symmetric bit for bit), Cgb[ndims * K] (row-major, row d = gradient component d) and the number of
+ * (slot, particle) states added so far. */
+int mjhmc_crossmoments_read(mjhmc_crossmoments* h, double* W, double* Sg, double* S2g, double* Sb, double* S2b, double* Cgg,
+                            double* Cgb, int64_t* n_states);
+/* zero the sums W, Sg, S2g, Sb, S2b, Cgg, Cgb and the count, and lift the refusal a non-finite value left; the shift stays */
+int mjhmc_crossmoments_reset(mjhmc_crossmoments* h);
+/* ndims (the length of Sg; Cgg is ndims x ndims) and K (the length of Sb; the sums Cgb are ndims x K) */
+int mjhmc_crossmoments_info(mjhmc_crossmoments* h, int* ndims, int* n_values);
+/* frees the handle's device memory and its sums (NULL: nothing) */
+int mjhmc_crossmoments_destroy(mjhmc_crossmoments* h);
+
 /* Fair sample paths on a uniform time grid, kept on the device (csrc/timegrid.hip): the one result the weighted
  * accumulators above cannot give -- a fair sample with its time order kept.  The reference's sample(resample=True)
  * (markov_jump_hmc.py:293-338) pools particles and steps into one weighted draw ("preserve_order has no effect if

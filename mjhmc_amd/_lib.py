@@ -137,6 +137,14 @@ PROTOTYPES = {
     'mjhmc_stein_create': (ctypes.c_int, [_P, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_stein_evaluate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
     'mjhmc_stein_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_crossmoments_create': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
+    'mjhmc_crossmoments_create_on': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
+    'mjhmc_crossmoments_set_shift': (ctypes.c_int, [_P, _P]),
+    'mjhmc_crossmoments_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_crossmoments_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_crossmoments_reset': (ctypes.c_int, [_P]),
+    'mjhmc_crossmoments_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    'mjhmc_crossmoments_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_timegrid_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

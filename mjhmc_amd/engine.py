@@ -458,6 +458,12 @@ class DeviceSampler(object):
         refused."""
         return DeviceStein(self, c)
 
+    def cross_moments(self):
+        """The sums of the control variates dE/dX over blocks of this sampler's ring (mjhmc_crossmoments_*): moments and
+        covariance of the gradient, moments of the state and the ndims x ndims cross moments between them.  The ring must
+        exist (ring_alloc); ndims <= 512; a host-evaluated energy is refused."""
+        return DeviceCrossMoments(self)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -554,6 +560,39 @@ class DeviceEstimator(_RingAccumulator):
         C = np.empty((D, D)) if self.want_cov else None
         check(self.lib.mjhmc_estimator_read(self.handle, ctypes.byref(W), ptr(S1), ptr(S2), ptr(C), ctypes.byref(n)), self.lib)
         return W.value, S1, S2, C, int(n.value)
+
+
+class DeviceCrossMoments(_RingAccumulator):
+    """The sums of the control variates g = dE/dX (include/mjhmc_hip.h: mjhmc_crossmoments_*): W = sum w, Sg = sum w g,
+    S2g = sum w g^2, Cgg = sum w g g^T (the gradient about 0, its known mean), Sb = sum w (b - cb), S2b = sum w (b - cb)^2 and
+    Cgb = sum w g (b - cb)^T over the (slot, particle) states given to ``accumulate``, b the state itself or, with ``on``,
+    the K values of a DeviceFunctionals; float64 throughout, bit-identical from run to run and whatever the blocks."""
+    _kind = 'crossmoments'
+
+    def __init__(self, dev, on=None):
+        """``on``: a DeviceFunctionals of ``dev`` whose derived ring b is read from (x_slot0 then counts slots of both rings)"""
+        self._create(dev, on)
+        d, k = ctypes.c_int(), ctypes.c_int()
+        self._call('info', ctypes.byref(d), ctypes.byref(k))
+        self.ndims, self.n_values = int(d.value), int(k.value)
+
+    def set_shift(self, cb=None):
+        cb = None if cb is None else as_f64(np.asarray(cb, dtype=np.float64).reshape(-1), (self.n_values,))
+        self._call('set_shift', ptr(cb))
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A weight that is not finite raises and adds nothing; a
+        state, gradient or energy that is not finite raises naming the slot, and the handle refuses until ``reset``."""
+        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
+
+    def read(self):
+        """(W, Sg (D,), S2g (D,), Sb (K,), S2b (K,), Cgg (D, D), Cgb (D, K), n_states)"""
+        D, K = self.ndims, self.n_values
+        W, n = ctypes.c_double(), ctypes.c_int64()
+        Sg, S2g, Sb, S2b, Cgg, Cgb = np.empty(D), np.empty(D), np.empty(K), np.empty(K), np.empty((D, D)), np.empty((D, K))
+        self._call('read', ctypes.byref(W), ptr(Sg), ptr(S2g), ptr(Sb), ptr(S2b), ptr(Cgg), ptr(Cgb), ctypes.byref(n))
+        return W.value, Sg, S2g, Sb, S2b, Cgg, Cgb, int(n.value)
 
 
 class DeviceChainStats(_RingAccumulator):
@@ -829,6 +868,10 @@ class DeviceFunctionals(object):
 
     def pair_histogram(self, pairs, bins, lo, hi, quantum=1.0):
         return DevicePairHistogram(self.dev, pairs, bins, lo, hi, quantum, on=self)
+
+    def cross_moments(self):
+        """the sampler's DeviceCrossMoments with b the K values of this derived ring (K <= 512)"""
+        return DeviceCrossMoments(self.dev, on=self)
 
     def close(self):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)

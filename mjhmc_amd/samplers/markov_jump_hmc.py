@@ -33,6 +33,43 @@ class Expectations(object):
         self.cov = None if C is None else C / W - np.outer(m1, m1)
 
 
+class ControlVariateExpectations(object):
+    """What ``cv_expectations()`` returns: expectations of the K values f with the gradient g = dE/dX as ndims control
+    variates of known mean zero.  From the device sums (include/mjhmc_hip.h: mjhmc_crossmoments_read) -- ``W``, ``Sg``,
+    ``S2g``, ``Cgg`` of g about 0 and ``Sb``, ``S2b``, ``Cgb`` of f about ``shift`` --
+
+      grad_mean = Sg / W                               ~ 0 on a correct chain: a per-dimension Stein check in its own right
+      m = Sb / W
+      cov_gg = Cgg / W - grad_mean grad_mean^T         cov_gf = Cgb / W - grad_mean m^T
+      coef = solve(cov_gg, cov_gf)                     (ndims, K): Cholesky; when cov_gg is not positive definite, the
+                                                       minimum-norm least-squares solution, and ``rank`` < ndims says so
+      mean = shift + m - coef^T grad_mean              the control-variate estimate of E[f]
+      plain                                            the ``Expectations`` of f from the same run (mean, var)
+      variance_ratio = 1 - diag(cov_gf^T coef) / plain.var
+                                                       the in-sample residual of the regression of f on g, in [0, 1]
+
+    plus ``rank``, ``n_states`` and ``total_weight``."""
+
+    def __init__(self, W, Sg, S2g, Sb, S2b, Cgg, Cgb, n_states, shift):
+        self.W, self.Sg, self.S2g, self.Sb, self.S2b, self.Cgg, self.Cgb, self.shift = W, Sg, S2g, Sb, S2b, Cgg, Cgb, shift
+        self.total_weight, self.n_states = W, n_states
+        D = Sg.shape[0]
+        self.grad_mean = Sg / W
+        m = Sb / W
+        self.cov_gg = Cgg / W - np.outer(self.grad_mean, self.grad_mean)
+        self.cov_gf = Cgb / W - np.outer(self.grad_mean, m)
+        try:
+            L = np.linalg.cholesky(self.cov_gg)
+            self.coef = np.linalg.solve(L.T, np.linalg.solve(L, self.cov_gf))
+            self.rank = D
+        except np.linalg.LinAlgError:
+            self.coef, _, rank, _ = np.linalg.lstsq(self.cov_gg, self.cov_gf, rcond=None)
+            self.rank = int(rank)
+        self.plain = Expectations(W, Sb, S2b, None, n_states, shift)
+        self.mean = shift + m - self.coef.T.dot(self.grad_mean)
+        self.variance_ratio = 1.0 - np.sum(self.cov_gf * self.coef, axis=0) / self.plain.var
+
+
 class Diagnostics(object):
     """What ``diagnostics()`` returns: do the chains agree with each other, and how many independent draws are they worth.
 
@@ -1081,6 +1118,89 @@ class HMCBase(object):
             if fn is not None:
                 fn.close()
         return Expectations(W, S1, S2, C, n_states, shift)
+
+    def cv_expectations(self, n_iter, of=None, block=None, shift=None):
+        """Variance-reduced expectations of ``n_iter`` consecutive states of every particle: the means of
+        ``expectations(n_iter, of=of)`` with the gradient g = dE/dX of every recorded state as ndims control variates
+        (csrc/crossmoments.hip).  Integration by parts gives E_p[g] = 0 for every target p = exp(-E) / Z that vanishes at
+        infinity, so f - coef^T g has the expectation of f for any coef, and with coef = Cov(g, g)^-1 Cov(g, f) the variance
+        of the residual of a linear regression of f on g (the first-order zero-variance control variates of Mira, Solgi and
+        Imparato 2013).  For a Gaussian target the mean is exact at every state, equilibrated or not.  Returns a
+        ``ControlVariateExpectations``: ``mean``, ``plain`` (the ``Expectations`` of the same run), ``variance_ratio``,
+        ``coef``, ``grad_mean``, ``rank``, ``n_states`` and the raw sums.
+
+        The run is that of ``expectations(n_iter, of=of)``: the same iterations in blocks of ``block`` states, the same
+        weights (holding times for the jump samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the
+        same counters, ``dwelling_times`` and final state, bit for bit.  The pass costs one gradient per recorded state,
+        against num_leapfrog_steps per iteration; these evaluations are NOT counted in ``E_count`` / ``dEdX_count``
+        (measurement, not sampling).  Every slot is added to the device sums separately: under a given ``shift`` the sums
+        do not depend on ``block``.  ``shift``: the vector the sums of f are taken about; None takes the first block's own
+        mean, at the price of reading that block twice.
+
+        ``of``: None (f is the state itself, K = ndims), or the K values of a ``Functionals``, ``Projections`` or
+        ``EnergyObservables``.  Second moments of the coordinates come from ``projections(np.eye(ndims), link='u*u')``.
+
+        Caveats.  E_p[g] = 0 needs p -> 0 at infinity: it fails in SparseImageCode's improper directions (the Cauchy prior
+        at lambda = 0.01, the warning ``temperature()`` gives).  ``coef`` is estimated from the same states, which leaves a
+        bias of order ndims / n_eff.  ``variance_ratio`` is the in-sample residual of the regression, not an ESS-aware
+        promise of the error of ``mean``.
+
+        ValueError, before anything runs: n_iter < 1; n_iter * nbatch <= 2 * ndims (the regression is not determined);
+        ndims > 512 or K > 512; an energy given as opaque callables; a sharded sampler (the sums are additive over ranks,
+        but that is out of scope here: it has not been proved on a multi-rank machine)."""
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+        K = int(self.ndims) if of is None else int(of.n_values)
+        if int(self.ndims) > 512 or K > 512:
+            raise ValueError('cv_expectations takes ndims <= 512 and K <= 512 values, got ndims = %d, K = %d' % (self.ndims, K))
+        if n_iter * int(self.nbatch) <= 2 * int(self.ndims):
+            raise ValueError('cv_expectations: n_iter * nbatch = %d states do not determine a regression on ndims = %d '
+                             'control variates (more than 2 * ndims are needed)' % (n_iter * int(self.nbatch), self.ndims))
+        if shift is not None and np.size(shift) != K:
+            raise ValueError('shift must have %d entries' % K)
+        self._check_of(of)
+        if self.distribution.device_energy()[0] == _lib.E_HOST:
+            raise ValueError('cv_expectations: the energy is a pair of opaque Python callables, which are its only '
+                             'evaluation -- there is no device evaluation of dE/dX to take the control variates from')
+        if self._comm is not None:
+            raise ValueError('cv_expectations: a sharded sampler (comm set) is not supported -- the sums are additive over '
+                             'ranks, but that is out of scope: it has not been proved on a multi-rank machine')
+        lead = 1 if self._dwell_weighted else 0
+        if block is None:
+            # the handle's dE/dX matrix is at most two slots (float32 gradient of a bfloat16 state); the partials of the
+            # covariance and cross passes are at most ~2048 waves x 32 KiB each
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of),
+                                                reserve_bytes=2 * self._dev.ring_slot_bytes() + (160 << 20)) - lead
+        block = max(1, min(int(block), n_iter))
+        self._dev.ring_alloc(block + lead)
+        fn = cm = None
+        try:
+            fn = None if of is None else self._open_functionals(of, block)
+            cm = (self._dev if fn is None else fn).cross_moments()
+            if shift is not None:
+                shift = self._checked_shift(shift, of)
+                cm.set_shift(shift)
+            for _, k in self._ring_blocks([n_iter], block):
+                if fn is not None:
+                    fn.evaluate(0, k, 0)
+                cm.accumulate(0, k, w_slot0=1 if lead else -1)
+                if shift is None:                          # the first block's own mean, then the same block again about it
+                    sums = cm.read()
+                    shift = sums[3] / sums[0]
+                    cm.reset()
+                    cm.set_shift(shift)
+                    cm.accumulate(0, k, w_slot0=1 if lead else -1)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            sums = cm.read()
+        finally:
+            if cm is not None:
+                cm.close()
+            if fn is not None:
+                fn.close()
+        return ControlVariateExpectations(*(sums + (shift,)))
 
     def _checked_shift(self, shift, of=None):
         shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
