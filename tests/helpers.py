@@ -249,6 +249,17 @@ def jump_instance(E, logG, full, fused, mode='mjhmc', block_decide=True):
     return True, 0
 
 
+def pot_padded_dim(ndims):
+    """Pure-Python restatement of the padded size of the ProductOfT tile kernels (MJHMC_E_PRODUCT_OF_T in csrc/api.hip,
+    csrc/dense_pot_tile.hpp) up to 512 dims: (DIM, NB) -- DIM = 128 NB rows and columns of the pre-scaled matrices, NB
+    accumulator blocks per wave.  Rows from ndims up are padding; at NB = 1 the GEMMs skip the groups of eight k-rows that
+    lie entirely in it."""
+    if not 1 <= ndims <= 512:
+        raise ValueError('the register-resident tile kernels hold 1 .. 512 dims')
+    dim = 128 if ndims <= 128 else 256 if ndims <= 256 else 512
+    return dim, dim // 128
+
+
 _HOOKS_CTX = {}
 
 
