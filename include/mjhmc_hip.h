@@ -181,6 +181,20 @@ int mjhmc_energy_create_linear(mjhmc_ctx* ctx, int ndims, int nexperts, const do
 /* compile-only check of a linear-model energy's expressions (needs no device): 0, MJHMC_ERR_INVALID with the compiler's
  * log, MJHMC_ERR_UNSUPPORTED beyond 512 */
 int mjhmc_linear_check(int ndims, int nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
+/* Tall linear-model energies: the same form and the same expressions with MORE experts than dims -- 1 <= ndims <= 512,
+ * 1 <= nexperts <= 2^20 (a GLM posterior: one expert per data row plus ndims prior experts).  The experts are stored in
+ * ceil(nexperts / P) blocks of P = ndims padded to 128, 256 or 512, and one fused matrix-core kernel (compiled with hipRTC
+ * at creation, cached per process) walks the blocks per tile of 32 particles: u = W x + b never reaches memory.  j is the
+ * GLOBAL expert index; q[m] reads row m at it.  The kind is MJHMC_E_LINEAR_EXPR; samplers of such an energy run the
+ * engine's multi-pass path with either state dtype (as PRODUCT_OF_T beyond 512 dims), so everything built on the ring works.
+ * nexperts <= 512 is legal (one or a few blocks).  ndims > 512 or nexperts > 2^20: MJHMC_ERR_UNSUPPORTED; sizes < 1, NULLs,
+ * more than 4 expert rows, non-finite W / b, compile errors (with the log): MJHMC_ERR_INVALID.  Device memory of the
+ * matrices: 2 * ceil(nexperts / P) * P * P * 4 bytes (reported when the allocation fails). */
+int mjhmc_energy_create_linear_tall(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
+                                    const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                                    const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out);
+/* compile-only check of a tall linear-model energy (needs no device): 0, MJHMC_ERR_INVALID, MJHMC_ERR_UNSUPPORTED as above */
+int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
 int mjhmc_energy_destroy(mjhmc_energy* e);
 
 /* One evaluation of E_val / dEdX_val (mjhmc/misc/distributions.py:66-81) on n columns.

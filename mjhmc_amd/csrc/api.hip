@@ -146,9 +146,9 @@ int pick_shape(int D, int dtype, Shape* out) {
 static int shape_for(const mjhmc_energy* e, int* dtype, Shape* sh) {
   if (e->is_pot()) {
     if (*dtype != MJHMC_F64 && *dtype != MJHMC_F32) return fail(MJHMC_ERR_UNSUPPORTED, "PRODUCT_OF_T and LINEAR_EXPR run with float32 or float64 state");
-    if (*dtype == MJHMC_F64 || e->pot_big()) {
+    if (*dtype == MJHMC_F64 || e->pot_big() || e->lin_tall()) {
       // the reference's own arithmetic: float64 HMCState arrays around the float32 force (distributions.py:408-415,
-      // hmc_state.py:29-38); ndims > 512: the blocked force evaluation exists on the multi-pass path only
+      // hmc_state.py:29-38); ndims > 512 and tall linear models: their force evaluation exists on the multi-pass path only
       *sh = Shape{0, 0, e->pot_dim, e->pot_dim / 2, 8, true};
       sh->round32 = *dtype != MJHMC_F64;
     } else {
@@ -1031,6 +1031,47 @@ int mjhmc_linear_check(int ndims, int nexperts, const char* energy_expr, const c
   return rc ? fail(rc, err) : 0;
 }
 
+int mjhmc_energy_create_linear_tall(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
+                                    const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                                    const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out) {
+  TRY(linear_tall_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
+  if (nparams && !params) return fail(MJHMC_ERR_INVALID, "params is NULL");
+  if (n_expert_rows < 0 || n_expert_rows > 4 || (n_expert_rows && !expert_params))
+    return fail(MJHMC_ERR_INVALID, "LINEAR_EXPR takes 0 to 4 per-expert parameter rows");
+  for (size_t i = 0, n = (size_t)nexperts * ndims; i < n; ++i)
+    if (!std::isfinite(W[i])) return fail(MJHMC_ERR_INVALID, "W has a non-finite entry (row " + std::to_string(i / ndims) + ")");
+  for (int64_t j = 0; j < nexperts; ++j)
+    if (!std::isfinite(b[j])) return fail(MJHMC_ERR_INVALID, "b has a non-finite entry (" + std::to_string(j) + ")");
+  HIPCHK(hipSetDevice(ctx->device));
+  mjhmc_energy* e = new mjhmc_energy();
+  e->ctx = ctx;
+  std::memset(&e->ep, 0, sizeof(e->ep));
+  e->ep.kind = MJHMC_E_LINEAR_EXPR;
+  e->ep.ndims = ndims;
+  const int rc = linear_tall_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params,
+                                          n_expert_rows, include_dir);
+  if (rc) {
+    std::string keep = g_err;
+    mjhmc_energy_destroy(e);
+    g_err = keep;
+    return rc;
+  }
+  *out = e;
+  return 0;
+}
+
+int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
+  TRY(linear_tall_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  std::string err;
+  const std::vector<char>* code = nullptr;
+  const std::vector<std::string>* lowered = nullptr;
+  const int dim = ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim);
+  const int rc = linear_tall_compile(energy_expr, grad_expr, dim, include_dir, &err, &code, &lowered);
+  return rc ? fail(rc, err) : 0;
+}
+
 int mjhmc_energy_destroy(mjhmc_energy* e) {
   if (!e) return 0;
   user_energy_free(e);
@@ -1134,7 +1175,7 @@ int mjhmc_sampler_create(mjhmc_ctx* ctx, mjhmc_energy* e, int64_t nparticles, in
           HIPCHK(hipMalloc((void**)&s->Hwork, s->Npad * ssize(s)));  // float32, or float64 for ProductOfT's float64 state
           HIPCHK(hipMemsetAsync(s->Hwork, 0, s->Npad * ssize(s), s->stream));   // (padding rows read it and ignore it)
           HIPCHK(hipMalloc((void**)&s->cold_list, (2 * s->Npad + 3 * kMaxDenseParts) * sizeof(int)));  // two lists (iterations alternate) + [part][3] counters
-          if (e->is_pot() && dtype == MJHMC_F64 && !e->pot_big())   // working rows of the tile kernel, one set per concurrent launch
+          if (e->is_pot() && dtype == MJHMC_F64 && !e->pot_big() && !e->lin_tall())   // working rows of the tile kernel, one set per concurrent launch
             HIPCHK(hipMalloc((void**)&s->pot64_scratch, (size_t)kMaxDenseParts * pot64_scratch_workgroups() * 2 * 32 * row_bytes(s)));
         }
         HIPCHK(hipMalloc(&s->Hspec[i], s->Npad * ssize(s)));
@@ -2029,7 +2070,7 @@ int mjhmc_iterate(mjhmc_sampler* s, int n_iter, const double* replay_normal, con
   HIPCHK(hipSetDevice(s->ctx->device));
   // ProductOfT with float64 state: the tile kernel with the state streamed through its epilogue (dense_pot64.hip); its
   // multi-pass form (the same arithmetic, bit for bit) serves L = 0 and, in the test build, the A/B switch
-  const bool pot64_fused = s->sh.wide && s->en->is_pot() && !s->en->pot_big() && !s->sh.round32 && s->L >= 1 &&
+  const bool pot64_fused = s->sh.wide && s->en->is_pot() && !s->en->pot_big() && !s->en->lin_tall() && !s->sh.round32 && s->L >= 1 &&
                            !test_env("MJHMC_POT64_MULTIPASS");
   if (s->sh.wide && !pot64_fused) {
     s->list_valid = false;

@@ -38,6 +38,15 @@ struct PotLinear {
   int stride;       // the padded dimension
 };
 
+// A tall linear-model energy (more experts than the tile kernels hold; dense_lin_tall.hpp): the experts in
+// nblk blocks of P = the pad of D (128, 256 or 512), each block laid out like a <= 512 model's matrices, zero padded
+struct LinTallModel {
+  const float* W1b;    // [blk][d][j] = W[blk P + j][d]   (first GEMM of the block:  u = W1b[blk]^T x + cb[blk])
+  const float* W2Tb;   // [blk][j][d] = W[blk P + j][d]   (second GEMM: dE/dx += W2Tb[blk]^T phi(u))
+  const float* cb;     // [nblk P]    = b
+  int nblk, D, K;
+};
+
 // Rates, waiting times and first minimum of ONE particle, evaluated serially by one lane (the dense
 // kernels run it on 32 lanes of one wave, one particle each; ~1e3 instructions against ~1e6 cycles of
 // trajectory).  markov_jump_hmc.py:366-396, utils.py:15-49.  Returns k (0 L, 1 F, 2 R).

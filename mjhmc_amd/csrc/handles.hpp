@@ -55,6 +55,9 @@ struct mjhmc_energy {
   bool is_pot() const { return ep.kind == MJHMC_E_PRODUCT_OF_T || ep.kind == MJHMC_E_LINEAR_EXPR; }
   LinearEnergy* lin = nullptr;  // MJHMC_E_LINEAR_EXPR: its hipRTC-built kernels, launched by the pot_launch_* entry points
   const PotGenerated* pot_gen() const { return lin ? &lin->gen : nullptr; }
+  // a tall linear model (more than 512 experts allowed; pot_dim: the pad of ndims): one fused force kernel, no tile
+  // kernels -- routed like pot_big(), to the multi-pass path (is_pot() stays true, pot_big() false)
+  bool lin_tall() const { return lin && lin->tall; }
   void* sic[3] = {nullptr, nullptr, nullptr};  // SparseImageCode: A1, A2 (bf16, fragment order), y (float32 [P][256])
   float sic_lambda = 0.f;
   int sic_cauchy = 1;

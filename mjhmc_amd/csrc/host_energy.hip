@@ -508,6 +508,10 @@ static void pot_force32(mjhmc_sampler* s, float* const* buf, bool want_G, bool w
     pot_big_eval(s->en->pot_big_model(), buf[0], want_G ? buf[1] : nullptr, want_E ? buf[2] : nullptr, buf[3], rows_pad, s->stream);
     return;
   }
+  if (s->en->lin_tall()) {   // the fused block-by-block kernel of a tall linear model (no u rows: buf[3] is not used)
+    lin_tall_eval(s->en, buf[0], want_G ? buf[1] : nullptr, want_E ? buf[2] : nullptr, rows_pad, nrows, s->stream);
+    return;
+  }
   PotEvalArgs a;
   a.X = buf[0];
   a.G = want_G ? buf[1] : nullptr;

@@ -11,8 +11,11 @@
 // for the one NB the model needs: float32-state jump kernels x 3 modes x replay, the float64-state ones likewise, eval
 // and leap -- 14 kernels.  The cold-list, fix and decide kernels take no model and are the library's own.  Everything
 // else (dE/dX storage, call blocks, parts, the multi-pass path at L = 0, state operations) is ProductOfT's: is_pot().
+// Models with more experts than 512 (K <= 2^20, D <= 512) are the second half of this file: one fused kernel over expert
+// blocks (dense_lin_tall.hpp) as the force of the multi-pass path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -33,11 +36,9 @@ struct Compiled {
 std::mutex g_cache_mu;
 std::map<std::string, std::unique_ptr<Compiled>> g_cache;   // generated source + NB -> code object (never evicted)
 
-std::string linear_source(const std::string& energy_expr, const std::string& grad_expr) {
+// E = sum_j f(u_j, j), dE/dx = W^T f'(u): the caller's expressions as a functor (shared by both generated sources)
+std::string user_functor_source(const std::string& energy_expr, const std::string& grad_expr) {
   std::string s;
-  s += "#include \"dense_pot_kernels.hpp\"\n";
-  s += "#include \"dense_pot64_kernels.hpp\"\n";
-  s += "namespace mjhmc {\n";
   s += "// E = sum_j f(u_j, j), dE/dx = W^T f'(u): the caller's expressions (u float, j int, p[k], q[m])\n";
   s += "struct LinUserF {\n";
   s += "  static __device__ __forceinline__ float f(float u, int j, const float* __restrict__ p, LinQ q) {\n";
@@ -47,6 +48,15 @@ std::string linear_source(const std::string& energy_expr, const std::string& gra
   s += "    (void)u; (void)j; (void)p; (void)q;\n";
   s += "    return (float)(" + grad_expr + ");\n  }\n";
   s += "};\n";
+  return s;
+}
+
+std::string linear_source(const std::string& energy_expr, const std::string& grad_expr) {
+  std::string s;
+  s += "#include \"dense_pot_kernels.hpp\"\n";
+  s += "#include \"dense_pot64_kernels.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += user_functor_source(energy_expr, grad_expr);
   s += "using LinXP = LinearExperts<LinUserF>;\n";
   s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_eval_kernel(const PotEvalArgs a, const PotModel mdl, const PotLinear lin) {\n";
   s += "  const LinXP xp{lin};\n#include \"dense_pot_eval.inc\"\n}\n";
@@ -71,6 +81,27 @@ std::vector<std::string> linear_kernel_names(int NB) {
   n.push_back("mjhmc::lin_eval_kernel<" + nb + ">");
   n.push_back("mjhmc::lin_leap_kernel<" + nb + ">");
   return n;
+}
+
+// A tall model's one kernel (dense_lin_tall.hpp): a source of its own, so a tall model compiles this and nothing else
+std::string linear_tall_source(const std::string& energy_expr, const std::string& grad_expr) {
+  std::string s;
+  s += "#include \"dense_lin_tall.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += user_functor_source(energy_expr, grad_expr);
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_tall_eval_kernel(const PotEvalArgs a, const LinTallModel tm, const PotLinear lin) {\n";
+  s += "  __shared__ Shared<NB> sh;\n  lin_tall_eval_tiles<NB, LinUserF>(a, tm, lin, sh);\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
+int tall_pad(int ndims) { return ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim); }
+
+int resident_cus() {
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus > 1 ? cus : 1;
 }
 
 }  // namespace
@@ -161,4 +192,114 @@ void linear_energy_free(mjhmc_energy* e) {
   if (e->lin->module) (void)hipModuleUnload(e->lin->module);
   delete e->lin;
   e->lin = nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Tall models: 1 <= D <= 512, 1 <= K <= 2^20.  P = the pad of D alone; the experts in
+// nblk = ceil(K / P) blocks, each stored like a <= 512 model's W1 / W2T / cb, and one generated kernel that walks them
+// (dense_lin_tall.hpp).  The energy keeps the kind MJHMC_E_LINEAR_EXPR and is_pot(); its samplers run the multi-pass path
+// (lin_tall(), handles.hpp), whose float32 force this kernel is.
+// ---------------------------------------------------------------------------------------------------------------------
+int linear_tall_check_args(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
+  if (!energy_expr || !grad_expr || !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (ndims < 1 || nexperts < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "LINEAR_EXPR needs ndims >= 1 and nexperts >= 1");
+  if (ndims > kPotDim)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a tall LINEAR_EXPR model takes at most 512 dims (got " + std::to_string(ndims) +
+                                             "): its expert blocks are the tile kernels' 512 x 512 at the most");
+  if (nexperts > kLinTallMaxExperts)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a tall LINEAR_EXPR model takes at most 1048576 (2^20) experts (got " +
+                                             std::to_string(nexperts) + ")");
+  return 0;
+}
+
+int linear_tall_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
+                        std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered) {
+  const int NB = dim / 128;
+  const std::string src = linear_tall_source(energy_expr, grad_expr);
+  const std::string key = src + "\n// tall, NB = " + std::to_string(NB) + ", -I" + include_dir;
+  std::lock_guard<std::mutex> lk(g_cache_mu);
+  auto it = g_cache.find(key);
+  if (it == g_cache.end()) {
+    std::unique_ptr<Compiled> c(new Compiled());
+    const int rc = rtc_compile(src, "mjhmc_linear_tall.hip", include_dir, {"mjhmc::lin_tall_eval_kernel<" + std::to_string(NB) + ">"},
+                               &c->code, &c->lowered, err);
+    if (rc) return rc;
+    it = g_cache.emplace(key, std::move(c)).first;
+  }
+  *code = &it->second->code;
+  *lowered = &it->second->lowered;
+  return 0;
+}
+
+int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, const char* energy_expr,
+                             const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
+                             int n_expert_rows, const char* include_dir) {
+  const int D = e->ep.ndims, K = (int)nexperts, P = tall_pad(D), nblk = (K + P - 1) / P;
+  const size_t KP = (size_t)nblk * P;
+  LinearEnergy* l = new LinearEnergy();
+  e->lin = l;
+  const std::vector<char>* code = nullptr;
+  const std::vector<std::string>* lowered = nullptr;
+  std::string err;
+  const int rc = linear_tall_compile(energy_expr, grad_expr, P, include_dir, &err, &code, &lowered);
+  if (rc) return mjhmc_fail(rc, err);
+  HIPCHK(hipModuleLoadData(&l->module, code->data()));
+  HIPCHK(hipModuleGetFunction(&l->tall, l->module, (*lowered)[0].c_str()));
+  l->tall_nblk = nblk;
+  l->tall_K = K;
+  e->pot_dim = P;      // the state rows' pitch: the pad of D
+  e->pot_rows = D;
+
+  // W1b[blk][d][j] = W2Tb[blk][j][d] = W[blk P + j][d], cb = b, zero padded; float32
+  const size_t M = (size_t)P * P, mat_bytes = KP * P * sizeof(float), nrows = (size_t)4 * KP + (nparams ? nparams : 1);
+  std::vector<float> w1(KP * P, 0.f), w2t(KP * P, 0.f), cb(KP, 0.f), rows(nrows, 0.f);
+  for (int j = 0; j < K; ++j) {
+    const size_t blk = (size_t)j / P, jl = (size_t)j % P;
+    cb[j] = (float)b[j];
+    for (int d = 0; d < D; ++d) {
+      const float w = (float)W[(size_t)j * D + d];
+      w1[blk * M + (size_t)d * P + jl] = w;
+      w2t[blk * M + jl * P + d] = w;
+    }
+  }
+  for (int m = 0; m < n_expert_rows; ++m)
+    for (int j = 0; j < K; ++j) rows[(size_t)m * KP + j] = (float)expert_params[(size_t)m * K + j];
+  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * KP + k] = (float)params[k];
+  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
+  const size_t bytes[3] = {mat_bytes, mat_bytes, KP * sizeof(float)};
+  for (int i = 0; i < 3; ++i) {
+    if (hipMalloc((void**)&e->pot[i], bytes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      e->pot[i] = nullptr;
+      return mjhmc_fail(MJHMC_ERR_HIP, "a tall LINEAR_EXPR model of " + std::to_string(D) + " dims x " + std::to_string(K) +
+                                       " experts needs " + std::to_string(2 * mat_bytes) + " bytes of device memory for its matrices (" +
+                                       std::to_string(nblk) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
+                                       ", twice): the allocation failed");
+    }
+    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
+  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
+  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * KP, K, (int)KP};
+  return 0;
+}
+
+void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st) {
+  PotEvalArgs a;
+  a.X = X32;
+  a.G = G32;
+  a.E = E32;
+  a.EV = nullptr;
+  a.V = nullptr;
+  a.V_gen = nullptr;
+  a.N = nrows;
+  a.ntiles = rows_pad / 32;
+  a.first_pid = 0;
+  a.D = e->ep.ndims;
+  a.key = RngKey{0u, 0u, 0u, 0u};
+  const LinTallModel tm{e->pot[0], e->pot[1], e->pot[2], e->lin->tall_nblk, e->ep.ndims, e->lin->tall_K};
+  const PotLinear lin = e->lin->gen.lin;
+  const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
+  void* params[] = {(void*)&a, (void*)&tm, (void*)&lin};
+  (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
 }

@@ -14,7 +14,13 @@ struct LinearEnergy {
   hipModule_t module = nullptr;
   mjhmc::PotGenerated gen;   // the module's kernels and the experts' device arguments
   float* rows = nullptr;     // [4][dim] per-expert rows, then the shared parameters (gen.lin.q, gen.lin.p)
+  // a tall model (more than 512 experts): its one kernel, lin_tall_eval_kernel, and its block count; the
+  // tile kernels of `gen` are then absent (gen.lin alone is used) and the sampler runs the multi-pass path
+  hipFunction_t tall = nullptr;
+  int tall_nblk = 0, tall_K = 0;
 };
+
+constexpr int64_t kLinTallMaxExperts = (int64_t)1 << 20;
 
 // the padded dimension of a (D, K) model: 128, 256 or 512; 0 beyond the tile kernels
 int linear_dim(int ndims, int nexperts);
@@ -27,3 +33,14 @@ int linear_energy_build(mjhmc_energy* e, int nexperts, const double* W, const do
                         const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
                         int n_expert_rows, const char* include_dir);
 void linear_energy_free(mjhmc_energy* e);
+
+// Tall models: 1 <= ndims <= 512, 1 <= nexperts <= 2^20 (kLinTallMaxExperts), experts in blocks of the pad of ndims
+int linear_tall_check_args(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
+// the hipRTC compile of lin_tall_eval_kernel<dim / 128>: its own small source, its own cache key
+int linear_tall_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
+                        std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered);
+int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, const char* energy_expr,
+                             const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
+                             int n_expert_rows, const char* include_dir);
+// E (or none) and dE/dX (or none) of float32 rows X32 [rows_pad][pad of ndims] (rows_pad a multiple of 32) on `st`
+void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st);

@@ -98,14 +98,20 @@ class Context(object):
         return which
 
 
-def linear_arrays(W, b, params=(), expert_params=None):
+TALL_MAX_EXPERTS = 2 ** 20      # mjhmc_energy_create_linear_tall
+
+
+def linear_arrays(W, b, params=(), expert_params=None, _tall=False):
     """The checked float64 arrays of a linear-model energy: W (K, D), b (K,), params (n,), expert_params (M <= 4, K).
     Raises ValueError on a shape the device form does not take (before any device call)."""
     W = np.ascontiguousarray(W, dtype=np.float64)
     if W.ndim != 2 or W.shape[0] < 1 or W.shape[1] < 1:
         raise ValueError('W must be a (K, D) matrix, got shape %r' % (W.shape,))
     K, D = W.shape
-    if K > 512 or D > 512:
+    if _tall:
+        if K > TALL_MAX_EXPERTS or D > 512:
+            raise ValueError('tall linear-model energies take at most 2**20 experts and 512 dims (W is %d x %d)' % (K, D))
+    elif K > 512 or D > 512:
         raise ValueError('linear-model energies take at most 512 experts and 512 dims (W is %d x %d)' % (K, D))
     b = np.ascontiguousarray(np.zeros(K) if b is None else b, dtype=np.float64)
     if b.shape != (K,):
@@ -117,6 +123,11 @@ def linear_arrays(W, b, params=(), expert_params=None):
     if q.ndim != 2 or q.shape[1] != K or q.shape[0] > 4:
         raise ValueError('expert_params must be (M <= 4, K = %d), got shape %r' % (K, q.shape))
     return W, b, params, np.ascontiguousarray(q)
+
+
+def tall_linear_arrays(W, b, params=(), expert_params=None):
+    """linear_arrays for a tall model (mjhmc_energy_create_linear_tall): W (K, D) with D <= 512 and K <= 2**20."""
+    return linear_arrays(W, b, params, expert_params, _tall=True)
 
 
 def context(device=0):
@@ -175,6 +186,27 @@ class DeviceEnergy(object):
         self.W, self.b, self.expert_params = W, b, q
         h = ctypes.c_void_p()
         check(ctx.lib.mjhmc_energy_create_linear(
+            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), str(energy_expr).encode(), str(grad_expr).encode(),
+            ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
+            _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
+        self.handle = h
+        return self
+
+    @classmethod
+    def from_linear_tall(cls, ctx, W, b, energy_expr, grad_expr, params=(), expert_params=None):
+        """The same form with more experts than the tile kernels hold (mjhmc_energy_create_linear_tall): W (K, D),
+        1 <= D <= 512, 1 <= K <= 2**20, the experts in blocks of the padded D under one fused matrix-core kernel; ``j`` in
+        the expressions is the global expert index.  Samplers of it run the engine's multi-pass path."""
+        W, b, params, q = tall_linear_arrays(W, b, params, expert_params)
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.kind = _lib.E_LINEAR_EXPR
+        self.nexperts, self.ndims = W.shape
+        self.params = params
+        self.W, self.b, self.expert_params = W, b, q
+        self.tall = True
+        h = ctypes.c_void_p()
+        check(ctx.lib.mjhmc_energy_create_linear_tall(
             ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), str(energy_expr).encode(), str(grad_expr).encode(),
             ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
             _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)

@@ -47,10 +47,10 @@ class Distribution(object):
             kind, params = self.device_energy()
             if kind == _lib.E_USER_EXPR:                   # params = (energy_expr, grad_expr, float64 parameters, stats, energy0_expr)
                 self._dev = engine.DeviceEnergy.from_expr(engine.context(device), self.ndims, *params)
-            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=)
-                self._dev = engine.DeviceEnergy.from_linear(engine.context(device), params['W'], params.get('b'),
-                                                            params['energy'], params['grad'], params.get('params', ()),
-                                                            params.get('expert_params'))
+            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=[, tall=])
+                make = engine.DeviceEnergy.from_linear_tall if params.get('tall') else engine.DeviceEnergy.from_linear
+                self._dev = make(engine.context(device), params['W'], params.get('b'), params['energy'], params['grad'],
+                                 params.get('params', ()), params.get('expert_params'))
             elif kind == _lib.E_HOST:                      # params = (energy_func, energy_grad_func): opaque callables
                 self._dev = engine.DeviceEnergy.host(engine.context(device), self.ndims, *params)
             else:
@@ -166,11 +166,16 @@ class LambdaDistribution(Distribution):
       (default: float64 state around the float32 force, as ProductOfT) or 'float32'.  Callables given as well are checked
       against the device energy at bind time at a float32-force bar: ``|dE| <= 1e-4 (1 + |E|)`` and
       ``max |d grad| <= 1e-4 max(1, max |grad|)`` on a few probe points;
+    * ``device_linear_tall=dict(W=, b=, energy=, grad=, params=(), expert_params=None)``: the same contract for a model
+      with more experts than dims -- W (K, D), D <= 512, K <= 2**20 (a GLM posterior: an expert per data row) -- on one
+      fused matrix-core kernel that walks the experts in blocks of the padded D (mjhmc_energy_create_linear_tall); ``j`` is
+      the global expert index.  Samplers run the engine's multi-pass path with either ``state_dtype``; the callables are
+      checked at the same float32-force bar;
     * ``device_energy=(kind, params)``: one of the built-in device energies by name.
     """
 
     def __init__(self, energy_func=None, energy_grad_func=None, init=None, name=None, device_energy=None,
-                 device_expr=None, device_params=(), device_linear=None, state_dtype='float64'):
+                 device_expr=None, device_params=(), device_linear=None, state_dtype='float64', device_linear_tall=None):
         self.energy_func = energy_func
         self.energy_grad_func = energy_grad_func
         self.init = np.array(init, dtype=np.float64)
@@ -178,16 +183,20 @@ class LambdaDistribution(Distribution):
         self._functor = device_energy
         self._checked = False
         self._bar32 = False
-        if device_linear is not None:
+        if device_linear is not None and device_linear_tall is not None:
+            raise ValueError('give device_linear or device_linear_tall, not both')
+        if device_linear is not None or device_linear_tall is not None:
+            tall = device_linear_tall is not None
             if state_dtype not in ('float32', 'float64'):
                 raise ValueError("device_linear state_dtype must be 'float32' or 'float64'")
             self.state_dtype = state_dtype
-            lin = dict(device_linear)
-            W, b, params, q = engine.linear_arrays(lin['W'], lin.get('b'), lin.get('params', ()), lin.get('expert_params'))
+            lin = dict(device_linear_tall if tall else device_linear)
+            W, b, params, q = engine.linear_arrays(lin['W'], lin.get('b'), lin.get('params', ()), lin.get('expert_params'),
+                                                   _tall=tall)
             if W.shape[1] != self.init.shape[0]:
                 raise ValueError('W has %d columns but init has %d dims' % (W.shape[1], self.init.shape[0]))
             self._functor = (_lib.E_LINEAR_EXPR, dict(W=W, b=b, energy=str(lin['energy']), grad=str(lin['grad']),
-                                                      params=params, expert_params=q))
+                                                      params=params, expert_params=q, **(dict(tall=True) if tall else {})))
             self._bar32 = True
         elif device_expr is not None:
             if isinstance(device_expr, dict):              # coupled through per-particle statistics S[k]
@@ -429,6 +438,119 @@ class CorrelatedGaussian(Distribution):
         import hashlib
         h = hashlib.sha1()
         for a in (self.precision, self.mean):
+            h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        return int(h.hexdigest()[:15], 16)
+
+
+class GeneralizedLinearModel(Distribution):
+    """Posterior of the coefficients x of a generalized linear model under the prior x ~ N(0, prior_scale^2 I):
+    ``features`` (n, D), ``targets`` (n,).  A linear-model energy of K = n + D experts -- the n data rows, then the prior
+    as D more experts with rows I / prior_scale and f = u^2 / 2:
+
+    * ``'gaussian'``: y ~ N(a.x, noise_scale^2); rows features / noise_scale, b = -targets / noise_scale, f = u^2 / 2;
+    * ``'logistic'``: y in {0, 1}, P(y = 1) = sigmoid(a.x); f = softplus(u) - y u, f' = sigmoid(u) - y;
+    * ``'poisson'``: y ~ Poisson(exp(a.x)); f = exp(u) - y u, f' = exp(u) - y  (constants in y dropped).
+
+    For the two non-Gaussian families the per-expert rows are q[0] = y and q[1] = 1 on the data rows, 0 on the prior rows
+    (the expressions select the prior's term by q[1]).  K > 512 runs as a tall model on the fused block kernel
+    (mjhmc_energy_create_linear_tall, D <= 512, K <= 2**20), K <= 512 on the tile kernels (mjhmc_energy_create_linear).
+    ``E_host`` / ``dEdX_host`` are the same energy in float64 NumPy; ``posterior()`` is exact for the Gaussian family.
+    ``gen_init_X`` draws N(0, init_scale^2) (from ``seed`` when given)."""
+
+    _PRIOR = ('0.5f*u*u', 'u')
+    _DATA = {
+        'logistic': ('(u > 20.f ? u : log1pf(expf(u))) - q[0]*u', '1.f/(1.f + expf(-u)) - q[0]'),
+        'poisson': ('expf(u) - q[0]*u', 'expf(u) - q[0]'),
+    }
+
+    def __init__(self, features, targets, family, prior_scale=1.0, noise_scale=1.0, nbatch=100, init_scale=0.1, seed=None,
+                 state_dtype='float64'):
+        if state_dtype not in ('float32', 'float64'):
+            raise ValueError("GeneralizedLinearModel state_dtype must be 'float32' or 'float64'")
+        if family not in ('gaussian', 'logistic', 'poisson'):
+            raise ValueError("family must be 'gaussian', 'logistic' or 'poisson', got %r" % (family,))
+        A = np.array(features, dtype=np.float64)
+        y = np.array(targets, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] < 1:
+            raise ValueError('features must be an (n, D) matrix, got shape %r' % (A.shape,))
+        n, D = A.shape
+        if y.shape != (n,):
+            raise ValueError('targets must have one entry per row of features (%d), got shape %r' % (n, y.shape))
+        if not (prior_scale > 0 and noise_scale > 0):
+            raise ValueError('prior_scale and noise_scale must be positive')
+        if family == 'logistic' and not np.all((y == 0) | (y == 1)):
+            raise ValueError('logistic targets must be 0 or 1')
+        if family == 'poisson' and np.any(y < 0):
+            raise ValueError('poisson targets must be non-negative')
+        self.features, self.targets, self.family = A, y, family
+        self.prior_scale, self.noise_scale = float(prior_scale), float(noise_scale)
+        self.init_scale, self.seed = float(init_scale), seed
+        prior = np.eye(D) / self.prior_scale
+        if family == 'gaussian':
+            self.W = np.vstack([A / self.noise_scale, prior])
+            self.b = np.concatenate([-y / self.noise_scale, np.zeros(D)])
+            self.q = None
+        else:
+            self.W = np.vstack([A, prior])
+            self.b = np.zeros(n + D)
+            self.q = np.vstack([np.concatenate([y, np.zeros(D)]), np.concatenate([np.ones(n), np.zeros(D)])])
+        engine.tall_linear_arrays(self.W, self.b, (), self.q)        # the size limits, before anything else
+        self.nexperts = n + D
+        self.state_dtype = state_dtype
+        self.backend = 'hip-mfma'
+        super(GeneralizedLinearModel, self).__init__(D, nbatch)
+
+    def device_energy(self):
+        if self.family == 'gaussian':
+            e, g = self._PRIOR
+        else:
+            (de, dg), (pe, pg) = self._DATA[self.family], self._PRIOR
+            e = 'q[1] != 0.f ? (%s) : (%s)' % (de, pe)
+            g = 'q[1] != 0.f ? (%s) : (%s)' % (dg, pg)
+        d = dict(W=self.W, b=self.b, energy=e, grad=g, params=(), expert_params=self.q)
+        if self.nexperts > 512:
+            d['tall'] = True
+        return (_lib.E_LINEAR_EXPR, d)
+
+    def _terms(self, X):
+        """u (K, n), f(u), f'(u) in float64"""
+        u = self.W.dot(np.asarray(X, dtype=np.float64)) + self.b[:, None]
+        f, fp = 0.5 * u * u, u.copy()
+        if self.family != 'gaussian':
+            nd = self.features.shape[0]
+            ud, yd = u[:nd], self.targets[:, None]
+            if self.family == 'logistic':
+                f[:nd] = np.logaddexp(0.0, ud) - yd * ud
+                fp[:nd] = 0.5 * (1.0 + np.tanh(0.5 * ud)) - yd        # sigmoid, without overflow
+            else:
+                f[:nd] = np.exp(ud) - yd * ud
+                fp[:nd] = np.exp(ud) - yd
+        return u, f, fp
+
+    def E_host(self, X):
+        return self._terms(X)[1].sum(axis=0).reshape((1, -1))
+
+    def dEdX_host(self, X):
+        return self.W.T.dot(self._terms(X)[2])
+
+    def posterior(self):
+        """(mean, cov) of the posterior; the Gaussian family only (the others have no closed form)"""
+        if self.family != 'gaussian':
+            raise NotImplementedError('posterior() is exact for the gaussian family only')
+        precision = self.W.T.dot(self.W)
+        cov = np.linalg.inv(precision)
+        cov = (cov + cov.T) / 2
+        return np.linalg.solve(precision, -self.W.T.dot(self.b)), cov
+
+    def gen_init_X(self):
+        rs = np.random if self.seed is None else np.random.RandomState(self.seed)
+        self.Xinit = self.init_scale * rs.randn(self.ndims, self.nbatch)
+
+    def __hash__(self):
+        import hashlib
+        h = hashlib.sha1()
+        h.update(self.family.encode())
+        for a in (self.features, self.targets, [self.prior_scale, self.noise_scale]):
             h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
         return int(h.hexdigest()[:15], 16)
 
