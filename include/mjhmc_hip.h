@@ -645,6 +645,55 @@ int mjhmc_crossmoments_info(mjhmc_crossmoments* h, int* ndims, int* n_values);
 /* frees the handle's device memory and its sums (NULL: nothing) */
 int mjhmc_crossmoments_destroy(mjhmc_crossmoments* h);
 
+/* Per-expert statistics of a linear-model energy over the recorded ensemble, on the device (csrc/pointwise.hip,
+ * csrc/dense_lin_pointwise.hpp): what the accumulators above do not report on -- the DATA ROWS of a regression, not its
+ * coefficients.  For an energy E(x) = sum_{j<K} f(u_j, j), u = W x + b (MJHMC_E_LINEAR_EXPR, square or tall), M <= 4 value
+ * expressions h_m(u, j; p, q) -- float32 C expressions of exactly the variables the energy expression sees, j the global
+ * expert index -- states x[k][p][:] (sample-ring slot x_slot0 + k, particle p < N) and weights w[k][p], the handle keeps
+ * per value m and expert j, with t = (double)h_m(u_j(x[k][p]), j) widened exactly,
+ *   W = sum w,   S1[m][j] = sum w t,   S2[m][j] = sum (w t) t,
+ * and, for the values whose bit of lme_mask is set, the pair (mx, se)[m][j]: mx = max t over the states with w > 0,
+ * se = sum w exp(t - mx), kept online (a new maximum rescales se by exp(mx_old - mx_new); two pairs merge as mx = max,
+ * se = se1 exp(mx1 - mx) + se2 exp(mx2 - mx); an expert that has seen no weight reads (-inf, 0)): log(se / W) + mx is the
+ * log of the weighted mean of exp(t), finite where a plain mean of exp underflows.  u is formed on the matrix cores by the
+ * first GEMM of the force, block of experts by block of experts, and never leaves the chip: the N x K matrix of values is
+ * not stored, the result is O(M K) numbers however long the run.  Sums in float64, every product rounded before its sum;
+ * a state of weight 0 is selected out, never multiplied.  No floating-point atomic: particles are cut into strips of a
+ * fixed number of tiles of 32 (mjhmc_pointwise_info), a strip's tiles are taken in ascending order, a slot's strips are
+ * added in ascending order, slots are added to the totals in slot order -- bit-identical from run to run, for every grid,
+ * and for every cut of a run into calls.
+ * Ownership as for mjhmc_estimator: the handle belongs to the sampler it was created on, mjhmc_sampler_destroy frees every
+ * one still alive and the handle is INVALID from then on; a re-allocated sample ring invalidates it.  The kernel is
+ * compiled with hipRTC around the values when the handle is created (code objects are cached per process by source);
+ * creating an energy compiles nothing of it.  No sampler state, counter or random stream is touched.
+ * mjhmc_pointwise_check: the compile alone, for a model of ndims x nexperts, with no device.
+ * MJHMC_ERR_INVALID: NULL arguments, no sample ring yet, no value or more than 4 (';'-separated), an empty value, mask
+ * bits beyond the M values, an expression that does not compile (the message is the compiler's log);
+ * MJHMC_ERR_UNSUPPORTED: an energy that is not MJHMC_E_LINEAR_EXPR (the message names its kind). */
+typedef struct mjhmc_pointwise mjhmc_pointwise;
+int mjhmc_pointwise_check(int ndims, int64_t nexperts, const char* values, const char* include_dir);
+int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_mask, const char* include_dir,
+                           mjhmc_pointwise** out);
+/* the number of values M, the number of experts K and the tiles of 32 particles in a strip (a constant of the library) */
+int mjhmc_pointwise_info(mjhmc_pointwise* h, int* n_values, int64_t* nexperts, int* strip_tiles);
+/* Adds the n states of slots [x_slot0, x_slot0 + n) to the sums with the weights of dwell-ring slots
+ * [w_slot0, w_slot0 + n), or unit weights for w_slot0 == -1: the pairing of mjhmc_estimator_accumulate (a jump sampler
+ * takes w_slot0 = x_slot0 + 1).  A float64 slot is narrowed to float32 rows first (what its force is given); a float32
+ * slot is read in place.  One read-back (one synchronisation) per call.  Rows p >= N are never counted.
+ * MJHMC_ERR_INVALID: slots outside the ring, n < 1, a ring re-allocated since create.
+ * MJHMC_ERR_NONFINITE: a weight that is negative or not finite, or a value that is not finite at a state of positive
+ * weight -- the message names the lowest such value index and, for it, the lowest expert.  A refused call has added
+ * nothing: it worked on a copy of the sums. */
+int mjhmc_pointwise_accumulate(mjhmc_pointwise* h, int x_slot0, int w_slot0, int n);
+/* The only download, none of the pointers NULL: W, S1[M * K], S2[M * K], lme_max[M * K], lme_sum[M * K] (row m = value m;
+ * (-inf, 0) where the mask did not ask) and the number of (slot, particle) states added so far. */
+int mjhmc_pointwise_read(mjhmc_pointwise* h, double* W, double* S1, double* S2, double* lme_max, double* lme_sum,
+                         int64_t* n_states);
+/* the sums back to (0, 0, 0, (-inf, 0)) and the count to 0 */
+int mjhmc_pointwise_reset(mjhmc_pointwise* h);
+/* frees the handle's device memory and its sums (NULL: nothing) */
+int mjhmc_pointwise_destroy(mjhmc_pointwise* h);
+
 /* Fair sample paths on a uniform time grid, kept on the device (csrc/timegrid.hip): the one result the weighted
  * accumulators above cannot give -- a fair sample with its time order kept.  The reference's sample(resample=True)
  * (markov_jump_hmc.py:293-338) pools particles and steps into one weighted draw ("preserve_order has no effect if

@@ -148,6 +148,14 @@ PROTOTYPES = {
     'mjhmc_crossmoments_reset': (ctypes.c_int, [_P]),
     'mjhmc_crossmoments_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'mjhmc_crossmoments_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_pointwise_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p]),
+    'mjhmc_pointwise_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_uint, ctypes.c_char_p, ctypes.POINTER(_P)]),
+    'mjhmc_pointwise_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_int)]),
+    'mjhmc_pointwise_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_pointwise_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_pointwise_reset': (ctypes.c_int, [_P]),
+    'mjhmc_pointwise_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_timegrid_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

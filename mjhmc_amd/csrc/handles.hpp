@@ -213,6 +213,7 @@ int multipass_iterate(mjhmc_sampler* s, int n_iter, const double* replay_normal,
                       const double* replay_unif, int ring_slot0, mjhmc_iter_stats* per_iter, int* n_done);
 int multipass_rollback(mjhmc_sampler* s);
 int round_rows32(mjhmc_sampler* s, void* rows);   // float64 rows -> float32 values (Shape::round32), api.hip
+void pot_narrow_rows32(const double* src, float* dst, int64_t n, hipStream_t st);   // dst[i] = (float)src[i], i < n
 int wide_leapfrog(mjhmc_sampler* w, const double* X, const double* V, double* Xo, double* Vo, double* G, double* EX,
                   double* EV, double eps, int n_steps);
 

@@ -608,6 +608,11 @@ int check_host(mjhmc_sampler* s) {
 
 }  // namespace
 
+// the float32 copy of float64 rows the float32 force reads (pot_eval_rows_f64), for the other readers of a float64 slot
+void pot_narrow_rows32(const double* src, float* dst, int64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(hk_narrow, grid1(n), dim3(256), 0, st, src, dst, n);
+}
+
 void host_traj_free(mjhmc_sampler* s) {
   HostTraj* t = s->ht;
   if (!t) return;

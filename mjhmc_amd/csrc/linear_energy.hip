@@ -95,6 +95,29 @@ std::string linear_tall_source(const std::string& energy_expr, const std::string
   return s;
 }
 
+// The per-expert statistics pass (dense_lin_pointwise.hpp): the caller's M value expressions as a
+// functor, and the one kernel around it -- a source of its own, compiled when a pointwise handle is created and never
+// when an energy is
+std::string linear_pointwise_source(const std::vector<std::string>& values) {
+  std::string s;
+  s += "#include \"dense_lin_pointwise.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += "// the caller's value expressions h_m(u, j; p, q) (u float, j int, p[k], q[m])\n";
+  s += "struct PwUserH {\n";
+  s += "  static constexpr int kM = " + std::to_string(values.size()) + ";\n";
+  s += "  template <int MI>\n";
+  s += "  static __device__ __forceinline__ float h(float u, int j, const float* __restrict__ p, LinQ q) {\n";
+  s += "    (void)u; (void)j; (void)p; (void)q;\n";
+  for (size_t m = 0; m < values.size(); ++m)
+    s += std::string(m ? "    else " : "    ") + "if constexpr (MI == " + std::to_string(m) + ") return (float)(" + values[m] + ");\n";
+  s += "    else return 0.f;\n  }\n";
+  s += "};\n";
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_pointwise_kernel(const PwArgs a, const LinTallModel tm, const PotLinear lin) {\n";
+  s += "  __shared__ Shared<NB> sh;\n  __shared__ double wts[kP];\n  lin_pointwise_items<NB, PwUserH>(a, tm, lin, sh, wts);\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
 int tall_pad(int ndims) { return ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim); }
 
 int resident_cus() {
@@ -302,4 +325,35 @@ void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
   void* params[] = {(void*)&a, (void*)&tm, (void*)&lin};
   (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The per-expert statistics pass of a linear model, square or tall (dense_lin_pointwise.hpp, pointwise.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+int linear_pointwise_dim(int ndims, int64_t nexperts) {
+  return nexperts > kPotDim ? tall_pad(ndims) : linear_dim(ndims, (int)nexperts);
+}
+
+int linear_pointwise_compile(const std::vector<std::string>& values, int dim, const std::string& include_dir,
+                             std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered) {
+  const int NB = dim / 128;
+  const std::string src = linear_pointwise_source(values);
+  const std::string key = src + "\n// pointwise, NB = " + std::to_string(NB) + ", -I" + include_dir;
+  std::lock_guard<std::mutex> lk(g_cache_mu);
+  auto it = g_cache.find(key);
+  if (it == g_cache.end()) {
+    std::unique_ptr<Compiled> c(new Compiled());
+    const int rc = rtc_compile(src, "mjhmc_linear_pointwise.hip", include_dir, {"mjhmc::lin_pointwise_kernel<" + std::to_string(NB) + ">"},
+                               &c->code, &c->lowered, err);
+    if (rc) {
+      const std::string energy_words = "the energy expressions do not compile:";
+      if (err->compare(0, energy_words.size(), energy_words) == 0)
+        *err = "the value expressions do not compile:" + err->substr(energy_words.size());
+      return rc;
+    }
+    it = g_cache.emplace(key, std::move(c)).first;
+  }
+  *code = &it->second->code;
+  *lowered = &it->second->lowered;
+  return 0;
 }

@@ -44,3 +44,11 @@ int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W,
                              int n_expert_rows, const char* include_dir);
 // E (or none) and dE/dX (or none) of float32 rows X32 [rows_pad][pad of ndims] (rows_pad a multiple of 32) on `st`
 void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st);
+
+// The per-expert statistics pass (dense_lin_pointwise.hpp, pointwise.hip): the padded dimension of the blocks a model of
+// (ndims, nexperts) is stored in (the tall layout beyond 512 experts, the square one otherwise; 0: no such model), and the
+// hipRTC compile of lin_pointwise_kernel<dim / 128> around 1 .. 4 value expressions (which of them keep a log-mean-exp is
+// a launch argument) -- its own source and cache key: creating an energy compiles none of it
+int linear_pointwise_dim(int ndims, int64_t nexperts);
+int linear_pointwise_compile(const std::vector<std::string>& values, int dim, const std::string& include_dir,
+                             std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered);

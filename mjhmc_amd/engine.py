@@ -496,6 +496,12 @@ class DeviceSampler(object):
         exist (ring_alloc); ndims <= 512; a host-evaluated energy is refused."""
         return DeviceCrossMoments(self)
 
+    def pointwise(self, values, log_mean_exp=None):
+        """Per-expert sums of 1 .. 4 value expressions h_m(u, j) of a linear-model energy over blocks of this sampler's
+        ring (mjhmc_pointwise_*): u = W x + b on the matrix cores, float64 sums per expert, a log-mean-exp where
+        ``log_mean_exp`` (one flag per value) asks.  The ring must exist (ring_alloc); another energy is refused."""
+        return DevicePointwise(self, values, log_mean_exp)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -625,6 +631,60 @@ class DeviceCrossMoments(_RingAccumulator):
         Sg, S2g, Sb, S2b, Cgg, Cgb = np.empty(D), np.empty(D), np.empty(K), np.empty(K), np.empty((D, D)), np.empty((D, K))
         self._call('read', ctypes.byref(W), ptr(Sg), ptr(S2g), ptr(Sb), ptr(S2b), ptr(Cgg), ptr(Cgb), ctypes.byref(n))
         return W.value, Sg, S2g, Sb, S2b, Cgg, Cgb, int(n.value)
+
+
+POINTWISE_MAX_VALUES = 4
+
+
+def pointwise_args(values, log_mean_exp=None):
+    """(the ';'-separated bytes of 1 .. 4 value expressions, the log-mean-exp bit mask) of a DevicePointwise; ValueError
+    for no value, more than 4, an empty one or one with a semicolon, and for flags that do not pair with the values"""
+    values = [values] if isinstance(values, str) else [str(v) for v in values]
+    if not 1 <= len(values) <= POINTWISE_MAX_VALUES:
+        raise ValueError('the pointwise statistics take 1 to %d value expressions, got %d' % (POINTWISE_MAX_VALUES, len(values)))
+    flags = [False] * len(values) if log_mean_exp is None else [bool(f) for f in np.atleast_1d(log_mean_exp)]
+    if len(flags) != len(values):
+        raise ValueError('log_mean_exp must have one flag per value (%d), got %d' % (len(values), len(flags)))
+    return join_exprs(values), sum(1 << m for m, f in enumerate(flags) if f)
+
+
+def pointwise_check(ndims, nexperts, values):
+    """Compile the pointwise kernel of an (ndims, nexperts) linear model around ``values`` with no device
+    (mjhmc_pointwise_check); a refused or uncompilable expression raises ValueError with the compiler's message."""
+    check_args(_lib.load().mjhmc_pointwise_check(int(ndims), int(nexperts), pointwise_args(values)[0],
+                                                 _lib.KERNEL_HEADERS.encode()))
+
+
+class DevicePointwise(_RingAccumulator):
+    """Per expert j of a linear-model energy and per value m: W = sum w, S1 = sum w t, S2 = sum (w t) t and, where
+    ``log_mean_exp`` asks, (mx, se) with mx = max t and se = sum w exp(t - mx), t = h_m(u_j, j) over the (slot, particle)
+    states of the ring blocks given to ``accumulate`` (include/mjhmc_hip.h: mjhmc_pointwise_*).  u = W x + b is formed on
+    the matrix cores and never stored; float64 sums, bit-identical from run to run and whatever the blocks."""
+    _kind = 'pointwise'
+
+    def __init__(self, dev, values, log_mean_exp=None):
+        exprs, mask = pointwise_args(values, log_mean_exp)
+        self.dev, self.lib, self.on = dev, dev.lib, None
+        h = ctypes.c_void_p()
+        check_args(self.lib.mjhmc_pointwise_create(dev.handle, exprs, mask, _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
+        self.handle = h
+        m, k, t = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
+        self._call('info', ctypes.byref(m), ctypes.byref(k), ctypes.byref(t))
+        self.n_values, self.nexperts, self.strip_tiles = int(m.value), int(k.value), int(t.value)
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A weight that is negative or not finite, or a value
+        that is not finite at a state of positive weight, raises EngineError (status -5) and adds nothing."""
+        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
+
+    def read(self):
+        """(W, S1 (M, K), S2 (M, K), lme_max (M, K), lme_sum (M, K), n_states)"""
+        shape = (self.n_values, self.nexperts)
+        W, n = ctypes.c_double(), ctypes.c_int64()
+        S1, S2, mx, se = np.empty(shape), np.empty(shape), np.empty(shape), np.empty(shape)
+        self._call('read', ctypes.byref(W), ptr(S1), ptr(S2), ptr(mx), ptr(se), ctypes.byref(n))
+        return W.value, S1, S2, mx, se, int(n.value)
 
 
 class DeviceChainStats(_RingAccumulator):

@@ -512,6 +512,33 @@ class GeneralizedLinearModel(Distribution):
             d['tall'] = True
         return (_lib.E_LINEAR_EXPR, d)
 
+    _FITTED = {'logistic': '1.f/(1.f + expf(-u))', 'poisson': 'expf(u)'}
+
+    def pointwise_values(self):
+        """(values, log_mean_exp flags) of ``sampler.pointwise()`` / ``waic()`` over all K = n + D experts: value 0 is the
+        pointwise log-likelihood l = -(energy expression), without the constants the energy leaves out
+        (``log_lik_constants``), with log-mean-exp on; value 1 is the fitted mean -- u (gaussian: the standardised
+        residual (a.x - y) / noise_scale, see ``fitted_from_value``), sigmoid(u) (logistic), exp(u) (poisson), and 0 on
+        the prior's experts of the two non-Gaussian families (selected by q[1] as the energy selects them)."""
+        energy = self.device_energy()[1]['energy']
+        fitted = 'u' if self.family == 'gaussian' else 'q[1] != 0.f ? (%s) : 0.f' % self._FITTED[self.family]
+        return ['-(%s)' % energy, fitted], [True, False]
+
+    def log_lik_constants(self):
+        """the n per-row constants of log p(y_i | x) that the energy drops"""
+        n = self.features.shape[0]
+        if self.family == 'gaussian':
+            return np.full(n, -np.log(self.noise_scale) - 0.5 * np.log(2 * np.pi))
+        if self.family == 'logistic':
+            return np.zeros(n)
+        from scipy.special import gammaln
+        return -gammaln(self.targets + 1.0)
+
+    def fitted_from_value(self, v):
+        """value 1 on the data rows -> the fitted mean of y: a.x = u noise_scale + y for the gaussian family"""
+        v = np.asarray(v, dtype=np.float64)
+        return v * self.noise_scale + self.targets if self.family == 'gaussian' else v
+
     def _terms(self, X):
         """u (K, n), f(u), f'(u) in float64"""
         u = self.W.dot(np.asarray(X, dtype=np.float64)) + self.b[:, None]

@@ -576,6 +576,102 @@ class SteinDiscrepancy(object):
         return float(np.mean(self.u[ok])) if ok.any() else float('nan')
 
 
+def merge_log_sum_exp(mx1, se1, mx2, se2):
+    """Two (max, sum of w exp(t - max)) pairs as one: mx = max(mx1, mx2), se = se1 exp(mx1 - mx) + se2 exp(mx2 - mx); an
+    empty pair is (-inf, 0) and two empty pairs stay empty (no -inf - (-inf) is formed).  Arrays broadcast."""
+    mx1, se1, mx2, se2 = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (mx1, se1, mx2, se2)))
+    mx = np.maximum(mx1, mx2)
+    base = np.where(np.isneginf(mx), 0.0, mx)               # (an empty pair has se = 0: its factor does not matter)
+    with np.errstate(under='ignore'):
+        se = se1 * np.exp(np.where(np.isneginf(mx1), -np.inf, mx1 - base)) + \
+            se2 * np.exp(np.where(np.isneginf(mx2), -np.inf, mx2 - base))
+    return mx, se
+
+
+class PointwiseStatistics(object):
+    """What ``pointwise()`` returns: statistics of M values h_m(u_j, j) per expert j of a linear-model energy over the
+    recorded ensemble, from the device sums (include/mjhmc_hip.h: mjhmc_pointwise_read) ``W`` = sum w, ``S1`` = sum w t,
+    ``S2`` = sum w t^2 and the pairs ``lme_max`` = max t, ``lme_sum`` = sum w exp(t - lme_max), each (M, K):
+
+      ``mean = S1 / W``
+      ``var = max(S2 / W - mean^2, 0)``                     the weighted POPULATION variance (no n - 1 correction)
+      ``log_mean_exp = log(lme_sum / W) + lme_max``         log of the weighted mean of exp(t), finite where exp(t)
+                                                            underflows; NaN in the rows that did not ask for it, -inf
+                                                            for an expert that has seen no weight
+
+    plus ``n_states``, the number of (slot, particle) states, ``total_weight`` = W and ``flags`` (which rows asked)."""
+
+    def __init__(self, W, S1, S2, lme_max, lme_sum, n_states, log_mean_exp):
+        self.W, self.S1, self.S2, self.lme_max, self.lme_sum = float(W), S1, S2, lme_max, lme_sum
+        self.total_weight, self.n_states = self.W, int(n_states)
+        self.flags = np.array([bool(f) for f in log_mean_exp], dtype=bool).reshape(-1)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.mean = S1 / self.W
+            self.var = np.maximum(S2 / self.W - self.mean * self.mean, 0.0)
+            self.log_mean_exp = np.where(np.isneginf(lme_max), -np.inf, np.log(lme_sum / self.W) + lme_max)
+        self.log_mean_exp[~self.flags] = np.nan
+
+
+class Waic(object):
+    """What ``waic()`` returns: the widely applicable information criterion of a model with pointwise log-likelihoods
+    l_i = log p(y_i | x), from a ``PointwiseStatistics`` whose value 0 is l_i without its constants (log-mean-exp on) and
+    whose value 1 is the fitted mean, on the first ``n_data`` experts (Gelman, Hwang and Vehtari 2014, sections 3.4-3.5):
+
+      ``lppd_i = log_mean_exp[0][i] + const_i``             log pointwise predictive density
+      ``p_waic_i = var[0][i]``                              effective number of parameters (their p_WAIC2) -- the weighted
+                                                            POPULATION variance over the S recorded states stands where
+                                                            they use the sample variance with S - 1
+      ``elpd_i = lppd_i - p_waic_i``
+      ``lppd``, ``p_waic``, ``elpd_waic``                   the sums over the rows;  ``waic = -2 elpd_waic``
+      ``se = sqrt(n_data * var_i(elpd_i))``                 standard error of elpd_waic over the rows
+      ``fitted``                                            posterior-predictive mean of every row (value 1)
+      ``n_warn``                                            rows with p_waic_i > 0.4: where WAIC is unreliable (Vehtari,
+                                                            Gelman and Gabry 2017)
+
+    and ``pointwise``, the statistics of all experts."""
+
+    def __init__(self, pointwise, n_data, constants, fitted=None):
+        n = int(n_data)
+        constants = np.broadcast_to(np.asarray(constants, dtype=np.float64), (n,))
+        self.pointwise, self.n_data = pointwise, n
+        self.lppd_i = pointwise.log_mean_exp[0, :n] + constants
+        self.p_waic_i = pointwise.var[0, :n].copy()
+        self.elpd_i = self.lppd_i - self.p_waic_i
+        self.lppd, self.p_waic, self.elpd_waic = float(self.lppd_i.sum()), float(self.p_waic_i.sum()), float(self.elpd_i.sum())
+        self.se = float(np.sqrt(n * np.var(self.elpd_i)))
+        self.waic = -2.0 * self.elpd_waic
+        self.fitted = pointwise.mean[1, :n].copy() if fitted is None else np.asarray(fitted, dtype=np.float64)
+        self.n_warn = int(np.sum(self.p_waic_i > 0.4))
+
+
+def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, compile_check=True):
+    """The checks ``pointwise()`` makes before anything runs, none of which needs a device: returns
+    (values, flags) or raises ValueError -- n_iter < 1, no value or more than 4, an energy that is not a linear model, an
+    expression that does not compile (with the compiler's message, mjhmc_pointwise_check)."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+    kind, params = distribution.device_energy()
+    if kind != _lib.E_LINEAR_EXPR:
+        names = dict((getattr(_lib, n), n[2:]) for n in dir(_lib) if n.startswith('E_') and isinstance(getattr(_lib, n), int))
+        raise ValueError('pointwise: the per-expert statistics are those of a linear-model energy (LINEAR_EXPR: '
+                         'device_linear, device_linear_tall, GeneralizedLinearModel); the energy of %s is %s'
+                         % (type(distribution).__name__, names.get(kind, kind)))
+    if values is None:
+        if not hasattr(distribution, 'pointwise_values'):
+            raise ValueError('pointwise: %s has no pointwise_values(); pass values=' % type(distribution).__name__)
+        if log_mean_exp is not None:
+            raise ValueError('log_mean_exp belongs to values=: the distribution\'s own values carry their flags')
+        values, log_mean_exp = distribution.pointwise_values()
+    values = [values] if isinstance(values, str) else [str(v) for v in values]
+    engine.pointwise_args(values, log_mean_exp)
+    flags = [False] * len(values) if log_mean_exp is None else [bool(f) for f in np.atleast_1d(log_mean_exp)]
+    if compile_check:
+        K, D = np.shape(params['W'])
+        engine.pointwise_check(D, K, values)
+    return values, flags
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -1201,6 +1297,69 @@ class HMCBase(object):
             if fn is not None:
                 fn.close()
         return ControlVariateExpectations(*(sums + (shift,)))
+
+    def pointwise(self, n_iter, values=None, log_mean_exp=None, block=None):
+        """Statistics of the DATA ROWS of a linear model over ``n_iter`` consecutive states of every particle: for the
+        experts j of the energy E = sum_j f(u_j, j), u = W x + b, and 1 .. 4 ``values`` h_m(u, j) -- float32 C expressions
+        of the variables the energy expression sees (``u``, ``j``, ``p[k]``, ``q[m]``) -- the weighted mean and variance of
+        every value at every expert and, where ``log_mean_exp`` (one flag per value) asks, the log of the weighted mean of
+        exp(value), kept as an online log-sum-exp.  u is formed on the matrix cores by the force's own first GEMM and is
+        never stored (csrc/dense_lin_pointwise.hpp): the host receives O(M K) numbers whatever the length of the run.
+        Returns a ``PointwiseStatistics``.  ``values=None`` takes ``self.distribution.pointwise_values()``.
+
+        The run is that of ``expectations(n_iter)``: the same iterations in blocks of ``block`` states, the same weights
+        (holding times for the jump samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the same
+        counters, ``dwelling_times`` and final state, bit for bit.  Nothing is added to ``E_count`` / ``dEdX_count``
+        (measurement, not sampling).  The results do not depend on ``block``, bit for bit.
+
+        ValueError, before anything runs: n_iter < 1, no value or more than 4, an energy that is not a linear model, an
+        expression that does not compile (with the compiler's message), a sharded sampler (summing over ranks is out of
+        scope here)."""
+        values, flags = pointwise_request(self.distribution, n_iter, values, log_mean_exp)
+        n_iter = int(n_iter)
+        if self._comm is not None:
+            raise ValueError('pointwise: a sharded sampler (comm set) is not supported -- the sums are additive over ranks, '
+                             'but summing them is out of scope here')
+        lead = 1 if self._dwell_weighted else 0
+        if block is None:
+            # the handle's float32 rows are at most one slot; its partials are (strips x 4 M x K) doubles
+            K = int(np.shape(self.distribution.device_energy()[1]['W'])[0])
+            strips = (int(self.nbatch) + 1023) // 1024
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False,
+                                                reserve_bytes=self._dev.ring_slot_bytes() + 32 * len(values) * (strips + 2) * (K + 512)) - lead
+        block = max(1, min(int(block), n_iter))
+        self._dev.ring_alloc(block + lead)
+        pw = None
+        try:
+            pw = self._dev.pointwise(values, flags)
+            for _, k in self._ring_blocks([n_iter], block):
+                pw.accumulate(0, k, w_slot0=1 if lead else -1)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            sums = pw.read()
+        finally:
+            if pw is not None:
+                pw.close()
+        return PointwiseStatistics(*(sums + (flags,)))
+
+    def waic(self, n_iter, block=None):
+        """WAIC of the model from ``pointwise(n_iter)`` with the distribution's own values: value 0 the pointwise
+        log-likelihood without its constants (log-mean-exp on), value 1 the fitted mean
+        (``distribution.pointwise_values()``), the constants from ``distribution.log_lik_constants()``, on the first
+        ``n_data`` experts (the data rows; the prior's experts are left out).  Returns a ``Waic`` -- ``elpd_waic``,
+        ``p_waic``, ``lppd``, ``se``, ``waic``, the per-row arrays, ``fitted`` and ``n_warn``.  Definitions: Gelman, Hwang and
+        Vehtari (2014); the weighted population variance of the recorded states stands where they use S - 1.  The run is
+        that of ``pointwise(n_iter)``.  ValueError for a distribution without those two methods."""
+        d = self.distribution
+        if not (hasattr(d, 'pointwise_values') and hasattr(d, 'log_lik_constants')):
+            raise ValueError('waic: %s has no pointwise_values() / log_lik_constants() (GeneralizedLinearModel has)'
+                             % type(d).__name__)
+        const = np.asarray(d.log_lik_constants(), dtype=np.float64)
+        pw = self.pointwise(n_iter, block=block)
+        n = const.shape[0]
+        fitted = d.fitted_from_value(pw.mean[1, :n]) if hasattr(d, 'fitted_from_value') else None
+        return Waic(pw, n, const, fitted)
 
     def _checked_shift(self, shift, of=None):
         shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
