@@ -694,6 +694,62 @@ int mjhmc_pointwise_reset(mjhmc_pointwise* h);
 /* frees the handle's device memory and its sums (NULL: nothing) */
 int mjhmc_pointwise_destroy(mjhmc_pointwise* h);
 
+/* Data-row influence of a linear-model energy, on the device (csrc/influence.hip, csrc/dense_lin_values.hpp): what ties a
+ * data row to a coefficient.  For an energy E(x) = sum_{j<K} f(u_j, j), u = W x + b (MJHMC_E_LINEAR_EXPR, square or tall),
+ * ONE value expression h(u, j; p, q) -- a float32 C expression of the variables a mjhmc_pointwise value sees -- the experts
+ * j0 <= j < j1, states x[k][p][:] (sample-ring slot x_slot0 + k, particle p < N), weights w[k][p] and two shifts cx (ndims
+ * doubles) and ct (j1 - j0 doubles), the handle keeps on the device, with t_j = (double)h(u_j(x[k][p]), j) widened exactly,
+ *   W = sum w,   Sx_d = sum w (x_d - cx_d),   S2x_d = sum w (x_d - cx_d)^2,
+ *   St_j = sum w (t_j - ct_j),   S2t_j = sum w (t_j - ct_j)^2,   Cxt_dj = sum w x_d (t_j - ct_j)
+ * all in float64: Cov(x_d, t_j) = Cxt_dj / W - (cx_d + Sx_d / W) (St_j / W).  x enters the cross sum about 0 and only t is
+ * shifted: with ct near the mean of t the sum has nothing large to cancel whatever the offset of x.  With t the pointwise
+ * log-likelihood of data row j, -Cov(x, t_j) is the first-order change of the posterior mean when row j is deleted.
+ * The experts are walked in panels of one block of the model's P = 128, 256 or 512 experts (mjhmc_influence_info): per
+ * slot and panel the first GEMM of the force forms u on the matrix cores, the values go to a float32 panel matrix
+ * [particles][P] (0 where w == 0, selected, never multiplied), and the moment pass of mjhmc_estimator and the cross pass
+ * of mjhmc_crossmoments run on it (a float64 state pairs with the panel widened exactly to float64).  The N x K matrix
+ * of values is never stored; scratch is a function of (N, ndims, P), not of K.  No floating-point atomic, one fixed order
+ * of sums; every slot is added to the totals separately and in slot order: bit-identical from run to run and for every cut
+ * of a run into calls.  Cxt exists once, ndims x (j1 - j0) doubles: a model of 2^20 experts is taken in ranges.
+ * Ownership as for mjhmc_estimator: the handle belongs to the sampler it was created on, mjhmc_sampler_destroy frees every
+ * one still alive and the handle is INVALID from then on; a re-allocated sample ring invalidates it.  The kernel is
+ * compiled with hipRTC around the value when the handle is created.  No gradient is evaluated; no sampler state, counter
+ * or random stream is touched.
+ * mjhmc_influence_check: the compile alone, for a model of ndims x nexperts, with no device.
+ * MJHMC_ERR_INVALID: NULL arguments, no sample ring yet, an empty value, more than one value (a ';'), an expression that
+ * does not compile (the message is the compiler's log), j0 < 0, j1 > K, j0 >= j1;
+ * MJHMC_ERR_UNSUPPORTED: an energy that is not MJHMC_E_LINEAR_EXPR (the message names its kind);
+ * MJHMC_ERR_HIP: the totals do not fit (the message gives their size in bytes). */
+typedef struct mjhmc_influence mjhmc_influence;
+int mjhmc_influence_check(int ndims, int64_t nexperts, const char* value, const char* include_dir);
+int mjhmc_influence_create(mjhmc_sampler* s, const char* value, int64_t j0, int64_t j1, const char* include_dir,
+                           mjhmc_influence** out);
+/* cx: ndims finite doubles, ct: j1 - j0 finite doubles, NULL = zero for either (the state at create).  Only while the
+ * handle is empty (MJHMC_ERR_INVALID after an accumulate; reset first). */
+int mjhmc_influence_set_shift(mjhmc_influence* h, const double* cx, const double* ct);
+/* ndims, the experts [j0, j1), the experts of a panel P and the bytes of scratch (the panel, the float32 rows and the
+ * widened panel of a float64 state, the partials of the passes): the same for every K at equal particles, ndims and P */
+int mjhmc_influence_info(mjhmc_influence* h, int* ndims, int64_t* j0, int64_t* j1, int* panel_experts, int64_t* scratch_bytes);
+/* Adds the n states of slots [x_slot0, x_slot0 + n) to the sums with the weights of dwell-ring slots
+ * [w_slot0, w_slot0 + n), or unit weights for w_slot0 == -1: the pairing of mjhmc_pointwise_accumulate (a jump sampler
+ * takes w_slot0 = x_slot0 + 1).  The call's n * N weights are checked first; then, slot by slot, the moments of the state
+ * and, panel by panel, the values, their moments and the cross pass.  One read-back (one synchronisation) per call.
+ * MJHMC_ERR_INVALID: slots outside the ring, n < 1, a ring re-allocated since create.
+ * MJHMC_ERR_NONFINITE: a weight that is negative or not finite -- nothing of the call has been added; or a value that is
+ * not finite at a state of positive weight -- the message names the lowest such expert, the sums may hold the value, and
+ * the handle refuses every further accumulate (MJHMC_ERR_INVALID) until mjhmc_influence_reset. */
+int mjhmc_influence_accumulate(mjhmc_influence* h, int x_slot0, int w_slot0, int n);
+/* None of the pointers NULL: W, Sx[ndims], S2x[ndims], St[j1 - j0], S2t[j1 - j0] and the number of (slot, particle)
+ * states added so far. */
+int mjhmc_influence_read(mjhmc_influence* h, double* W, double* Sx, double* S2x, double* St, double* S2t, int64_t* n_states);
+/* The columns j0 <= ja < jb <= j1 of Cxt into Cxt_out[ndims * (jb - ja)] (row-major, row d = state dimension d): a caller
+ * pages a wide range through a buffer of its own size.  MJHMC_ERR_INVALID for a range outside [j0, j1). */
+int mjhmc_influence_read_cross(mjhmc_influence* h, int64_t ja, int64_t jb, double* Cxt_out);
+/* zero the sums and the count, and lift the refusal a value that is not finite left; the shifts stay */
+int mjhmc_influence_reset(mjhmc_influence* h);
+/* frees the handle's device memory and its sums (NULL: nothing) */
+int mjhmc_influence_destroy(mjhmc_influence* h);
+
 /* Fair sample paths on a uniform time grid, kept on the device (csrc/timegrid.hip): the one result the weighted
  * accumulators above cannot give -- a fair sample with its time order kept.  The reference's sample(resample=True)
  * (markov_jump_hmc.py:293-338) pools particles and steps into one weighted draw ("preserve_order has no effect if

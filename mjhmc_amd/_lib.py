@@ -156,6 +156,18 @@ PROTOTYPES = {
     'mjhmc_pointwise_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
     'mjhmc_pointwise_reset': (ctypes.c_int, [_P]),
     'mjhmc_pointwise_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_influence_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p]),
+    'mjhmc_influence_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_char_p,
+                                              ctypes.POINTER(_P)]),
+    'mjhmc_influence_set_shift': (ctypes.c_int, [_P, _P, _P]),
+    'mjhmc_influence_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_influence_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_influence_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_influence_read_cross': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, _P]),
+    'mjhmc_influence_reset': (ctypes.c_int, [_P]),
+    'mjhmc_influence_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_timegrid_destroy': (ctypes.c_int, [_P]),
     'mjhmc_timegrid_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -76,6 +76,13 @@ struct mjhmc_energy {
   bool is_host() const { return ep.kind == MJHMC_E_HOST; }
 };
 
+// MJHMC_E_<name> of an energy kind, for the messages that refuse one (pointwise.hip, influence.hip)
+inline const char* energy_kind_name(int kind) {
+  static const char* const names[] = {"ISO_GAUSS", "DIAG_GAUSS", "ROUGH_WELL", "MM_GAUSS", "FUNNEL_NEAL", "FUNNEL_REF",
+                                      "PRODUCT_OF_T", "SPARSE_CODE", "USER_EXPR", "HOST", "LINEAR_EXPR"};
+  return kind >= 0 && kind < (int)(sizeof(names) / sizeof(names[0])) ? names[kind] : "unknown";
+}
+
 struct Shape {
   int E, logG, pitch, CH, esize;
   // ndims beyond the register-resident elementwise kernels (> 64 lanes x 16 elements): the sampler runs the multi-pass

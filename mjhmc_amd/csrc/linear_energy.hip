@@ -118,6 +118,24 @@ std::string linear_pointwise_source(const std::vector<std::string>& values) {
   return s;
 }
 
+// The values of one block of experts, stored (dense_lin_values.hpp): ONE value expression as a
+// functor and the one kernel around it -- a source and a cache key of its own, compiled when an influence handle is created
+std::string linear_values_source(const std::string& value) {
+  std::string s;
+  s += "#include \"dense_lin_values.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += "// the caller's value expression h(u, j; p, q) (u float, j int, p[k], q[m])\n";
+  s += "struct LvUserH {\n";
+  s += "  static __device__ __forceinline__ float h(float u, int j, const float* __restrict__ p, LinQ q) {\n";
+  s += "    (void)u; (void)j; (void)p; (void)q;\n";
+  s += "    return (float)(" + value + ");\n  }\n";
+  s += "};\n";
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_values_kernel(const LvArgs a, const LinTallModel tm, const PotLinear lin) {\n";
+  s += "  __shared__ Shared<NB> sh;\n  __shared__ double wts[kP];\n  lin_values_tiles<NB, LvUserH>(a, tm, lin, sh, wts);\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
 int tall_pad(int ndims) { return ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim); }
 
 int resident_cus() {
@@ -349,6 +367,33 @@ int linear_pointwise_compile(const std::vector<std::string>& values, int dim, co
       const std::string energy_words = "the energy expressions do not compile:";
       if (err->compare(0, energy_words.size(), energy_words) == 0)
         *err = "the value expressions do not compile:" + err->substr(energy_words.size());
+      return rc;
+    }
+    it = g_cache.emplace(key, std::move(c)).first;
+  }
+  *code = &it->second->code;
+  *lowered = &it->second->lowered;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The values of one block of experts, stored: the first half of the influence pass (dense_lin_values.hpp, influence.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+int linear_values_compile(const std::string& value, int dim, const std::string& include_dir, std::string* err,
+                          const std::vector<char>** code, const std::vector<std::string>** lowered) {
+  const int NB = dim / 128;
+  const std::string src = linear_values_source(value);
+  const std::string key = src + "\n// values, NB = " + std::to_string(NB) + ", -I" + include_dir;
+  std::lock_guard<std::mutex> lk(g_cache_mu);
+  auto it = g_cache.find(key);
+  if (it == g_cache.end()) {
+    std::unique_ptr<Compiled> c(new Compiled());
+    const int rc = rtc_compile(src, "mjhmc_linear_values.hip", include_dir, {"mjhmc::lin_values_kernel<" + std::to_string(NB) + ">"},
+                               &c->code, &c->lowered, err);
+    if (rc) {
+      const std::string energy_words = "the energy expressions do not compile:";
+      if (err->compare(0, energy_words.size(), energy_words) == 0)
+        *err = "the value expression does not compile:" + err->substr(energy_words.size());
       return rc;
     }
     it = g_cache.emplace(key, std::move(c)).first;

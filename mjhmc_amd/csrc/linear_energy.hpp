@@ -52,3 +52,8 @@ void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E
 int linear_pointwise_dim(int ndims, int64_t nexperts);
 int linear_pointwise_compile(const std::vector<std::string>& values, int dim, const std::string& include_dir,
                              std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered);
+
+// The values of one block of experts, stored (dense_lin_values.hpp, influence.hip): the hipRTC compile of
+// lin_values_kernel<dim / 128> around ONE value expression, dim from linear_pointwise_dim -- its own source and cache key
+int linear_values_compile(const std::string& value, int dim, const std::string& include_dir, std::string* err,
+                          const std::vector<char>** code, const std::vector<std::string>** lowered);

@@ -99,12 +99,6 @@ int checked_values(const char* values, std::vector<std::string>* out) {
   return 0;
 }
 
-const char* energy_kind_name(int kind) {
-  static const char* const names[] = {"ISO_GAUSS", "DIAG_GAUSS", "ROUGH_WELL", "MM_GAUSS", "FUNNEL_NEAL", "FUNNEL_REF",
-                                      "PRODUCT_OF_T", "SPARSE_CODE", "USER_EXPR", "HOST", "LINEAR_EXPR"};
-  return kind >= 0 && kind < (int)(sizeof(names) / sizeof(names[0])) ? names[kind] : "unknown";
-}
-
 }  // namespace
 
 struct mjhmc_pointwise : RingAccumulator {

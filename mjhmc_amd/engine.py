@@ -502,6 +502,12 @@ class DeviceSampler(object):
         ``log_mean_exp`` (one flag per value) asks.  The ring must exist (ring_alloc); another energy is refused."""
         return DevicePointwise(self, values, log_mean_exp)
 
+    def influence(self, value, experts=None):
+        """The cross moments of the state with one value h(u, j) per expert of a linear-model energy over blocks of this
+        sampler's ring (mjhmc_influence_*): what Cov(x_d, h(u_j)) is made of.  ``experts``: (j0, j1), None for all.  The
+        ring must exist (ring_alloc); another energy is refused."""
+        return DeviceInfluence(self, value, experts)
+
     def last_timing(self):
         t, k, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
         check(self.lib.mjhmc_last_timing(self.handle, ctypes.byref(t), ctypes.byref(k), ctypes.byref(n)), self.lib)
@@ -685,6 +691,76 @@ class DevicePointwise(_RingAccumulator):
         S1, S2, mx, se = np.empty(shape), np.empty(shape), np.empty(shape), np.empty(shape)
         self._call('read', ctypes.byref(W), ptr(S1), ptr(S2), ptr(mx), ptr(se), ctypes.byref(n))
         return W.value, S1, S2, mx, se, int(n.value)
+
+
+def influence_args(value):
+    """the bytes of the ONE value expression of a DeviceInfluence; ValueError for none, an empty one or more than one"""
+    values = [value] if isinstance(value, str) else [str(v) for v in value]
+    if len(values) != 1:
+        raise ValueError('the influence pass takes one value expression per pass, got %d' % len(values))
+    return join_exprs(values)
+
+
+def influence_check(ndims, nexperts, value):
+    """Compile the stored-values kernel of an (ndims, nexperts) linear model around ``value`` with no device
+    (mjhmc_influence_check); a refused or uncompilable expression raises ValueError with the compiler's message."""
+    check_args(_lib.load().mjhmc_influence_check(int(ndims), int(nexperts), influence_args(value),
+                                                 _lib.KERNEL_HEADERS.encode()))
+
+
+class DeviceInfluence(_RingAccumulator):
+    """The cross moments of the state with ONE value t_j = h(u_j, j) per expert j0 <= j < j1 of a linear-model energy
+    (include/mjhmc_hip.h: mjhmc_influence_*): W = sum w, Sx = sum w (x - cx), S2x = sum w (x - cx)^2, St = sum w (t - ct),
+    S2t = sum w (t - ct)^2 and Cxt = sum w x (t - ct)^T over the (slot, particle) states given to ``accumulate``.  u = W x + b
+    is formed on the matrix cores panel of experts by panel; float64 sums, bit-identical from run to run and whatever the
+    blocks."""
+    _kind = 'influence'
+
+    def __init__(self, dev, value, experts=None):
+        expr = influence_args(value)
+        self.dev, self.lib, self.on = dev, dev.lib, None
+        if experts is None:                                # all of them (an energy without experts is refused by name below)
+            experts = (0, int(getattr(dev.energy, 'nexperts', 0)))
+        j0, j1 = int(experts[0]), int(experts[1])
+        h = ctypes.c_void_p()
+        check_args(self.lib.mjhmc_influence_create(dev.handle, expr, j0, j1, _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
+        self.handle = h
+        d, a, b, p, sb = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int64()
+        self._call('info', ctypes.byref(d), ctypes.byref(a), ctypes.byref(b), ctypes.byref(p), ctypes.byref(sb))
+        self.ndims, self.experts = int(d.value), (int(a.value), int(b.value))
+        self.panel_experts, self.scratch_bytes = int(p.value), int(sb.value)
+        self.n_values = self.experts[1] - self.experts[0]
+
+    def set_shift(self, cx=None, ct=None):
+        """the shifts of the state sums and of the value sums (None: zero); only while the handle is empty"""
+        cx = None if cx is None else as_f64(np.asarray(cx, dtype=np.float64).reshape(-1), (self.ndims,))
+        ct = None if ct is None else as_f64(np.asarray(ct, dtype=np.float64).reshape(-1), (self.n_values,))
+        check_args(self.lib.mjhmc_influence_set_shift(self.handle, ptr(cx), ptr(ct)), self.lib)
+
+    def accumulate(self, x_slot0, n, w_slot0=-1):
+        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A weight that is negative or not finite raises
+        EngineError (status -5) and adds nothing; a value that is not finite at a state of positive weight raises naming
+        the lowest expert, and the handle refuses until ``reset``."""
+        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
+
+    def read(self):
+        """(W, Sx (D,), S2x (D,), St (J,), S2t (J,), n_states), J = j1 - j0"""
+        D, J = self.ndims, self.n_values
+        W, n = ctypes.c_double(), ctypes.c_int64()
+        Sx, S2x, St, S2t = np.empty(D), np.empty(D), np.empty(J), np.empty(J)
+        self._call('read', ctypes.byref(W), ptr(Sx), ptr(S2x), ptr(St), ptr(S2t), ctypes.byref(n))
+        return W.value, Sx, S2x, St, S2t, int(n.value)
+
+    def read_cross(self, ja=None, jb=None):
+        """Cxt (D, jb - ja): the columns of the experts ja <= j < jb (None: the handle's own range)"""
+        ja = self.experts[0] if ja is None else int(ja)
+        jb = self.experts[1] if jb is None else int(jb)
+        if not self.experts[0] <= ja < jb <= self.experts[1]:
+            raise ValueError('columns [%d, %d) are not a range inside the experts [%d, %d)' % ((ja, jb) + self.experts))
+        C = np.empty((self.ndims, jb - ja))
+        self._call('read_cross', ja, jb, ptr(C))
+        return C
 
 
 class DeviceChainStats(_RingAccumulator):

@@ -524,6 +524,17 @@ class GeneralizedLinearModel(Distribution):
         fitted = 'u' if self.family == 'gaussian' else 'q[1] != 0.f ? (%s) : 0.f' % self._FITTED[self.family]
         return ['-(%s)' % energy, fitted], [True, False]
 
+    def influence_value(self):
+        """the value of ``sampler.influence()``: value 0 of ``pointwise_values()``, the pointwise log-likelihood l of every
+        expert without its constants (they do not enter a covariance) -- on the first ``n_data`` experts the data rows,
+        on the last ndims the prior's terms"""
+        return self.pointwise_values()[0][0]
+
+    @property
+    def n_data(self):
+        """the experts that are data rows: the first n of the K = n + ndims"""
+        return int(self.features.shape[0])
+
     def log_lik_constants(self):
         """the n per-row constants of log p(y_i | x) that the energy drops"""
         n = self.features.shape[0]

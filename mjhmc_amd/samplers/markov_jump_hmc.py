@@ -672,6 +672,115 @@ def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, comp
     return values, flags
 
 
+class Influence(object):
+    """What ``influence()`` returns: how the experts j0 <= j < j1 of a linear-model energy (its data rows) move the
+    coefficients x, from the device sums (include/mjhmc_hip.h: mjhmc_influence_read, _read_cross) ``W`` = sum w,
+    ``Sx`` = sum w (x - cx), ``S2x`` = sum w (x - cx)^2, ``St`` = sum w (t - ct), ``S2t`` = sum w (t - ct)^2 and
+    ``Cxt`` = sum w x (t - ct)^T of shape (D, J), J = j1 - j0, t_j the value (the pointwise log-likelihood l_j):
+
+      ``mean_x = cx + Sx / W``, ``var_x``           of the coefficients; both variances are weighted POPULATION variances,
+      ``mean_t = ct + St / W``, ``var_t``           clipped at 0
+      ``cov = Cxt / W - mean_x (St / W)^T``         Cov(x_d, t_j), (D, J)
+      ``corr``                                      cov / sqrt(var_x var_t^T); 0 where a variance is 0
+      ``loo_shift = -cov``                          to first order E_{-j}[x] - E[x]: what deleting row j does to the
+                                                    posterior mean; ``loo_mean(j)`` = mean_x + loo_shift[:, j - j0]
+      ``ij_cov(rows=None, center=True)``            sum_j I_j I_j^T, I_j = cov[:, j]: the infinitesimal-jackknife covariance
+                                                    of the posterior mean (Giordano and Broderick), valid under
+                                                    misspecification; ``center`` takes the I_j about their mean over the rows
+      ``distance(precision)``                       I_j^T precision I_j per expert, (J,): a Cook's distance
+      ``most_influential(k, precision=None)``       the k experts of largest distance, largest first
+
+    Experts are named by their index in the model throughout (``rows``, ``j``, the result of ``most_influential``).
+    ``n_data``: the experts below it are data rows (None: all are); ``rows=None`` means those of them inside [j0, j1)."""
+
+    def __init__(self, W, Sx, S2x, St, S2t, Cxt, n_states, experts, cx, ct, n_data=None):
+        self.W, self.Sx, self.S2x, self.St, self.S2t, self.Cxt = float(W), Sx, S2x, St, S2t, Cxt
+        self.total_weight, self.n_states = self.W, int(n_states)
+        self.experts = (int(experts[0]), int(experts[1]))
+        self.cx, self.ct = np.asarray(cx, dtype=np.float64), np.asarray(ct, dtype=np.float64)
+        self.n_data = None if n_data is None else int(n_data)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mx, mt = Sx / self.W, St / self.W
+            self.mean_x, self.mean_t = self.cx + mx, self.ct + mt
+            self.var_x = np.maximum(S2x / self.W - mx * mx, 0.0)
+            self.var_t = np.maximum(S2t / self.W - mt * mt, 0.0)
+            self.cov = Cxt / self.W - np.outer(self.mean_x, mt)
+            scale = np.sqrt(np.outer(self.var_x, self.var_t))
+            self.corr = np.where(scale > 0, self.cov / np.where(scale > 0, scale, 1.0), 0.0)
+        self.loo_shift = -self.cov
+
+    def _columns(self, rows):
+        j0, j1 = self.experts
+        if rows is None:
+            rows = np.arange(j0, j1 if self.n_data is None else max(j0, min(j1, self.n_data)))
+        rows = np.atleast_1d(np.asarray(rows, dtype=np.int64))
+        if rows.size and (rows.min() < j0 or rows.max() >= j1):
+            raise ValueError('rows must be experts in [%d, %d)' % (j0, j1))
+        return rows - j0
+
+    def loo_mean(self, j):
+        """the first-order posterior mean without expert (data row) j"""
+        return self.mean_x + self.loo_shift[:, int(self._columns([j])[0])]
+
+    def ij_cov(self, rows=None, center=True):
+        I = self.cov[:, self._columns(rows)]
+        if center and I.shape[1]:
+            I = I - I.mean(axis=1, keepdims=True)
+        return I.dot(I.T)
+
+    def distance(self, precision):
+        P = np.asarray(precision, dtype=np.float64)
+        if P.shape != (self.cov.shape[0],) * 2:
+            raise ValueError('precision must be (%d, %d)' % ((self.cov.shape[0],) * 2))
+        return np.einsum('dj,de,ej->j', self.cov, P, self.cov)
+
+    def most_influential(self, k, precision=None):
+        """the k experts of largest ``distance``, largest first; ``precision=None`` takes diag(1 / var_x) (dimensions of
+        zero variance left out)"""
+        if precision is None:
+            with np.errstate(divide='ignore'):
+                precision = np.diag(np.where(self.var_x > 0, 1.0 / np.where(self.var_x > 0, self.var_x, 1.0), 0.0))
+        d = self.distance(precision)
+        order = np.argsort(-d, kind='stable')[:max(0, int(k))]
+        return order + self.experts[0]
+
+
+def influence_request(distribution, n_iter, value=None, experts=None, sharded=False, compile_check=True):
+    """The checks ``influence()`` makes before anything runs, none of which needs a device: returns (value, (j0, j1)) or
+    raises ValueError -- n_iter < 1, an energy that is not a linear model (named), a distribution without
+    ``influence_value()`` when no value is given, more than one value, experts that are not a range 0 <= j0 < j1 <= K, a
+    sharded sampler, an expression that does not compile (with the compiler's message, mjhmc_influence_check)."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+    kind, params = distribution.device_energy()
+    if kind != _lib.E_LINEAR_EXPR:
+        names = dict((getattr(_lib, n), n[2:]) for n in dir(_lib) if n.startswith('E_') and isinstance(getattr(_lib, n), int))
+        raise ValueError('influence: the influence of a data row is that of an expert of a linear-model energy (LINEAR_EXPR: '
+                         'device_linear, device_linear_tall, GeneralizedLinearModel); the energy of %s is %s'
+                         % (type(distribution).__name__, names.get(kind, kind)))
+    if value is None:
+        if not hasattr(distribution, 'influence_value'):
+            raise ValueError('influence: %s has no influence_value(); pass value=' % type(distribution).__name__)
+        value = distribution.influence_value()
+    if not isinstance(value, str):
+        value = list(value)
+        if len(value) != 1:
+            raise ValueError('influence: one value per pass, got %d (more than one value is more than one call)' % len(value))
+        value = str(value[0])
+    engine.influence_args(value)
+    K, D = np.shape(params['W'])
+    j0, j1 = (0, K) if experts is None else (int(experts[0]), int(experts[1]))
+    if j0 < 0 or j1 > K or j0 >= j1:
+        raise ValueError('influence: experts=(%d, %d) is not a range 0 <= j0 < j1 <= K of the model\'s K = %d' % (j0, j1, K))
+    if sharded:
+        raise ValueError('influence: a sharded sampler (comm set) is not supported -- the sums are additive over ranks, '
+                         'but summing them is out of scope here')
+    if compile_check:
+        engine.influence_check(D, K, value)
+    return value, (j0, j1)
+
+
 class HMCBase(object):
     """Hyper-parameters, counters and plumbing shared by all samplers (markov_jump_hmc.py:16-104)."""
 
@@ -1360,6 +1469,81 @@ class HMCBase(object):
         n = const.shape[0]
         fitted = d.fitted_from_value(pw.mean[1, :n]) if hasattr(d, 'fitted_from_value') else None
         return Waic(pw, n, const, fitted)
+
+    def influence(self, n_iter, value=None, experts=None, block=None, shift=None):
+        """How the DATA ROWS of a linear model move its coefficients, over ``n_iter`` consecutive states of every particle:
+        the (ndims, j1 - j0) matrix Cov(x_d, t_j) of the state with ONE value t_j = h(u_j, j) per expert -- a float32 C
+        expression of the variables a ``pointwise`` value sees; ``value=None`` takes ``distribution.influence_value()``, the
+        pointwise log-likelihood.  To first order -Cov(x, l_j) is what deleting row j does to the posterior mean, and
+        sum_j Cov(x, l_j) Cov(x, l_j)^T the infinitesimal-jackknife covariance of that mean.  u is formed on the matrix
+        cores panel of experts by panel; the values of one panel are stored, the N x K matrix never is
+        (csrc/dense_lin_values.hpp, csrc/influence.hip).  Returns an ``Influence``.  ``experts``: (j0, j1), None for all K.
+
+        The run is that of ``expectations(n_iter)``: the same iterations in blocks of ``block`` states, the same weights
+        (holding times for the jump samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the same
+        counters, ``dwelling_times`` and final state, bit for bit.  Nothing is added to ``E_count`` / ``dEdX_count``: no
+        gradient is evaluated.  Under a given ``shift`` the sums do not depend on ``block``, bit for bit.  ``shift``:
+        (cx, ct), the ndims and j1 - j0 numbers the sums of x and of t are taken about; None takes the first block's own
+        means (an estimator for x, the ``pointwise`` pass for t), at the price of reading that block twice.
+
+        ValueError, before anything runs: n_iter < 1, an energy that is not a linear model (named), a distribution without
+        ``influence_value()`` when ``value=None``, experts that are not a range inside the model, a sharded sampler, an
+        expression that does not compile (with the compiler's message)."""
+        value, (j0, j1) = influence_request(self.distribution, n_iter, value, experts, sharded=self._comm is not None)
+        n_iter = int(n_iter)
+        D, J = int(self.ndims), j1 - j0
+        if shift is not None:
+            cx = np.ascontiguousarray(np.asarray(shift[0], dtype=np.float64).reshape(-1))
+            ct = np.ascontiguousarray(np.asarray(shift[1], dtype=np.float64).reshape(-1))
+            if cx.shape != (D,) or ct.shape != (J,):
+                raise ValueError('shift must be (cx with ndims = %d entries, ct with %d entries)' % (D, J))
+            shift = (cx, ct)
+        lead = 1 if self._dwell_weighted else 0
+        w_slot0 = 1 if lead else -1
+        if block is None:
+            # the handle's panel, float32 rows and widened panel are at most two slots, the first block's pointwise handle
+            # half a slot and its partials; the totals are D x J doubles, the cross pass's partials at most ~2048 waves x 32 KiB
+            K = int(np.shape(self.distribution.device_energy()[1]['W'])[0])
+            strips = (int(self.nbatch) + 1023) // 1024
+            block = self._dev.ring_budget_slots(n_iter + lead, staging=False,
+                                                reserve_bytes=3 * self._dev.ring_slot_bytes() + (96 << 20) + 8 * D * J
+                                                + 16 * 1025 * (J // 128 + 2) + 32 * (strips + 2) * (K + 512)) - lead
+        block = max(1, min(int(block), n_iter))
+        self._dev.ring_alloc(block + lead)
+        inf = None
+        try:
+            inf = self._dev.influence(value, (j0, j1))
+            if shift is not None:
+                inf.set_shift(*shift)
+            for _, k in self._ring_blocks([n_iter], block):
+                if shift is None:                          # the first block's own means; neither handle touches the sampler
+                    est = pw = None
+                    try:
+                        est = self._dev.estimator(False)
+                        est.accumulate(0, k, w_slot0=w_slot0)
+                        W, S1 = est.read()[:2]
+                        pw = self._dev.pointwise([value], [False])
+                        pw.accumulate(0, k, w_slot0=w_slot0)
+                        Wt, T1 = pw.read()[:2]
+                    finally:
+                        if est is not None:
+                            est.close()
+                        if pw is not None:
+                            pw.close()
+                    shift = (S1 / W, np.ascontiguousarray(T1[0, j0:j1] / Wt))
+                    inf.set_shift(*shift)
+                inf.accumulate(0, k, w_slot0=w_slot0)
+            self._publish()
+            if lead:
+                self._read_dwell()
+            sums = inf.read()
+            Cxt = inf.read_cross()
+        finally:
+            if inf is not None:
+                inf.close()
+        W, Sx, S2x, St, S2t, n_states = sums
+        return Influence(W, Sx, S2x, St, S2t, Cxt, n_states, (j0, j1), shift[0], shift[1],
+                         n_data=getattr(self.distribution, 'n_data', None))
 
     def _checked_shift(self, shift, of=None):
         shift = np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1))
