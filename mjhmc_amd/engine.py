@@ -532,25 +532,23 @@ class DeviceSampler(object):
             pass
 
 
-class _RingAccumulator(object):
-    """What DeviceEstimator, DeviceChainStats, DeviceHistogram and DevicePairHistogram share: the handle created on the
-    sampler's ring or, with ``on``, on the derived ring of a DeviceFunctionals, ``reset`` and ``close``.  ``_kind`` names
-    the mjhmc_<kind>_* entry points."""
+class _RingHandle(object):
+    """The lifecycle every ring-statistics handle shares: created on the sampler's ring or, with ``on``, on the derived
+    ring of a DeviceFunctionals, and closed once.  ``_kind`` names the mjhmc_<kind>_* entry points."""
     _kind = None
+    on = None
 
-    def _create(self, dev, on, *args):
-        """mjhmc_<kind>_create(dev, *args, &handle), or mjhmc_<kind>_create_on(on, *args, &handle)"""
+    def _create(self, dev, on, *args, checker=check):
+        """mjhmc_<kind>_create(dev, *args, &handle), or mjhmc_<kind>_create_on(on, *args, &handle); ``checker``:
+        check_args where the wrapper promises ValueError for a refused argument"""
         self.dev, self.lib, self.on = dev, dev.lib, on
         h = ctypes.c_void_p()
         create = getattr(self.lib, 'mjhmc_%s_create%s' % (self._kind, '' if on is None else '_on'))
-        check(create((dev if on is None else on).handle, *(args + (ctypes.byref(h),))), self.lib)
+        checker(create((dev if on is None else on).handle, *(args + (ctypes.byref(h),))), self.lib)
         self.handle = h
 
     def _call(self, name, *args):
         check(getattr(self.lib, 'mjhmc_%s_%s' % (self._kind, name))(self.handle, *args), self.lib)
-
-    def reset(self):
-        self._call('reset')
 
     def close(self):
         if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None) and \
@@ -565,13 +563,15 @@ class _RingAccumulator(object):
             pass
 
 
-class _RingHistogram(_RingAccumulator):
-    """accumulate of the two histogram handles"""
+class _RingAccumulator(_RingHandle):
+    """A handle whose sums stay on the device between ``accumulate`` calls over blocks of the ring, until ``reset``"""
+
+    def reset(self):
+        self._call('reset')
 
     def accumulate(self, x_slot0, n, w_slot0=-1):
         """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A refused block (a weight that is not finite, negative
-        or too large for the quantum) raises and adds nothing."""
+        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  What a class refuses is in its own docstring."""
         self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
 
 
@@ -591,11 +591,6 @@ class DeviceEstimator(_RingAccumulator):
         c = None if c is None else as_f64(np.asarray(c, dtype=np.float64).reshape(-1), (self.ndims,))
         check(self.lib.mjhmc_estimator_set_shift(self.handle, ptr(c)), self.lib)
 
-    def accumulate(self, x_slot0, n, w_slot0=-1):
-        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1)."""
-        check(self.lib.mjhmc_estimator_accumulate(self.handle, int(x_slot0), int(w_slot0), int(n)), self.lib)
-
     def read(self):
         """(W, S1 (D,), S2 (D,), C (D, D) or None, n_states)"""
         D = self.ndims
@@ -610,7 +605,9 @@ class DeviceCrossMoments(_RingAccumulator):
     """The sums of the control variates g = dE/dX (include/mjhmc_hip.h: mjhmc_crossmoments_*): W = sum w, Sg = sum w g,
     S2g = sum w g^2, Cgg = sum w g g^T (the gradient about 0, its known mean), Sb = sum w (b - cb), S2b = sum w (b - cb)^2 and
     Cgb = sum w g (b - cb)^T over the (slot, particle) states given to ``accumulate``, b the state itself or, with ``on``,
-    the K values of a DeviceFunctionals; float64 throughout, bit-identical from run to run and whatever the blocks."""
+    the K values of a DeviceFunctionals; float64 throughout, bit-identical from run to run and whatever the blocks.
+    ``accumulate``: a weight that is not finite raises and adds nothing; a state, gradient or energy that is not finite
+    raises naming the slot, and the handle refuses until ``reset``."""
     _kind = 'crossmoments'
 
     def __init__(self, dev, on=None):
@@ -623,12 +620,6 @@ class DeviceCrossMoments(_RingAccumulator):
     def set_shift(self, cb=None):
         cb = None if cb is None else as_f64(np.asarray(cb, dtype=np.float64).reshape(-1), (self.n_values,))
         self._call('set_shift', ptr(cb))
-
-    def accumulate(self, x_slot0, n, w_slot0=-1):
-        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A weight that is not finite raises and adds nothing; a
-        state, gradient or energy that is not finite raises naming the slot, and the handle refuses until ``reset``."""
-        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
 
     def read(self):
         """(W, Sg (D,), S2g (D,), Sb (K,), S2b (K,), Cgg (D, D), Cgb (D, K), n_states)"""
@@ -665,24 +656,17 @@ class DevicePointwise(_RingAccumulator):
     """Per expert j of a linear-model energy and per value m: W = sum w, S1 = sum w t, S2 = sum (w t) t and, where
     ``log_mean_exp`` asks, (mx, se) with mx = max t and se = sum w exp(t - mx), t = h_m(u_j, j) over the (slot, particle)
     states of the ring blocks given to ``accumulate`` (include/mjhmc_hip.h: mjhmc_pointwise_*).  u = W x + b is formed on
-    the matrix cores and never stored; float64 sums, bit-identical from run to run and whatever the blocks."""
+    the matrix cores and never stored; float64 sums, bit-identical from run to run and whatever the blocks.
+    ``accumulate``: a weight that is negative or not finite, or a value that is not finite at a state of positive weight,
+    raises EngineError (status -5) and adds nothing."""
     _kind = 'pointwise'
 
     def __init__(self, dev, values, log_mean_exp=None):
         exprs, mask = pointwise_args(values, log_mean_exp)
-        self.dev, self.lib, self.on = dev, dev.lib, None
-        h = ctypes.c_void_p()
-        check_args(self.lib.mjhmc_pointwise_create(dev.handle, exprs, mask, _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
-        self.handle = h
+        self._create(dev, None, exprs, mask, _lib.KERNEL_HEADERS.encode(), checker=check_args)
         m, k, t = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
         self._call('info', ctypes.byref(m), ctypes.byref(k), ctypes.byref(t))
         self.n_values, self.nexperts, self.strip_tiles = int(m.value), int(k.value), int(t.value)
-
-    def accumulate(self, x_slot0, n, w_slot0=-1):
-        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A weight that is negative or not finite, or a value
-        that is not finite at a state of positive weight, raises EngineError (status -5) and adds nothing."""
-        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
 
     def read(self):
         """(W, S1 (M, K), S2 (M, K), lme_max (M, K), lme_sum (M, K), n_states)"""
@@ -713,18 +697,16 @@ class DeviceInfluence(_RingAccumulator):
     (include/mjhmc_hip.h: mjhmc_influence_*): W = sum w, Sx = sum w (x - cx), S2x = sum w (x - cx)^2, St = sum w (t - ct),
     S2t = sum w (t - ct)^2 and Cxt = sum w x (t - ct)^T over the (slot, particle) states given to ``accumulate``.  u = W x + b
     is formed on the matrix cores panel of experts by panel; float64 sums, bit-identical from run to run and whatever the
-    blocks."""
+    blocks.  ``accumulate``: a weight that is negative or not finite raises EngineError (status -5) and adds nothing; a
+    value that is not finite at a state of positive weight raises naming the lowest expert, and the handle refuses until
+    ``reset``."""
     _kind = 'influence'
 
     def __init__(self, dev, value, experts=None):
         expr = influence_args(value)
-        self.dev, self.lib, self.on = dev, dev.lib, None
         if experts is None:                                # all of them (an energy without experts is refused by name below)
             experts = (0, int(getattr(dev.energy, 'nexperts', 0)))
-        j0, j1 = int(experts[0]), int(experts[1])
-        h = ctypes.c_void_p()
-        check_args(self.lib.mjhmc_influence_create(dev.handle, expr, j0, j1, _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
-        self.handle = h
+        self._create(dev, None, expr, int(experts[0]), int(experts[1]), _lib.KERNEL_HEADERS.encode(), checker=check_args)
         d, a, b, p, sb = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int64()
         self._call('info', ctypes.byref(d), ctypes.byref(a), ctypes.byref(b), ctypes.byref(p), ctypes.byref(sb))
         self.ndims, self.experts = int(d.value), (int(a.value), int(b.value))
@@ -736,13 +718,6 @@ class DeviceInfluence(_RingAccumulator):
         cx = None if cx is None else as_f64(np.asarray(cx, dtype=np.float64).reshape(-1), (self.ndims,))
         ct = None if ct is None else as_f64(np.asarray(ct, dtype=np.float64).reshape(-1), (self.n_values,))
         check_args(self.lib.mjhmc_influence_set_shift(self.handle, ptr(cx), ptr(ct)), self.lib)
-
-    def accumulate(self, x_slot0, n, w_slot0=-1):
-        """States of ring slots [x_slot0, x_slot0 + n), weights of dwell slots [w_slot0, w_slot0 + n) (-1: unit weights;
-        a jump sampler's time average takes w_slot0 = x_slot0 + 1).  A weight that is negative or not finite raises
-        EngineError (status -5) and adds nothing; a value that is not finite at a state of positive weight raises naming
-        the lowest expert, and the handle refuses until ``reset``."""
-        self._call('accumulate', int(x_slot0), int(w_slot0), int(n))
 
     def read(self):
         """(W, Sx (D,), S2x (D,), St (J,), S2t (J,), n_states), J = j1 - j0"""
@@ -803,11 +778,12 @@ class DeviceChainStats(_RingAccumulator):
         return a0, a1, a2
 
 
-class DeviceHistogram(_RingHistogram):
+class DeviceHistogram(_RingAccumulator):
     """Per dimension d and bin b: count[d][b] states and mass[d][b] = sum of rint(w / quantum) over the (slot, particle)
     states of the ring blocks given to ``accumulate`` whose element x_d falls into bin b -- b = 0 below ``lo`` (and NaN),
     bins + 1 from ``hi`` on, 1 + int((x - lo) * (bins / (hi - lo))) between (include/mjhmc_hip.h: mjhmc_histogram_create).
-    Integer sums: bit-identical from run to run, whatever the blocks."""
+    Integer sums: bit-identical from run to run, whatever the blocks.  ``accumulate``: a refused block (a weight that is
+    not finite, negative or too large for the quantum) raises and adds nothing."""
     _kind = 'histogram'
 
     def __init__(self, dev, bins, lo, hi, quantum=1.0, on=None):
@@ -826,25 +802,23 @@ class DeviceHistogram(_RingHistogram):
         return count, mass, int(W.value), int(n.value)
 
 
-class DeviceTimeGrid(object):
+class DeviceTimeGrid(_RingAccumulator):
     """Per chain p a clock T[p] and a cursor j[p]; ``accumulate`` walks a block of ring slots in order and copies the state
     that holds at t_j = j * dt into grid slot j for every grid point its holding time covers (include/mjhmc_hip.h:
     mjhmc_timegrid_accumulate).  Grid, clocks and cursors are bit-identical to that sequence of float64 operations on the
     host, whatever the blocks."""
+    _kind = 'timegrid'
 
     def __init__(self, dev, n_grid, dt):
-        self.dev, self.lib = dev, dev.lib
         self.ndims, self.nparticles = dev.ndims, dev.nparticles
         self.n_grid, self.dt = int(n_grid), float(dt)
-        h = ctypes.c_void_p()
-        check(self.lib.mjhmc_timegrid_create(dev.handle, self.n_grid, self.dt, ctypes.byref(h)), self.lib)
-        self.handle = h
+        self._create(dev, None, self.n_grid, self.dt)
 
     def accumulate(self, x_slot0, n, w_slot0=-1):
         """States of ring slots [x_slot0, x_slot0 + n), holding times of dwell slots [w_slot0, w_slot0 + n) (-1: unit holding
         times; a jump sampler takes w_slot0 = x_slot0 + 1).  A refused block (a holding time that is not finite or is
         negative) raises and changes nothing."""
-        check(self.lib.mjhmc_timegrid_accumulate(self.handle, int(x_slot0), int(n), int(w_slot0)), self.lib)
+        self._call('accumulate', int(x_slot0), int(n), int(w_slot0))
 
     def progress(self):
         """(covered, max_filled): the grid slots complete for every chain, and for the chain that got furthest"""
@@ -879,31 +853,16 @@ class DeviceTimeGrid(object):
         check_args(self.lib.mjhmc_grid_lagcov(self.handle, int(slot0), int(n), max_lag, ptr(shift), ptr(A), ptr(S)), self.lib)
         return A, S
 
-    def reset(self):
-        check(self.lib.mjhmc_timegrid_reset(self.handle), self.lib)
 
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
-            self.lib.mjhmc_timegrid_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceStein(object):
+class DeviceStein(_RingHandle):
     """``evaluate`` returns (W, W2, S, Sd) of one ring slot: W = sum w, W2 = sum w^2, S = sum_ij w_i w_j k_p(x_i, x_j), Sd its
     diagonal, k_p the Stein kernel of the IMQ base kernel with scale ``c`` (include/mjhmc_hip.h: mjhmc_stein_evaluate).
     Float64 throughout, no floating-point atomics: bit-identical from run to run."""
+    _kind = 'stein'
 
     def __init__(self, dev, c):
-        self.dev, self.lib, self.c = dev, dev.lib, float(c)
-        h = ctypes.c_void_p()
-        check_args(self.lib.mjhmc_stein_create(dev.handle, self.c, ctypes.byref(h)), self.lib)
-        self.handle = h
+        self.c = float(c)
+        self._create(dev, None, self.c, checker=check_args)
 
     def evaluate(self, x_slot, w_slot=-1, n_use=None):
         """The first ``n_use`` particles (default: all) of ring slot ``x_slot`` with the weights of dwell slot ``w_slot`` (-1:
@@ -914,23 +873,12 @@ class DeviceStein(object):
         check_args(self.lib.mjhmc_stein_evaluate(self.handle, int(x_slot), int(w_slot), n_use, ptr(out)), self.lib)
         return tuple(float(v) for v in out)
 
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
-            self.lib.mjhmc_stein_destroy(self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DevicePairHistogram(_RingHistogram):
+class DevicePairHistogram(_RingAccumulator):
     """Per pair p = (i, j) and cell (b_j, b_i): count[p][b_j][b_i] states and mass[p][b_j][b_i] = sum of rint(w / quantum)
     over the (slot, particle) states of the ring blocks given to ``accumulate`` whose elements x_i, x_j fall into bins b_i,
     b_j of their axes -- per axis the bins of DeviceHistogram (include/mjhmc_hip.h: mjhmc_pairhist_create).  Integer sums:
-    bit-identical from run to run, whatever the blocks."""
+    bit-identical from run to run, whatever the blocks.  ``accumulate`` refuses what DeviceHistogram's refuses."""
     _kind = 'pairhist'
 
     def __init__(self, dev, pairs, bins, lo, hi, quantum=1.0, on=None):
@@ -961,11 +909,12 @@ def join_exprs(exprs):
     return ';'.join(str(e) for e in exprs).encode() if exprs else None
 
 
-class DeviceFunctionals(object):
+class DeviceFunctionals(_RingHandle):
     """K float64 values of every recorded state of a sampler, g[k] = value_k(S; p) with S[j] = sum_d stat_j(x_d, d; p),
     evaluated by one device pass from blocks of the sampler's ring into a derived ring of K-dimensional states
     (include/mjhmc_hip.h: mjhmc_functionals_create).  ``estimator``, ``chain_stats``, ``histogram`` and ``pair_histogram`` give the sampler's
     accumulators on the derived ring: their ``x_slot0`` counts derived slots, ``w_slot0`` the sampler's dwell slots."""
+    _kind = 'functionals'
 
     def __init__(self, dev, values, stats=(), params=(), _energy=False, _linear=None):
         self.dev, self.lib = dev, dev.lib
@@ -993,7 +942,7 @@ class DeviceFunctionals(object):
                                                     _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), self.lib)
         self.handle = h
         k, b = ctypes.c_int(), ctypes.c_uint64()
-        check(self.lib.mjhmc_functionals_info(h, ctypes.byref(k), ctypes.byref(b)), self.lib)
+        self._call('info', ctypes.byref(k), ctypes.byref(b))
         self.n_values, self.slot_bytes = int(k.value), int(b.value)
         self.ring_slots = 0
 
@@ -1011,18 +960,18 @@ class DeviceFunctionals(object):
 
     def ring_alloc(self, n_slots):
         """at least ``n_slots`` derived slots; a ring that grows is a new ring (handles created on the old one refuse)"""
-        check(self.lib.mjhmc_functionals_ring_alloc(self.handle, int(n_slots)), self.lib)
+        self._call('ring_alloc', int(n_slots))
         self.ring_slots = max(self.ring_slots, int(n_slots))
 
     def evaluate(self, x_slot0, n, out_slot0=0):
         """derived slots [out_slot0, out_slot0 + n) from the sampler's ring slots [x_slot0, x_slot0 + n); raises
         EngineError (MJHMC_ERR_NONFINITE) naming the value when one is not finite"""
-        check(self.lib.mjhmc_functionals_evaluate(self.handle, int(x_slot0), int(n), int(out_slot0)), self.lib)
+        self._call('evaluate', int(x_slot0), int(n), int(out_slot0))
 
     def read(self, slot0, n):
         """(K, n, N): the values of derived slots [slot0, slot0 + n)"""
         out = np.empty((self.n_values, int(n), self.nparticles))
-        check(self.lib.mjhmc_functionals_read(self.handle, int(slot0), int(n), ptr(out)), self.lib)
+        self._call('read', int(slot0), int(n), ptr(out))
         return out
 
     def estimator(self, want_cov=False):
@@ -1040,17 +989,6 @@ class DeviceFunctionals(object):
     def cross_moments(self):
         """the sampler's DeviceCrossMoments with b the K values of this derived ring (K <= 512)"""
         return DeviceCrossMoments(self.dev, on=self)
-
-    def close(self):
-        if getattr(self, 'handle', None) and getattr(self.dev, 'handle', None):   # (a closed sampler freed it already)
-            self.lib.mjhmc_functionals_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class HostEnergySampler(DeviceSampler):

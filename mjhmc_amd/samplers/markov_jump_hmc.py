@@ -1203,30 +1203,19 @@ class HMCBase(object):
         if self._comm is not None:
             raise ValueError('stein_discrepancy: a sharded sampler (comm set) is not supported -- pairs of particles '
                              'across ranks are not formed')
-        lead = 1 if self._dwell_weighted else 0
-        if block is None:
-            # the handle's dE/dX matrix is at most two slots (float32 gradient of a bfloat16 state); the partials are small
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False,
-                                                reserve_bytes=2 * self._dev.ring_slot_bytes()) - lead
-        block = max(1, min(int(block), n_iter))
-        self._dev.ring_alloc(block + lead)
-        st = None
+        # the handle's dE/dX matrix is at most two slots (float32 gradient of a bfloat16 state); the partials are small
+        reserve = lambda: 2 * self._dev.ring_slot_bytes()
         its, rows = [], []
-        try:
-            st = self._dev.stein(c)
+        with self._RecordedRun(self, [n_iter], block, reserve_bytes=reserve) as run:
+            st = run.own(self._dev.stein(c))
             done = 0
-            for _, k in self._ring_blocks([n_iter], block):
+            for _, k in run.blocks():
                 for j in range(k):
                     if (done + j) % every == 0:
                         its.append(done + j)
-                        rows.append(st.evaluate(j, 1 + j if lead else -1, particles))
+                        rows.append(st.evaluate(j, 1 + j if run.lead else -1, particles))
                 done += k
-            self._publish()
-            if lead:
-                self._read_dwell()
-        finally:
-            if st is not None:
-                st.close()
+            run.finish()
         rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
         return SteinDiscrepancy(its, rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], particles, c)
 
@@ -1278,19 +1267,8 @@ class HMCBase(object):
         if of is not None and shift is not None and np.size(shift) != of.n_values:
             raise ValueError('shift must have n_values = %d entries' % of.n_values)
         self._check_of(of)
-        lead = 1 if self._dwell_weighted else 0
-        if block is None:
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
-        block = max(1, min(int(block), n_iter))
-        if self._comm is not None:
-            # _run is collective for the jump samplers: every rank must walk the run in the same blocks, whatever its own
-            # free memory or the caller's argument on that rank say
-            block = int(self._comm.allreduce_ints([block], 'min')[0])
-        self._dev.ring_alloc(block + lead)
-        fn = est = None
-        try:
-            fn = None if of is None else self._open_functionals(of, block)
-            est = (self._dev if fn is None else fn).estimator(cov)
+        with self._RecordedRun(self, [n_iter], block, of) as run:
+            est = run.own(run.src.estimator(cov))
             if shift is not None:
                 shift = self._checked_shift(shift, of)
                 est.set_shift(shift)
@@ -1299,13 +1277,11 @@ class HMCBase(object):
                     # slot by slot, as the block was evaluated: the moment pass adds a call's sum to its running totals, so
                     # one call per slot makes W, S1 and S2 independent of how the run is cut into blocks, bit for bit
                     for j in range(k):
-                        est.accumulate(j, 1, w_slot0=1 + j if lead else -1)
+                        est.accumulate(j, 1, w_slot0=1 + j if run.lead else -1)
                 else:
-                    est.accumulate(0, k, w_slot0=1 if lead else -1)
+                    est.accumulate(0, k, w_slot0=run.w_slot0)
 
-            for _, k in self._ring_blocks([n_iter], block):
-                if fn is not None:
-                    fn.evaluate(0, k, 0)
+            for _, k in run.blocks():
                 accumulate(k)
                 if shift is None:                          # the first block's own mean, then the same block again about it
                     W, S1 = self._reduce_sums(est.read())[:2]
@@ -1313,15 +1289,8 @@ class HMCBase(object):
                     est.reset()
                     est.set_shift(shift)
                     accumulate(k)
-            self._publish()
-            if lead:
-                self._read_dwell()
+            run.finish()
             W, S1, S2, C, n_states = self._reduce_sums(est.read())
-        finally:
-            if est is not None:
-                est.close()
-            if fn is not None:
-                fn.close()
         return Expectations(W, S1, S2, C, n_states, shift)
 
     def cv_expectations(self, n_iter, of=None, block=None, shift=None):
@@ -1371,40 +1340,24 @@ class HMCBase(object):
         if self._comm is not None:
             raise ValueError('cv_expectations: a sharded sampler (comm set) is not supported -- the sums are additive over '
                              'ranks, but that is out of scope: it has not been proved on a multi-rank machine')
-        lead = 1 if self._dwell_weighted else 0
-        if block is None:
-            # the handle's dE/dX matrix is at most two slots (float32 gradient of a bfloat16 state); the partials of the
-            # covariance and cross passes are at most ~2048 waves x 32 KiB each
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of),
-                                                reserve_bytes=2 * self._dev.ring_slot_bytes() + (160 << 20)) - lead
-        block = max(1, min(int(block), n_iter))
-        self._dev.ring_alloc(block + lead)
-        fn = cm = None
-        try:
-            fn = None if of is None else self._open_functionals(of, block)
-            cm = (self._dev if fn is None else fn).cross_moments()
+        # the handle's dE/dX matrix is at most two slots (float32 gradient of a bfloat16 state); the partials of the
+        # covariance and cross passes are at most ~2048 waves x 32 KiB each
+        reserve = lambda: 2 * self._dev.ring_slot_bytes() + (160 << 20)
+        with self._RecordedRun(self, [n_iter], block, of, reserve_bytes=reserve) as run:
+            cm = run.own(run.src.cross_moments())
             if shift is not None:
                 shift = self._checked_shift(shift, of)
                 cm.set_shift(shift)
-            for _, k in self._ring_blocks([n_iter], block):
-                if fn is not None:
-                    fn.evaluate(0, k, 0)
-                cm.accumulate(0, k, w_slot0=1 if lead else -1)
+            for _, k in run.blocks():
+                cm.accumulate(0, k, w_slot0=run.w_slot0)
                 if shift is None:                          # the first block's own mean, then the same block again about it
                     sums = cm.read()
                     shift = sums[3] / sums[0]
                     cm.reset()
                     cm.set_shift(shift)
-                    cm.accumulate(0, k, w_slot0=1 if lead else -1)
-            self._publish()
-            if lead:
-                self._read_dwell()
+                    cm.accumulate(0, k, w_slot0=run.w_slot0)
+            run.finish()
             sums = cm.read()
-        finally:
-            if cm is not None:
-                cm.close()
-            if fn is not None:
-                fn.close()
         return ControlVariateExpectations(*(sums + (shift,)))
 
     def pointwise(self, n_iter, values=None, log_mean_exp=None, block=None):
@@ -1429,27 +1382,18 @@ class HMCBase(object):
         if self._comm is not None:
             raise ValueError('pointwise: a sharded sampler (comm set) is not supported -- the sums are additive over ranks, '
                              'but summing them is out of scope here')
-        lead = 1 if self._dwell_weighted else 0
-        if block is None:
+        def reserve():
             # the handle's float32 rows are at most one slot; its partials are (strips x 4 M x K) doubles
             K = int(np.shape(self.distribution.device_energy()[1]['W'])[0])
             strips = (int(self.nbatch) + 1023) // 1024
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False,
-                                                reserve_bytes=self._dev.ring_slot_bytes() + 32 * len(values) * (strips + 2) * (K + 512)) - lead
-        block = max(1, min(int(block), n_iter))
-        self._dev.ring_alloc(block + lead)
-        pw = None
-        try:
-            pw = self._dev.pointwise(values, flags)
-            for _, k in self._ring_blocks([n_iter], block):
-                pw.accumulate(0, k, w_slot0=1 if lead else -1)
-            self._publish()
-            if lead:
-                self._read_dwell()
+            return self._dev.ring_slot_bytes() + 32 * len(values) * (strips + 2) * (K + 512)
+
+        with self._RecordedRun(self, [n_iter], block, reserve_bytes=reserve) as run:
+            pw = run.own(self._dev.pointwise(values, flags))
+            for _, k in run.blocks():
+                pw.accumulate(0, k, w_slot0=run.w_slot0)
+            run.finish()
             sums = pw.read()
-        finally:
-            if pw is not None:
-                pw.close()
         return PointwiseStatistics(*(sums + (flags,)))
 
     def waic(self, n_iter, block=None):
@@ -1498,49 +1442,31 @@ class HMCBase(object):
             if cx.shape != (D,) or ct.shape != (J,):
                 raise ValueError('shift must be (cx with ndims = %d entries, ct with %d entries)' % (D, J))
             shift = (cx, ct)
-        lead = 1 if self._dwell_weighted else 0
-        w_slot0 = 1 if lead else -1
-        if block is None:
+        def reserve():
             # the handle's panel, float32 rows and widened panel are at most two slots, the first block's pointwise handle
             # half a slot and its partials; the totals are D x J doubles, the cross pass's partials at most ~2048 waves x 32 KiB
             K = int(np.shape(self.distribution.device_energy()[1]['W'])[0])
             strips = (int(self.nbatch) + 1023) // 1024
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False,
-                                                reserve_bytes=3 * self._dev.ring_slot_bytes() + (96 << 20) + 8 * D * J
-                                                + 16 * 1025 * (J // 128 + 2) + 32 * (strips + 2) * (K + 512)) - lead
-        block = max(1, min(int(block), n_iter))
-        self._dev.ring_alloc(block + lead)
-        inf = None
-        try:
-            inf = self._dev.influence(value, (j0, j1))
+            return (3 * self._dev.ring_slot_bytes() + (96 << 20) + 8 * D * J
+                    + 16 * 1025 * (J // 128 + 2) + 32 * (strips + 2) * (K + 512))
+
+        with self._RecordedRun(self, [n_iter], block, reserve_bytes=reserve) as run:
+            inf = run.own(self._dev.influence(value, (j0, j1)))
             if shift is not None:
                 inf.set_shift(*shift)
-            for _, k in self._ring_blocks([n_iter], block):
+            for _, k in run.blocks():
                 if shift is None:                          # the first block's own means; neither handle touches the sampler
-                    est = pw = None
-                    try:
-                        est = self._dev.estimator(False)
-                        est.accumulate(0, k, w_slot0=w_slot0)
-                        W, S1 = est.read()[:2]
-                        pw = self._dev.pointwise([value], [False])
-                        pw.accumulate(0, k, w_slot0=w_slot0)
-                        Wt, T1 = pw.read()[:2]
-                    finally:
-                        if est is not None:
-                            est.close()
-                        if pw is not None:
-                            pw.close()
+                    W, S1 = run.first_block_sums(k)[:2]
+                    pw = run.own(self._dev.pointwise([value], [False]))
+                    pw.accumulate(0, k, w_slot0=run.w_slot0)
+                    Wt, T1 = pw.read()[:2]
+                    run.release(pw).close()
                     shift = (S1 / W, np.ascontiguousarray(T1[0, j0:j1] / Wt))
                     inf.set_shift(*shift)
-                inf.accumulate(0, k, w_slot0=w_slot0)
-            self._publish()
-            if lead:
-                self._read_dwell()
+                inf.accumulate(0, k, w_slot0=run.w_slot0)
+            run.finish()
             sums = inf.read()
             Cxt = inf.read_cross()
-        finally:
-            if inf is not None:
-                inf.close()
         W, Sx, S2x, St, S2t, n_states = sums
         return Influence(W, Sx, S2x, St, S2t, Cxt, n_states, (j0, j1), shift[0], shift[1],
                          n_data=getattr(self.distribution, 'n_data', None))
@@ -1577,6 +1503,109 @@ class HMCBase(object):
                 yield seg, k
                 last, done, seg_done = k, done + k, seg_done + k
 
+    class _RecordedRun(object):
+        """The protocol every ring statistic runs, once: choose the block, size the ring, open ``of`` on it, walk
+        ``_ring_blocks``, publish, and close what was opened.
+
+            with self._RecordedRun(self, [n_iter], block, of, reserve_bytes) as run:
+                h = run.own(run.src.estimator(cov))        # closed on any exit, latest first, then the ``of`` handle
+                for seg, k in run.blocks():                # the block sits in slots 0 .. k - 1, ``of`` evaluated
+                    h.accumulate(0, k, w_slot0=run.w_slot0)
+                run.finish()                               # _publish, the dwelling times; then read the sums
+
+        ``reserve_bytes``: a number, or a callable that is asked only when the block comes from the budget.  ``src``: the
+        sampler's device or, with ``of``, its derived ring; ``lead``: 1 for the jump samplers (the lead slot).
+        ``early(run)``: handles that must exist before the budget is taken, because it is to count them (two-stage start:
+        ``head`` is what it returned on the final ring); ``early_keeps``: they have storage of their own."""
+
+        def __init__(self, sampler, segments, block, of=None, reserve_bytes=0, early=None, early_keeps=False):
+            self.sampler, self.segments, self.block, self.of, self.reserve_bytes = sampler, segments, block, of, reserve_bytes
+            self.early, self.early_keeps = early, early_keeps
+            self.lead = 1 if sampler._dwell_weighted else 0
+            self.w_slot0 = 1 if self.lead else -1
+            self.fn, self.src, self.head, self._owned = None, sampler._dev, None, []
+
+        def __enter__(self):
+            dev, lead = self.sampler._dev, self.lead
+            try:
+                if self.early is not None:
+                    dev.ring_alloc(1 + lead)               # (handles are created on a sampler that has its ring)
+                    self._open(1)
+                self.block = block = self._choose_block()
+                if self.early_keeps:
+                    dev.ring_alloc(block + lead)
+                elif self.early is None or block + lead > dev.ring_slots or \
+                        (self.fn is not None and block > self.fn.ring_slots):
+                    # a ring that grows is a new ring, and handles belong to the one they were created on: free them,
+                    # grow the ring by the budget that counted them, take them again (the functionals belong to the
+                    # sample ring in the same way, and the handles on them to the derived ring)
+                    self._close()
+                    dev.ring_alloc(block + lead)
+                    self._open(block)
+            except BaseException:
+                self._close()
+                raise
+            return self
+
+        def __exit__(self, *exc):
+            self._close()
+
+        def _choose_block(self):
+            s, n, block = self.sampler, self.segments[0], self.block
+            if block is None:
+                extra = s._extra_slot_bytes(self.of)
+                reserve = self.reserve_bytes() if callable(self.reserve_bytes) else self.reserve_bytes
+                block = s._dev.ring_budget_slots(n + self.lead, staging=False, extra_bytes=extra,
+                                                 reserve_bytes=reserve) - self.lead
+            block = max(1, min(int(block), n))
+            if s._comm is not None:
+                # _run is collective for the jump samplers: every rank must walk the run in the same blocks, whatever its
+                # own free memory or the caller's argument on that rank say
+                block = int(s._comm.allreduce_ints([block], 'min')[0])
+            return block
+
+        def _open(self, n_slots):
+            if self.of is not None:
+                self.fn = self.src = self.sampler._open_functionals(self.of, n_slots)
+            if self.early is not None:
+                self.head = self.early(self)
+
+        def _close(self):
+            while self._owned:
+                self._owned.pop().close()
+            if self.fn is not None:
+                self.fn.close()
+            self.fn, self.src, self.head = None, self.sampler._dev, None
+
+        def own(self, handle):
+            self._owned.append(handle)
+            return handle
+
+        def release(self, handle):
+            """``handle`` leaves the run open: its caller closes it"""
+            self._owned.remove(handle)
+            return handle
+
+        def blocks(self):
+            for seg, k in self.sampler._ring_blocks(self.segments, self.block):
+                if self.fn is not None:
+                    self.fn.evaluate(0, k, 0)
+                yield seg, k
+
+        def first_block_sums(self, k):
+            """One throw-away moment pass over the block in slots 0 .. k - 1 (the first: for a shift, a range, a quantum or
+            a dt that the caller did not give): (W, S1, S2, None, n_states), summed over ranks."""
+            est = self.own(self.src.estimator(False))
+            est.accumulate(0, k, w_slot0=self.w_slot0)
+            sums = self.sampler._reduce_sums(est.read())
+            self.release(est).close()
+            return sums
+
+        def finish(self):
+            self.sampler._publish()
+            if self.lead:
+                self.sampler._read_dwell()
+
     def diagnostics(self, n_iter, split=True, block=None, shift=None, of=None):
         """R-hat and the multi-chain effective sample size of ``n_iter`` consecutive states of every particle, every
         particle being one chain: per-chain sums kept on the device (csrc/chainstats.hip), O(ndims) numbers to the host
@@ -1605,58 +1634,23 @@ class HMCBase(object):
         elif shift is not None and np.size(shift) != self.ndims:
             raise ValueError('shift must have ndims = %d entries' % self.ndims)
         self._check_of(of)
-        lead = 1 if self._dwell_weighted else 0
         segments = [n_iter // 2, n_iter // 2] if split else [n_iter]
         grad0 = self.distribution.dEdX_count
-        self._dev.ring_alloc(1 + lead)                     # (the sums have the ring's row layout: it must exist)
-        fn = cs = None
-        try:
-            fn = None if of is None else self._open_functionals(of, 1)
-            cs = (self._dev if fn is None else fn).chain_stats(len(segments))
-            if block is None:
-                block = self._dev.ring_budget_slots(segments[0] + lead, staging=False,
-                                                    extra_bytes=self._extra_slot_bytes(of)) - lead
-            block = max(1, min(int(block), segments[0]))
-            if self._comm is not None:
-                block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
-            if block + lead > self._dev.ring_slots or (fn is not None and block > fn.ring_slots):
-                # a ring that grows is a new ring, and the sums belong to the one they were created on: free them, grow
-                # the ring by the budget that counted them, take them again (the functionals belong to the sample ring
-                # in the same way, and the sums on them to the derived ring)
-                cs.close()
-                cs = None
-                if fn is not None:
-                    fn.close()
-                    fn = None
-                self._dev.ring_alloc(block + lead)
-                fn = None if of is None else self._open_functionals(of, block)
-                cs = (self._dev if fn is None else fn).chain_stats(len(segments))
+        # (the per-chain sums have the ring's row layout and take memory: they exist before the budget is taken)
+        with self._RecordedRun(self, segments, block, of,
+                               early=lambda run: run.own(run.src.chain_stats(len(segments)))) as run:
+            cs = run.head
             if shift is not None:
                 shift = self._checked_shift(shift, of)
                 cs.set_shift(shift)
-            w_slot0 = 1 if lead else -1
-            for part, k in self._ring_blocks(segments, block):
-                if fn is not None:
-                    fn.evaluate(0, k, 0)
+            for part, k in run.blocks():
                 if shift is None:
-                    est = (self._dev if fn is None else fn).estimator(False)
-                    try:
-                        est.accumulate(0, k, w_slot0=w_slot0)
-                        W, S1 = self._reduce_sums(est.read())[:2]
-                    finally:
-                        est.close()
+                    W, S1 = run.first_block_sums(k)[:2]
                     shift = S1 / W
                     cs.set_shift(shift)
-                cs.accumulate(0, k, w_slot0=w_slot0, part=part)
-            self._publish()
-            if lead:
-                self._read_dwell()
+                cs.accumulate(0, k, w_slot0=run.w_slot0, part=part)
+            run.finish()
             parts = [cs.read(h) for h in range(len(segments))]
-        finally:
-            if cs is not None:
-                cs.close()
-            if fn is not None:
-                fn.close()
         if self._comm is not None:
             from ..parallel import reduce_chain_sums
             parts = reduce_chain_sums(self._comm, parts)
@@ -1679,11 +1673,19 @@ class HMCBase(object):
         evaluated into a derived ring first; ``range`` entries are scalars or K-vectors, and the range=None moment pass,
         ``span`` and the quantum rule apply to the values)."""
         n_iter, bins = int(n_iter), int(bins)
-        K = self.ndims if of is None else of.n_values
         if n_iter < 1:
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
         if not 1 <= bins <= 1024:
             raise ValueError('bins must be in [1, 1024], got %d' % bins)
+        lo, hi, q, sums = self._histograms(n_iter, range, block, span, of,
+                                           lambda src, lo, hi, q: src.histogram(bins, lo, hi, q))
+        return Marginals(lo, hi, bins, q, *sums)
+
+    def _histograms(self, n_iter, range, block, span, of, create):
+        """The run of marginals() and joint_marginals(): the range check, the first block's range and quantum, rank 0's
+        [lo | hi | q] for all ranks, the handle from ``create(src, lo, hi, q)``, the accumulation, and the tables added over
+        ranks.  Returns (lo, hi, q, (counts, units, W_units, n_states)), lo and hi per dimension."""
+        K = self.ndims if of is None else of.n_values
         if range is not None:
             if len(range) != 2:
                 raise ValueError('range must be (lo, hi)')
@@ -1696,30 +1698,13 @@ class HMCBase(object):
         elif not span > 0:
             raise ValueError('span must be positive')
         self._check_of(of)
-        lead = 1 if self._dwell_weighted else 0
-        if block is None:
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
-        block = max(1, min(int(block), n_iter))
-        if self._comm is not None:
-            block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
-        self._dev.ring_alloc(block + lead)
-        w_slot0 = 1 if lead else -1
-        fn, hist, q = None, None, 1.0
-        try:
-            fn = None if of is None else self._open_functionals(of, block)
-            src = self._dev if fn is None else fn
-            for _, k in self._ring_blocks([n_iter], block):
-                if fn is not None:
-                    fn.evaluate(0, k, 0)
+        hist, q = None, 1.0
+        with self._RecordedRun(self, [n_iter], block, of) as run:
+            for _, k in run.blocks():
                 if hist is None:
-                    if range is None or lead:
-                        est = src.estimator(False)
-                        try:
-                            est.accumulate(0, k, w_slot0=w_slot0)
-                            W, S1, S2, _, n_first = self._reduce_sums(est.read())
-                        finally:
-                            est.close()
-                        if lead:
+                    if range is None or run.lead:
+                        W, S1, S2, _, n_first = run.first_block_sums(k)
+                        if run.lead:
                             q = 2.0 ** (np.floor(np.log2(W / n_first)) - 24)
                         if range is None:
                             mean = S1 / W
@@ -1729,21 +1714,14 @@ class HMCBase(object):
                     if self._comm is not None:
                         packed = self._comm.bcast(np.concatenate([lo, hi, [q]]), 0)
                         lo, hi, q = packed[:K].copy(), packed[K:2 * K].copy(), float(packed[-1])
-                    hist = src.histogram(bins, lo, hi, q)
-                hist.accumulate(0, k, w_slot0=w_slot0)
-            self._publish()
-            if lead:
-                self._read_dwell()
-            counts, units, W_units, n_states = hist.read()
-        finally:
-            if hist is not None:
-                hist.close()
-            if fn is not None:
-                fn.close()
+                    hist = run.own(create(run.src, lo, hi, q))
+                hist.accumulate(0, k, w_slot0=run.w_slot0)
+            run.finish()
+            sums = hist.read()
         if self._comm is not None:
             from ..parallel import reduce_histogram
-            counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
-        return Marginals(lo, hi, bins, q, counts, units, W_units, n_states)
+            sums = reduce_histogram(self._comm, *sums)
+        return lo, hi, q, sums
 
     def joint_marginals(self, n_iter, pairs, bins=64, range=None, block=None, span=8.0, of=None):
         """Weighted joint histograms of ``pairs`` [(i, j), ...] of dimensions over ``n_iter`` consecutive states of every
@@ -1761,7 +1739,6 @@ class HMCBase(object):
         is evaluated into a derived ring first; ``range`` entries are scalars or K-vectors)."""
         n_iter, bins = int(n_iter), int(bins)
         K = self.ndims if of is None else of.n_values
-        what = 'ndims' if of is None else 'n_values'
         if n_iter < 1:
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
         if not 1 <= bins <= 128:
@@ -1771,67 +1748,10 @@ class HMCBase(object):
             raise ValueError('pairs must be 1 .. 64 pairs (i, j) of integers, got an array of shape %r' % (pairs.shape,))
         pairs = pairs.astype(np.int64)
         if pairs.min() < 0 or pairs.max() >= K:
-            raise ValueError('pairs must index [0, %s = %d)' % (what, K))
-        if range is not None:
-            if len(range) != 2:
-                raise ValueError('range must be (lo, hi)')
-            lo, hi = [np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (K,))) if np.size(v) in (1, K)
-                      else None for v in range]
-            if lo is None or hi is None:
-                raise ValueError('lo and hi must be scalars or have %s = %d entries' % (what, K))
-            if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-                raise ValueError('range needs finite lo < hi in every dimension')
-        elif not span > 0:
-            raise ValueError('span must be positive')
-        self._check_of(of)
-        lead = 1 if self._dwell_weighted else 0
-        if block is None:
-            block = self._dev.ring_budget_slots(n_iter + lead, staging=False, extra_bytes=self._extra_slot_bytes(of)) - lead
-        block = max(1, min(int(block), n_iter))
-        if self._comm is not None:
-            block = int(self._comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
-        self._dev.ring_alloc(block + lead)
-        w_slot0 = 1 if lead else -1
-        fn, hist, q = None, None, 1.0
-        try:
-            fn = None if of is None else self._open_functionals(of, block)
-            src = self._dev if fn is None else fn
-            for _, k in self._ring_blocks([n_iter], block):
-                if fn is not None:
-                    fn.evaluate(0, k, 0)
-                if hist is None:
-                    if range is None or lead:
-                        est = src.estimator(False)
-                        try:
-                            est.accumulate(0, k, w_slot0=w_slot0)
-                            W, S1, S2, _, n_first = self._reduce_sums(est.read())
-                        finally:
-                            est.close()
-                        if lead:
-                            q = 2.0 ** (np.floor(np.log2(W / n_first)) - 24)
-                        if range is None:
-                            mean = S1 / W
-                            sd = np.sqrt(np.maximum(S2 / W - mean * mean, 0.0))
-                            sd = np.where(sd > 0, sd, 1.0)             # (a constant coordinate still needs lo < hi)
-                            lo, hi = mean - span * sd, mean + span * sd
-                    if self._comm is not None:
-                        packed = self._comm.bcast(np.concatenate([lo, hi, [q]]), 0)
-                        lo, hi, q = packed[:K].copy(), packed[K:2 * K].copy(), float(packed[-1])
-                    hist = src.pair_histogram(pairs, bins, lo[pairs], hi[pairs], q)
-                hist.accumulate(0, k, w_slot0=w_slot0)
-            self._publish()
-            if lead:
-                self._read_dwell()
-            counts, units, W_units, n_states = hist.read()
-        finally:
-            if hist is not None:
-                hist.close()
-            if fn is not None:
-                fn.close()
-        if self._comm is not None:
-            from ..parallel import reduce_histogram
-            counts, units, W_units, n_states = reduce_histogram(self._comm, counts, units, W_units, n_states)
-        return JointMarginals(pairs, lo[pairs], hi[pairs], bins, q, counts, units, W_units, n_states)
+            raise ValueError('pairs must index [0, %s = %d)' % ('ndims' if of is None else 'n_values', K))
+        lo, hi, q, sums = self._histograms(n_iter, range, block, span, of,
+                                           lambda src, lo, hi, q: src.pair_histogram(pairs, bins, lo[pairs], hi[pairs], q))
+        return JointMarginals(pairs, lo[pairs], hi[pairs], bins, q, *sums)
 
     def paths(self, n_iter, n_grid=None, dt=None, block=None):
         """A fair sample of every chain with its time order kept: the process "chain p sits in state k for its holding
@@ -1856,42 +1776,28 @@ class HMCBase(object):
             raise ValueError('n_grid must be >= 1, got %d' % n_grid)
         if dt is not None and not (np.isfinite(dt) and dt > 0):
             raise ValueError('dt must be finite and positive, got %r' % (dt,))
-        lead = 1 if self._dwell_weighted else 0
-        w_slot0 = 1 if lead else -1
         comm = self._comm
-        if dt is None and not lead:
+        if dt is None and not self._dwell_weighted:
             dt = 1.0
         if dt is not None and comm is not None:
             dt = float(comm.bcast(np.array([dt], dtype=np.float64), 0)[0])
         grad0 = self.distribution.dEdX_count
-        self._dev.ring_alloc(1 + lead)                     # (a grid is created on a sampler that has its ring)
-        tg = None
-        try:
-            if dt is not None:
-                tg = self._dev.time_grid(n_grid, dt)       # its own storage: the ring may still grow
-            if block is None:
-                reserve = 0 if tg is not None else n_grid * self._dev.ring_slot_bytes()
-                block = self._dev.ring_budget_slots(n_iter + lead, staging=False, reserve_bytes=reserve) - lead
-            block = max(1, min(int(block), n_iter))
-            if comm is not None:
-                block = int(comm.allreduce_ints([block], 'min')[0])   # (_run is collective: see expectations())
-            self._dev.ring_alloc(block + lead)
-            for _, k in self._ring_blocks([n_iter], block):
+        # a grid whose dt is known exists before the budget is taken (its own storage: the ring may still grow); one that
+        # waits for the first block's dt is spoken for
+        dt0 = dt
+        early = lambda run: None if dt0 is None else run.own(self._dev.time_grid(n_grid, dt0))
+        reserve = lambda: n_grid * self._dev.ring_slot_bytes() if dt0 is None else 0
+        with self._RecordedRun(self, [n_iter], block, reserve_bytes=reserve, early=early, early_keeps=True) as run:
+            tg = run.head
+            for _, k in run.blocks():
                 if tg is None:                             # dt = W / (N k), the mean holding time of the first block
-                    est = self._dev.estimator(False)
-                    try:
-                        est.accumulate(0, k, w_slot0=w_slot0)
-                        W, _, _, _, n_first = self._reduce_sums(est.read())
-                    finally:
-                        est.close()
+                    W, _, _, _, n_first = run.first_block_sums(k)
                     dt = float(W) / n_first
                     if comm is not None:
                         dt = float(comm.bcast(np.array([dt], dtype=np.float64), 0)[0])
-                    tg = self._dev.time_grid(n_grid, dt)
-                tg.accumulate(0, k, w_slot0=w_slot0)
-            self._publish()
-            if lead:
-                self._read_dwell()
+                    tg = run.own(self._dev.time_grid(n_grid, dt))
+                tg.accumulate(0, k, w_slot0=run.w_slot0)
+            run.finish()
             covered = tg.progress()[0]
             T = tg.read_clocks()[0]
             sum_T, n_chains = float(np.sum(T)), int(T.size)
@@ -1899,10 +1805,7 @@ class HMCBase(object):
                 covered = int(comm.allreduce_ints([covered], 'min')[0])
                 n_chains = int(comm.allreduce_ints([n_chains], 'sum')[0])
                 sum_T = float(comm.allreduce_f64(np.array([sum_T]))[0])
-        except Exception:
-            if tg is not None:
-                tg.close()
-            raise
+            run.release(tg)                                # the caller's from here: Paths.close() frees it
         grad = self.distribution.dEdX_count - grad0
         return Paths(tg, dt, n_grid, covered, sum_T / n_chains, grad / float(n_chains), n_chains, comm)
 
