@@ -332,10 +332,18 @@ class SparseImageCode(Energy):
     ``operand_rounding`` (a callable, e.g. round-to-bfloat16) restates the mixed-precision form BASELINE.json
     configs[4] asks for -- "bf16 state / fp32 accumulate": both matrix products take rounded operands (the
     dictionary, the coefficients entering B a, the residual entering B^T r) and accumulate exactly; everything
-    else (prior, sums of squares, integrator) stays in full precision."""
+    else (prior, sums of squares, integrator) stays in full precision.
 
-    def __init__(self, basis, patches, lmbda=0.01, cauchy=True, operand_rounding=None):
+    ``accumulate_dtype`` = np.float32 is the twin of that restatement that accumulates as the device does: the two
+    matrix products of the rounded operands, the prior and the energy sums are taken in float32 (the results are handed
+    back as float64).  The reference alone then shows what the accumulation type is worth -- the role ``force_dtype``
+    plays for ProductOfT.  The default, np.float64, leaves every value bit for bit as it was."""
+
+    def __init__(self, basis, patches, lmbda=0.01, cauchy=True, operand_rounding=None, accumulate_dtype=np.float64):
         Energy.__init__(self)
+        self.acc = np.dtype(accumulate_dtype)
+        if self.acc not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError('accumulate_dtype is np.float64 or np.float32')
         self.rnd = operand_rounding or (lambda a: a)
         self.B = self.rnd(np.asarray(basis, dtype=np.float64))  # (img, n_coeffs)
         self.Y = np.asarray(patches, dtype=np.float64)          # (n_patches, img)
@@ -349,13 +357,36 @@ class SparseImageCode(Energy):
         recon = np.einsum('ic,pcn->pin', self.B, A)
         return recon - self.Y[:, :, None], A
 
+    def _resid32(self, X):
+        """the residual with float32 accumulation: (P, img, n) float32"""
+        P = self.Y.shape[0]
+        C = self.B.shape[1]
+        A = self.rnd(X).reshape(P, C, -1).astype(np.float32)
+        return np.matmul(self.B.astype(np.float32), A) - self.Y.astype(np.float32)[:, :, None]
+
     def E_val(self, X):
+        if self.acc == np.float32:
+            R = self._resid32(X)
+            one, half = np.float32(1), np.float32(0.5)
+            X32 = np.asarray(X, dtype=np.float32)
+            rec = np.sum(np.sum(half * R * R, axis=1, dtype=np.float32), axis=0, dtype=np.float32) / np.float32(R.shape[0])
+            pen = (np.sum(np.log(one + X32 * X32), axis=0, dtype=np.float32) if self.cauchy
+                   else np.sum(np.abs(X32), axis=0, dtype=np.float32))
+            return (rec + np.float32(self.lmbda) * pen).astype(np.float64).reshape((1, -1))
         R, _ = self._resid(X)
         rec = np.mean(np.sum(0.5 * R ** 2, axis=1), axis=0)
         pen = np.sum(np.log(1 + X ** 2), axis=0) if self.cauchy else np.sum(np.abs(X), axis=0)
         return (rec + self.lmbda * pen).reshape((1, -1))
 
     def dEdX_val(self, X):
+        if self.acc == np.float32:
+            R = self._resid32(X)
+            P = self.Y.shape[0]
+            Rr = self.rnd((R / np.float32(P)).astype(np.float64)).astype(np.float32)
+            g = np.matmul(self.B.astype(np.float32).T, Rr).reshape(X.shape)
+            X32 = np.asarray(X, dtype=np.float32)
+            pen = np.float32(2) * X32 / (np.float32(1) + X32 * X32) if self.cauchy else np.sign(X32)
+            return (g + np.float32(self.lmbda) * pen).astype(np.float64)
         R, _ = self._resid(X)
         P = self.Y.shape[0]
         g = np.einsum('ic,pin->pcn', self.B, self.rnd(R / P)).reshape(X.shape)   # d/da_p of the MEAN over patches

@@ -260,6 +260,29 @@ def pot_padded_dim(ndims):
     return dim, dim // 128
 
 
+def sic_tile_layout(n_patches):
+    """Pure-Python restatement of how the SparseImageCode tile kernels cut a tile of kP = 32 columns
+    (sic_particles_per_tile in csrc/dense_sic.hpp; col_of and kYLds = 4 in csrc/dense_sic.hip): (ppt, cpt, idle,
+    patches_in_lds) -- ppt = 32 // P particles share a tile, cpt = ppt * P columns work, the 32 - cpt idle columns are
+    clamped onto column cpt - 1, and the patches are read from their LDS copy up to kYLds of them (from global memory
+    beyond)."""
+    if not 1 <= n_patches <= 32:
+        raise ValueError('the SparseImageCode tile kernels hold 1 .. 32 patches per particle')
+    ppt = 32 // n_patches
+    cpt = ppt * n_patches
+    return ppt, cpt, 32 - cpt, n_patches <= 4
+
+
+def sic_tiles(n_patches, n_particles):
+    """(tiles, particles in the last tile) of a batch of `n_particles`: dense_ntiles counts in units of ppt; a last tile
+    holding fewer than ppt particles is ragged (col_of repeats the last particle with alive == false)."""
+    ppt = sic_tile_layout(n_patches)[0]
+    if n_particles < 1:
+        raise ValueError('at least one particle')
+    tiles = -(-n_particles // ppt)
+    return tiles, n_particles - (tiles - 1) * ppt
+
+
 _HOOKS_CTX = {}
 
 

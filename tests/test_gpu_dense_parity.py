@@ -556,7 +556,8 @@ def _dense_case(what, ctxs, seed=8):
         X0 = np.random.RandomState(3).randn(D, N)
         hp = (0.1, 6, 0.1)
     else:
-        P, N = (1, 17000) if what == 'sic_p1' else (9, 6100)
+        # 'sic_p17': one particle per tile -- 200 tiles reach the split threshold (4 tiles >= 3 CUs) on 256 CUs, parts of 128 particles
+        P, N = {'sic_p1': (1, 17000), 'sic_p9': (9, 6100), 'sic_p17': (17, 200)}[what]
         B, imgs, a0 = sic_problem(0, n_patches=P)
         D, dtype = P * 1024, 'bfloat16'
         params = np.concatenate([[float(P), 256.0, 1024.0, 0.01, 1.0], B.ravel(), imgs[:, :P].T.ravel()])
@@ -569,7 +570,7 @@ def _dense_case(what, ctxs, seed=8):
 _FIELDS = ('X', 'V', 'EX', 'EV', 'HFLF', 'CACHE', 'DWELL', 'TRANS')
 
 
-@pytest.mark.parametrize('what,parts', [('pot36', None), ('pot36f64', None), ('sic_p1', None), ('sic_p9', None), ('pot36_control', None),
+@pytest.mark.parametrize('what,parts', [('pot36', None), ('pot36f64', None), ('sic_p1', None), ('sic_p9', None), ('sic_p17', None), ('pot36_control', None),
                                         ('pot36f64_control', None), ('sic_p1_ct', None),
                                         ('pot36', 3), ('pot36f64', 4), ('sic_p1', 4), ('sic_p9', 3), ('pot36f64_control', 3)])
 def test_split_launches_equal_single_launches(what, parts, monkeypatch):
