@@ -3,7 +3,7 @@
 // Imparato (2013); E_p[g] = 0 for every target p = exp(-E) / Z that vanishes at infinity.
 //
 // Per recorded slot, in stream order on the sampler's stream:
-//   1. the sampler's own evaluation kernels on the sample-ring slot (api.hip: sampler_eval_rows) into the handle's gradient
+//   1. the sampler's own evaluation kernels on the sample-ring slot (state_io.hip: sampler_eval_rows) into the handle's gradient
 //      matrix G and energy vector, in the layout and types the energy family writes (as stein.hip);
 //   2. the moment and covariance passes of estimators.hip on G seen as a one-slot ring, about 0: W, Sg, S2g, Cgg;
 //   3. the moment pass on the matching slot of the handle's RingSource (sample ring or derived ring), about cb: Sb, S2b;

@@ -12,7 +12,7 @@
     *a.zero_count = 0;   // the list two iterations back is consumed: its counter is free for the next iteration's appends
     if (ncold) atomicAdd(&a.stats[3], (unsigned long long)ncold << 32);   // integrated here: the high half of the cold tally
   }
-  // tallies (meaning per mode: fill_iter_stats in api.hip) and the failure flag live in LDS, not in registers that would be
+  // tallies (meaning per mode: fill_iter_stats in iterate.hip) and the failure flag live in LDS, not in registers that would be
   // live across every GEMM loop and streamed pass of the kernel: [0..3] counts, [4] some particle met a non-finite rate
   __shared__ unsigned tally[5];
   if (threadIdx.x < 5) tally[threadIdx.x] = 0;

@@ -804,7 +804,7 @@ __global__ __launch_bounds__(512, 2) void sic_jump_kernel(const SicJumpArgsT<ST>
     *a.zero_count = 0;   // the list two iterations back is consumed: its counter is free for the next iteration's appends
     if (ncold) atomicAdd(&a.stats[3], (unsigned long long)ncold << 32);   // integrated here: the high half of the cold tally
   }
-  unsigned n0 = 0, n1 = 0, n2 = 0, n3 = 0;  // tallies (meaning per mode: fill_iter_stats in api.hip)
+  unsigned n0 = 0, n1 = 0, n2 = 0, n3 = 0;  // tallies (meaning per mode: fill_iter_stats in iterate.hip)
   bool any_bad = false;
   if (threadIdx.x < 4) sh.tally[threadIdx.x] = 0;
   stage_patches(mdl, sh);

@@ -97,7 +97,7 @@ int mjhmc_test_normal_pairs(mjhmc_ctx* ctx, uint64_t seed, uint64_t tick, int64_
   hipError_t rc = hipMalloc(&d, bytes);
   if (rc != hipSuccess) return mjhmc_fail(MJHMC_ERR_HIP, hipGetErrorString(rc));
   const RngKey key{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (uint32_t)(tick & 0xFFFFFFFFu),
-                   (uint32_t)(tick >> 32)};   // api.hip: rng_key()
+                   (uint32_t)(tick >> 32)};   // sampler_internal.hpp: rng_key()
   hipLaunchKernelGGL(normal_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, key, (uint32_t)first_pid,
                      n_pid, n_pairs, d);
   rc = hipGetLastError();

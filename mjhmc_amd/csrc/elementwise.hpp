@@ -248,7 +248,7 @@ struct NoLocal {};
 template <typename T>
 struct IsoGaussF {
   // fused launches (several iterations per launch) exist for this energy; WHEN they are used is the host's decision
-  // (api.hip, iterate_t): always for the Gaussian forces, whose single iteration is HBM-bound (measured 1.03-2.7x at
+  // (schedule.hpp, select_schedule): always for the Gaussian forces, whose single iteration is HBM-bound (measured 1.03-2.7x at
   // every row size), and for the vector-pipe-bound ones only while the batch is small (launch- and latency-bound:
   // funnel 18.7 -> 12.7 us per iteration at 1000 particles; 0.93-0.99x at 10^6, where the compacted passes win)
   static constexpr bool kFuse = true;
@@ -1950,7 +1950,7 @@ __global__ __launch_bounds__(256, (JumpWaves<En, T, E>::value)) void mjhmc_jump_
 // The same device functions as the jump kernel (trajectory, state_energies, decide, refresh_stash, kinetic) on the same
 // inputs: the same bits (tests/test_gpu_fused.py compares the paths).  C4: 0.269 -> 0.262 ms per iteration, 125 000
 // particles 0.057 -> 0.051.  (mjhmc_step_kernel can carry the trajectories of one part of a batch beside the jump process
-// of another; api.hip does not use that: measured, no gain -- the trajectories keep the vector pipe half busy themselves.)
+// of another; iterate.hip does not use that: measured, no gain -- the trajectories keep the vector pipe half busy themselves.)
 // ------------------------------------------------------------------------------------------
 template <class En, typename T, int E>
 __device__ __forceinline__ void traj_block(const TrajArgs<T>& a, const En& en, int vblock) {

@@ -3,7 +3,7 @@
 //     g[1] = sum_{d < ndims} G_d * G_d     G = dE/dX of the same evaluation
 //     g[2] = sum_{d < ndims} x_d * G_d     the virial: E_p[x . grad E] = ndims for every smooth target
 // written as a row [E, grad_sq, virial, 0.0] of the DERIVED ring of a mjhmc_functionals (functionals.hip), so that every
-// accumulator of the sample ring runs on them unchanged.  E and G come from run_eval (api.hip) on the ring slot itself --
+// accumulator of the sample ring runs on them unchanged.  E and G come from run_eval (state_io.hip) on the ring slot itself --
 // a ring slot has the layout of a state matrix -- into scratch of the handle; energy_observables_kernel below forms the row.
 //
 // Access shape: that of functionals_eval_kernel (functionals.hpp).  A lane owns 16 bytes of the X row (2 / 4 / 8 elements

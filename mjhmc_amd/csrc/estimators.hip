@@ -7,7 +7,7 @@
 // products and sums are float64.  Padding particles (N <= p < Npad) are never read.
 //
 // Which dwell goes with which state.  Every jump kernel writes the holding time it draws in the iteration that fills ring
-// slot s to dwell-ring slot s: api.hip jump_args() sets a.dwell_ring = s->dwell_ring + (ring_slot0 + iter) * Npad, the
+// slot s to dwell-ring slot s: iterate.hip jump_args() sets a.dwell_ring = s->dwell_ring + (ring_slot0 + iter) * Npad, the
 // fused kernels add `it * Npad` to the pointer of their first iteration (elementwise.hpp: a.dwell_ring[it * Npad + p]),
 // the dense kernels store `best` through it, and the host-energy / multi-pass path does the same
 // (host_energy.hip: c.dwell_ring = s->dwell_ring + ring_slot * Npad).  The draw uses the rates OUT of the state the
@@ -468,22 +468,6 @@ int mjhmc_estimator_read(mjhmc_estimator* est, double* W, double* S1, double* S2
   std::copy(h.begin() + 1, h.begin() + 1 + D, S1);
   std::copy(h.begin() + 1 + D, h.end(), S2);
   *n_states = est->n_states;
-  return 0;
-}
-
-int mjhmc_ring_copy(mjhmc_sampler* s, int src_slot, int dst_slot) {
-  if (!s) return mjhmc_fail(MJHMC_ERR_INVALID, "sampler is NULL");
-  if (src_slot < 0 || dst_slot < 0 || src_slot >= s->ring_slots || dst_slot >= s->ring_slots)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "slots out of range");
-  if (src_slot == dst_slot) return 0;
-  const size_t mb = mat_bytes(s);
-  char* dst = (char*)s->ring + (size_t)dst_slot * mb;
-  if ((char*)s->Xcur == dst) return mjhmc_fail(MJHMC_ERR_INVALID, "the destination slot holds the live state");
-  HIPCHK(hipSetDevice(s->ctx->device));
-  if (s->undo_valid && (char*)s->undo_X == dst) s->undo_valid = false;
-  HIPCHK(hipMemcpyAsync(dst, (const char*)s->ring + (size_t)src_slot * mb, mb, hipMemcpyDeviceToDevice, s->stream));
-  HIPCHK(hipMemcpyAsync(s->dwell_ring + (size_t)dst_slot * s->Npad, s->dwell_ring + (size_t)src_slot * s->Npad,
-                        (size_t)s->Npad * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   return 0;
 }
 

@@ -10,7 +10,7 @@
 //
 // A second kind of handle (mjhmc_functionals_create_energy) fills the same derived ring with the ENERGY OBSERVABLES
 // [E, grad_sq, virial] of every recorded state: no expressions and no hipRTC -- per slot the sampler's own evaluation
-// (api.hip: sampler_eval_rows) into scratch of the handle, then energy_observables_kernel (energy_observables.hpp).
+// (state_io.hip: sampler_eval_rows) into scratch of the handle, then energy_observables_kernel (energy_observables.hpp).
 //
 // A third kind (mjhmc_functionals_create_linear) fills it with LINEAR PROJECTIONS g = link(A x + b) of every recorded state:
 // K <= 512 caller-chosen directions through the small-GEMM kernel of projections.hpp -- the library's own instantiation for

@@ -1,4 +1,4 @@
-// Handle structs of the C ABI (include/mjhmc_hip.h) and the few helpers api.hip shares with comm.hip.
+// Handle structs of the C ABI (include/mjhmc_hip.h) and the few helpers the sampler's units share with comm.hip and the ring statistics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,13 +94,13 @@ struct Shape {
 };
 
 
-constexpr int kMaxDenseParts = 4;   // free-running parts of a dense batch (iterate_t)
+constexpr int kMaxDenseParts = 4;   // free-running parts of a dense batch (iterate_dense_parts)
 
 struct RingAccumulator;  // base of the accumulators over ring blocks: mjhmc_estimator, _chainstats, _histogram, _pairhist (ring_source.hpp)
 struct mjhmc_functionals;  // caller expressions g(x) evaluated into a derived ring (functionals.hip)
 struct mjhmc_timegrid;   // the jump process sampled on a uniform time grid, in a grid ring of its own (timegrid.hip)
 struct mjhmc_stein;      // kernel Stein discrepancy of one recorded ensemble (stein.hip)
-struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (api.hip)
+struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (iterate.hip)
 struct HostTraj;  // proposal workspace of a host-energy sampler (host_energy.hip)
 
 struct mjhmc_sampler {
@@ -112,7 +112,7 @@ struct mjhmc_sampler {
   hipStream_t stream = nullptr;
   char* h_pin = nullptr;          // pinned host staging of the per-call read-back (failure flag + tallies)
   size_t h_pin_cap = 0;
-  std::vector<hipStream_t> part_streams;   // further parts of a split launch: fused elementwise launches (iterate_fused_t), dense batches (iterate_t)
+  std::vector<hipStream_t> part_streams;   // further parts of a split launch: fused elementwise launches (iterate_fused_t), dense batches (iterate_dense_parts)
   std::vector<hipEvent_t> part_events;
   hipEvent_t ev_join = nullptr;
   void* ick[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // the split schedule's own checkpoint (as ck[])
@@ -154,7 +154,7 @@ struct mjhmc_sampler {
   uint8_t* trans = nullptr;
   // What a call zeroes at its start and reads back at its end lives in ONE device block -- [Control, 64 bytes][flf_counts:
   // stats_cap + 1 counters, padded to 64 bytes][stats: stats_cap x 4] -- so that a call is one fill and one copy
-  // (api.hip: ensure_call_block, zero_call, read_back_call).  ctl, flf_counts and stats point into it.
+  // (iterate.hip: ensure_call_block, zero_call, end_call).  ctl, flf_counts and stats point into it.
   char* call_block = nullptr;
   Control* ctl = nullptr;
   long long* stats = nullptr;  // [stats_cap][4]
@@ -173,7 +173,6 @@ struct mjhmc_sampler {
   double* rexp = nullptr;   // [3][N]
   double* runif = nullptr;  // [2N+1]
   void* scratch = nullptr;  // [N][pitch] scratch (dEdX reads)
-  bool download_f32 = false;  // bf16 state: the next download_cols source is a float32 matrix (dEdX)
   double eps = 1e-4, p_r = 0, beta = 1, p_flip = 0.5;
   int L = 5;
   uint64_t seed = 0, tick = 1;
@@ -219,12 +218,12 @@ int wide_run_eval(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const
 int multipass_iterate(mjhmc_sampler* s, int n_iter, const double* replay_normal, const double* replay_exp,
                       const double* replay_unif, int ring_slot0, mjhmc_iter_stats* per_iter, int* n_done);
 int multipass_rollback(mjhmc_sampler* s);
-int round_rows32(mjhmc_sampler* s, void* rows);   // float64 rows -> float32 values (Shape::round32), api.hip
+int round_rows32(mjhmc_sampler* s, void* rows);   // float64 rows -> float32 values (Shape::round32), state_io.hip
 void pot_narrow_rows32(const double* src, float* dst, int64_t n, hipStream_t st);   // dst[i] = (float)src[i], i < n
 int wide_leapfrog(mjhmc_sampler* w, const double* X, const double* V, double* Xo, double* Vo, double* G, double* EX,
                   double* EV, double eps, int n_steps);
 
-// api.hip: E and dE/dX of a state matrix through the sampler's own evaluation kernels (no momentum, no counters)
+// state_io.hip: E and dE/dX of a state matrix through the sampler's own evaluation kernels (no momentum, no counters)
 int sampler_eval_rows(mjhmc_sampler* s, const void* X, void* Gout, void* Eout);
 
 // lanes-per-particle / elements-per-lane selection of the elementwise kernels for ndims = D
@@ -232,9 +231,10 @@ int pick_shape(int D, int dtype, Shape* out);
 // device staging buffer of at least `elems` float64 (host layout side of every re-tiling)
 int ensure_stage(mjhmc_sampler* s, size_t elems);
 // device particle-major rows -> s->stage in the reference's (ndims, columns) layout: stage[d*rs + k*cs + off] = row(k)[d],
-// row(k) = dev_idx ? dev_idx[k] : k; copy_out: then copy host_elems doubles of the stage to `host` and synchronise
+// row(k) = dev_idx ? dev_idx[k] : k; copy_out: then copy host_elems doubles of the stage to `host` and synchronise.
+// elem: the dtype code of the rows' elements where it is not the state's (-1) -- SparseImageCode's float32 dE/dX
 int download_cols(mjhmc_sampler* s, const void* src, const int64_t* dev_idx, int64_t ncols, double* host,
-                  size_t host_elems, int64_t rs, int64_t cs, int64_t off, bool copy_out);
+                  size_t host_elems, int64_t rs, int64_t cs, int64_t off, bool copy_out, int elem = -1);
 // device -> pageable host memory on the sampler's stream, synchronised; big blocks go through a pinned double buffer
 // with the host-side copy spread over several threads
 int copy_to_host(mjhmc_sampler* s, const void* dev_src, void* host_dst, size_t bytes);

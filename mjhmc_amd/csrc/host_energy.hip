@@ -624,7 +624,7 @@ void host_traj_free(mjhmc_sampler* s) {
   s->ht = nullptr;
 }
 
-// run_eval of api.hip for a host energy: the kinetic energy of V (or the tick-0 momentum) is device work, E and dE/dX
+// run_eval of state_io.hip for a host energy: the kinetic energy of V (or the tick-0 momentum) is device work, E and dE/dX
 // are the caller's (mjhmc_host_set_energy)
 int host_run_eval(mjhmc_sampler* s, const void* V, void* Vgen, void* EVout) {
   if (Vgen) {
@@ -896,7 +896,7 @@ int multipass_rollback(mjhmc_sampler* s) {
 
 // ---- wide samplers: built-in elementwise energies with ndims beyond the register-resident kernels -------------------
 
-// run_eval of api.hip for a host energy or a wide sampler: the kinetic energy of V (or the tick-0 momentum) always; E and
+// run_eval of state_io.hip for a host energy or a wide sampler: the kinetic energy of V (or the tick-0 momentum) always; E and
 // dE/dX from the device kernel for a wide sampler, the caller's (mjhmc_host_set_energy) for a host energy
 int wide_run_eval(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen, void* EVout) {
   if (!s->en->is_host() && X && (Gout || Eout)) TRY(wide_eval_rows(s, (const double*)X, (double*)Gout, (double*)Eout, s->N));
@@ -951,7 +951,7 @@ static int pot_trajectory_f64(mjhmc_sampler* s) {
 }
 
 // mjhmc_iterate for a wide sampler: n_iter sampling iterations, each L x (kick, drift, device gradient) over the proposal
-// columns in HBM, then decide + commit -- the contract of iterate_t (stops at the first attempt with a non-finite rate)
+// columns in HBM, then decide + commit -- the contract of the schedules of iterate.hip (stops at the first attempt with a non-finite rate)
 int multipass_iterate(mjhmc_sampler* s, int n_iter, const double* replay_normal, const double* replay_exp,
                       const double* replay_unif, int ring_slot0, mjhmc_iter_stats* per_iter, int* n_done) {
   const size_t DN = (size_t)s->D * s->N;

@@ -1,7 +1,7 @@
 // Kernel Stein discrepancy of a recorded ensemble (include/mjhmc_hip.h: mjhmc_stein_*; kernels and the definition in
 // stein.hpp).  The handle owns what one evaluation needs -- dE/dX and E of ONE slot in the layout and types the energy
 // family writes (as the energy observables' scratch, functionals.hip), one (S, Sd) partial per tile of pairs, the four
-// results and the flag word -- and evaluate is: the sampler's own evaluation kernels on the slot (api.hip:
+// results and the flag word -- and evaluate is: the sampler's own evaluation kernels on the slot (state_io.hip:
 // sampler_eval_rows), the pair kernel, the finish kernel, one read-back; all on the sampler's stream.
 //   float64 state  -> float64 dE/dX   (elementwise and user-expression energies, the wide / multi-pass path, ProductOfT
 //                                      and linear models with float64 state)

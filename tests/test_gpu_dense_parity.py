@@ -541,7 +541,7 @@ def test_sic_512_atoms_control_arm_and_leapfrog():
 
 
 # ---------------------------------------------------------------------------------------------
-# dense batches are launched as free-running parts on their own streams (api.hip: part_args): invisible in the results
+# dense batches are launched as free-running parts on their own streams (iterate.hip: part_args): invisible in the results
 # ---------------------------------------------------------------------------------------------
 def _dense_case(what, ctxs, seed=8):
     """(energies per context, X0, dtype, mode, (eps, L, beta)) of the split / shortcut tests"""
@@ -672,7 +672,7 @@ def test_f_mover_shortcut_is_bit_identical(what, monkeypatch):
                                          ('pot36f64', '5:19000'), ('pot36f64', '2:7')])
 def test_split_launches_failure_in_the_middle_of_a_call(what, poison, monkeypatch):
     """A non-finite rate while the two halves of a big dense batch run freely: the call must end exactly like a call
-    that was never split -- same `done`, same state, same tallies of the good iterations -- (api.hip: the state copy
+    that was never split -- same `done`, same state, same tallies of the good iterations -- (iterate.hip: the state copy
     taken at the start of the call is put back and the call re-run on one stream).  The failure is placed with the
     library's test hook MJHMC_DEBUG_POISON=iteration:particle (that particle's kinetic energy reads NaN there)."""
     from mjhmc_amd import engine, _lib
@@ -729,7 +729,7 @@ def test_split_launches_failure_in_the_middle_of_a_call(what, poison, monkeypatc
 @pytest.mark.parametrize('what,poison', [('pot36', '3:19000'), ('pot36', '5:7'), ('pot36f64', '4:19000'), ('sic_p1', '4:300')])
 def test_streamed_download_when_a_split_call_fails_in_the_middle(what, poison, monkeypatch):
     """mjhmc_iterate_download while the two halves of a dense batch run freely and one of them meets a non-finite rate:
-    the call is put back and re-run on one stream (api.hip: iterate_t), and NOTHING the first run handed to the download
+    the call is put back and re-run on one stream (iterate.hip: iterate_dense_parts, mjhmc_iterate), and NOTHING the first run handed to the download
     thread may survive -- a lagging half left its columns of the slots stale (dl_restart).  The host array of the
     streamed call must hold, for the iterations that completed, exactly what a never-split call records in its ring."""
     from mjhmc_amd import engine, _lib

@@ -304,7 +304,7 @@ def test_timing_switched_off_changes_nothing_but_the_markers():
 def test_compacted_passes_failure_in_the_middle_of_a_batch(monkeypatch):
     """A non-finite rate in iteration i > 0 of a multi-iteration call through the compacted passes: the call stops
     there and the state is the one iteration i-1 handed on -- INCLUDING the momentum refresh of its R-movers, which
-    rides in the inverse-L pass of iteration i (api.hip, iterate_t) -- exactly as without the compacted passes.
+    rides in the inverse-L pass of iteration i (iterate.hip, iterate_compact_t) -- exactly as without the compacted passes.
     (Gaussian force with fusing switched off: its energy error grows as particles drift outwards, which gives late
     first failures; see test_fused_failure_in_the_middle_of_a_launch.)"""
     from mjhmc_amd import _lib
@@ -350,7 +350,7 @@ def test_compacted_passes_failure_in_the_middle_of_a_batch(monkeypatch):
                                       ('E_ISO_GAUSS', 24, 530003),      # a quad of lanes per particle
                                       ('E_ISO_GAUSS', 40, 270001)])     # ragged rows (predicated chunks)
 def test_split_fused_launch_equals_single_launch(kind, D, N, monkeypatch, mode_name='MODE_MJHMC'):
-    """A big fused launch runs as two halves on two streams (api.hip, iterate_fused_t): invisible in the results, and a
+    """A big fused launch runs as two halves on two streams (iterate.hip, iterate_fused_t): invisible in the results, and a
     non-finite rate in either half ends the call like an unsplit one."""
     from mjhmc_amd import _lib
     params = list(10.0 ** np.linspace(-1, 0, D)) if kind == 'E_DIAG_GAUSS' else [1.0]
