@@ -139,7 +139,7 @@ int mjhmc_energy_create(mjhmc_ctx* ctx, int kind, int ndims, const double* param
  *     E(x) = sum_d energy_expr(x_d)      dE/dx_d = grad_expr(x_d)
  * with `x` the coordinate (double), `d` its index (int) and `p[k]` the float64 parameters, e.g.
  * ("0.5*x*x/(p[0]*p[0])", "x/(p[0]*p[0])") or ("log(1.0 + x*x/p[d])", "2.0*x/(p[d] + x*x)").  The engine's kernel
- * templates are compiled around them with hipRTC for gfx950 (include_dir: the directory holding elementwise.hpp and
+ * templates are compiled around them with hipRTC for gfx950 (include_dir: the directory holding jump_kernel.hpp and
  * philox.hpp, mjhmc_amd/csrc of this package); float64 state; every sampler family and the replay mode work as for the
  * built-in elementwise energies.  A compile error in the expressions is returned as MJHMC_ERR_INVALID with the
  * compiler's log in mjhmc_last_error(). */
@@ -805,7 +805,7 @@ int mjhmc_leapfrog(mjhmc_energy* e, int dtype, const double* X, const double* V,
                    double* X_out, double* V_out, double* EX_out, double* EV_out, double* dEdX_out);
 
 /* The two helpers of the jump process as operators on caller arrays (mjhmc/misc/utils.py; the samplers' kernels use
- * the same device functions, `wait_time` and `first_min3` of csrc/elementwise.hpp):
+ * the same device functions, `wait_time` and `first_min3` of csrc/jump_math.hpp):
  *   draw_from (utils.py:31-50): waiting times of exponential clocks.  out[i] = inf where rates[i] == 0, otherwise
  *     (1 / rates[i]) * unit_exp[i] -- numpy's exponential(scale = 1/rate) is scale * standard_exponential(), so with the
  *     standard exponentials the caller drew the result is bit-identical.  A non-finite rate is the reference's

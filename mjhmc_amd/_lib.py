@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-KERNEL_HEADERS = os.path.join(_HERE, 'csrc')     # elementwise.hpp / philox.hpp / functionals.hpp: what hipRTC compiles user expressions against
+KERNEL_HEADERS = os.path.join(_HERE, 'csrc')     # jump_kernel.hpp / philox.hpp / functionals.hpp: what hipRTC compiles user expressions against
 LIB_PATH = os.environ.get('MJHMC_HIP_LIB') or os.path.join(_HERE, 'lib', 'libmjhmc_hip.so')
 
 # enums of include/mjhmc_hip.h

@@ -22,7 +22,7 @@ int mjhmc_fail(int code, const std::string& msg) {
 }
 const std::string& last_error_text() { return g_err; }
 
-// lanes-per-particle / elements-per-lane selection (see elementwise.hpp header comment)
+// lanes-per-particle / elements-per-lane selection (see lane_group.hpp header comment)
 
 int pick_shape(int D, int dtype, Shape* out) {
   const int esize = dtype == MJHMC_F64 ? 8 : 4;

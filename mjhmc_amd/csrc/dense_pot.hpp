@@ -5,7 +5,11 @@
 #endif
 #include <stdint.h>
 
-#include "elementwise.hpp"  // Control, RngKey, philox
+#include "jump_math.hpp"
+#include "jump_process.hpp"  // decide<double> / decide_ct<double> of the float64-state kernels
+#include "lane_group.hpp"
+#include "philox.hpp"
+#include "sampler_args.hpp"  // Control, the dense argument blocks
 
 namespace mjhmc {
 
@@ -22,7 +26,7 @@ struct PotModel {
   int ndims;           // true ndims == nbasis (rows at or beyond it are zero padding)
 };
 
-// the tile kernels' argument blocks (elementwise.hpp: DenseJumpArgs): float32 state rows, and the reference's
+// the tile kernels' argument blocks (sampler_args.hpp: DenseJumpArgs): float32 state rows, and the reference's
 // arithmetic (dense_pot64.hip) with float64 state rows around the float32 force
 using PotJumpArgs = DenseJumpArgs<float, float, true>;
 using Pot64JumpArgs = DenseJumpArgs<double, double, true>;

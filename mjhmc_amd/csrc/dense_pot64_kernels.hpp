@@ -10,6 +10,7 @@
 
 #include "dense_pot.hpp"
 #include "dense_pot_tile.hpp"
+#include "group_form.hpp"  // use_here
 
 namespace mjhmc {
 
@@ -604,13 +605,7 @@ __device__ __forceinline__ int pot64_decide(const Pot64JumpArgs& a, double H0, d
   ja.rexp = a.rexp;
   ja.runif = a.runif;
   ja.N = a.N;
-  LaneMap m;
-  m.j = 0;
-  m.G = 1;
-  m.D = 1;
-  m.CH = 1;
-  m.lane0 = 0;
-  m.wpp = 0;
+  const LaneMap m = LaneMap::one_lane();
   int k = 0;
   if constexpr (MODE == kModeMJHMC) {
     decide<double, REPLAY>(ja, a.key, m, H0, HL, Hflf, pp, pid, k, best, bad);

@@ -1,10 +1,11 @@
 // Test build only (libmjhmc_hip_test.so; the Makefile lists this file for that library alone): the hand-written device
 // math of the samplers -- neg_log_unit, sincospi_unit, box_muller (philox.hpp), box_muller_f32 (dense_pot.hpp), the exp
-// chains and jump_rate (elementwise.hpp) -- evaluated on caller arrays, one lane per element, and normal_pair on a grid
+// chains and jump_rate (jump_math.hpp) -- evaluated on caller arrays, one lane per element, and normal_pair on a grid
 // of (particle id, pair).  The kernels call the product's own inline functions: what tests/test_gpu_device_math.py
 // compares with its long-double references is the code the samplers run.
 #ifdef MJHMC_TEST_HOOKS
 #include "handles.hpp"
+#include "jump_math.hpp"
 
 namespace {
 

@@ -8,7 +8,7 @@
 //
 // Which dwell goes with which state.  Every jump kernel writes the holding time it draws in the iteration that fills ring
 // slot s to dwell-ring slot s: iterate.hip jump_args() sets a.dwell_ring = s->dwell_ring + (ring_slot0 + iter) * Npad, the
-// fused kernels add `it * Npad` to the pointer of their first iteration (elementwise.hpp: a.dwell_ring[it * Npad + p]),
+// fused kernels add `it * Npad` to the pointer of their first iteration (jump_kernel.hpp, row_form.hpp: a.dwell_ring[it * Npad + p]),
 // the dense kernels store `best` through it, and the host-energy / multi-pass path does the same
 // (host_energy.hip: c.dwell_ring = s->dwell_ring + ring_slot * Npad).  The draw uses the rates OUT of the state the
 // iteration starts from, so it is the time the particle spent in the state of slot s - 1: the holding time of the state

@@ -8,8 +8,9 @@
 #include "../../include/mjhmc_hip.h"
 #include "dense_pot.hpp"
 #include "dense_sic.hpp"
-#include "elementwise.hpp"
+#include "launcher_decls.hpp"
 #include "linear_energy.hpp"
+#include "sampler_args.hpp"
 #include "user_expr.hpp"
 
 using namespace mjhmc;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "handles.hpp"
+#include "jump_process.hpp"  // decide / decide_ct in their one-lane forms
 
 struct HostTraj {
   double* X = nullptr;  // [2 Npad][pitch] proposal columns
@@ -108,7 +109,7 @@ __global__ void hk_gen_v(double* __restrict__ V, RngKey key, int64_t first_pid, 
 // ---- built-in elementwise energies on rows of any length: one wavefront per row, E and dE/dX in one pass ------------
 struct WideEnergy {
   int kind;
-  double a, b, c;        // the functor constants of elementwise.hpp (IsoGaussF, RoughWellF, MMGaussF, FunnelNealF, FunnelRefF)
+  double a, b, c;        // the functor constants of energies.hpp (IsoGaussF, RoughWellF, MMGaussF, FunnelNealF, FunnelRefF)
   const double* jdiag;   // DIAG_GAUSS
 };
 
@@ -228,13 +229,7 @@ __global__ void hk_decide(const DecideArgs a) {
   ja.rexp = a.rexp;
   ja.runif = a.runif;
   ja.N = a.N;
-  LaneMap m;
-  m.j = 0;
-  m.G = 1;
-  m.D = 1;
-  m.CH = 1;
-  m.lane0 = 0;
-  m.wpp = 0;
+  const LaneMap m = LaneMap::one_lane();
   int k = 0;
   double dwell = 0.0;
   bool bad = false;

@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "energies.hpp"  // MMGaussF::kRelayMinL
 #include "sampler_internal.hpp"
 #include "schedule.hpp"
 
@@ -137,7 +138,7 @@ static int ab_flags() {
          (test_env("MJHMC_NO_RELAY") ? kAbNoRelay : 0) | (test_env("MJHMC_FORCE_RELAY") ? kAbForceRelay : 0);
 }
 
-// fused MarkovJumpHMC launches of this sampler run in row form (elementwise.hpp: mjhmc_fused_rows_kernel)
+// fused MarkovJumpHMC launches of this sampler run in row form (row_form.hpp: mjhmc_fused_rows_kernel)
 static bool fused_rows(const mjhmc_sampler* s) {
   const int kind = s->en->ep.kind;
   // (the mixture's force is a division per coordinate: its row form pays through the relay kernel only -- 0.500 ms against
@@ -361,7 +362,7 @@ static int dl_restart(mjhmc_sampler* s) {
 // ---------------------------------------------------------------------------------------------
 // the argument blocks of an iteration
 // ---------------------------------------------------------------------------------------------
-// the tile kernels' argument blocks (elementwise.hpp), apart from the elementwise energies' JumpArgs<T>
+// the tile kernels' argument blocks (sampler_args.hpp), apart from the elementwise energies' JumpArgs<T>
 template <class A>
 struct IsDenseJump : std::false_type {};
 template <typename S, typename H, bool POT>
@@ -828,7 +829,7 @@ static int iterate_dense_parts(mjhmc_sampler* s, int n_iter, const Replay& rp, i
   return commit_iterations(s, hs, hc, n_iter, xout, per_iter, n_done);
 }
 
-// The compacted passes of the elementwise energies (elementwise.hpp, mjhmc_step_kernel): the iteration's trajectories --
+// The compacted passes of the elementwise energies (step_kernel.hpp, mjhmc_step_kernel): the iteration's trajectories --
 // the L proposals and, beside them, the inverse-L proposals of the listed cold caches --, then its jump process with a
 // lane per particle, which finishes the movers and hands them on as the next iteration's list (only the first iteration
 // of a call scans the cache, and not even that one when the list was `carried` over from the call before).

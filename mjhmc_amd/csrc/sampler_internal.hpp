@@ -30,7 +30,7 @@ static inline const char* test_env(const char*) { return nullptr; }
 // ---------------------------------------------------------------------------------------------
 // dispatch over the elementwise energies
 // ---------------------------------------------------------------------------------------------
-// the launchers of one elementwise energy (elementwise.hpp: MJHMC_DEFINE_ENERGY_LAUNCHERS), overloaded on the argument block
+// the launchers of one elementwise energy (launchers.hpp: MJHMC_DEFINE_ENERGY_LAUNCHERS), overloaded on the argument block
 #define MJHMC_ENERGY_LAUNCHERS(NAME)                                               \
   struct NAME##_launchers {                                                        \
     template <class... A> static void jump(const A&... a) { NAME##_jump(a...); }  \

@@ -53,7 +53,7 @@ static __device__ unsigned g_sic_stamp[4][8][8];
 #endif
 
 // -DROWS_STAMPS (tools/rows_stamps.sh): cycle stamps of workgroup 0's four waves at the phase boundaries of the relay kernel's
-// sampling iterations (elementwise.hpp: mjhmc_fused_rows_relay_kernel), first workgroup tile only, [wave][iteration][point].
+// sampling iterations (row_form.hpp: mjhmc_fused_rows_relay_kernel), first workgroup tile only, [wave][iteration][point].
 // Twelve stamps per ~25 000-cycle iteration; tools/rows_stamps.py reads them (mjhmc_rows_stamps in energy_funnel.hip).
 #ifdef ROWS_STAMPS
 namespace mjhmc {

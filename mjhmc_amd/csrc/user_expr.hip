@@ -6,7 +6,7 @@
 //
 // (`x` the coordinate, `d` its index, `p[k]` float64 parameters; optionally coupled through per-particle statistics
 // S[k] = sum_d s_k(x_d, d; p), see user_expr_source), and this file compiles the engine's own kernel templates
-// (elementwise.hpp: mjhmc_jump_kernel, mjhmc_eval_kernel, mjhmc_leap_kernel) around them with hipRTC, at energy
+// (jump_kernel.hpp: mjhmc_jump_kernel, mjhmc_eval_kernel, mjhmc_leap_kernel) around them with hipRTC, at energy
 // creation, for gfx950.  The resulting energy runs through exactly the code paths of the built-in elementwise
 // energies: same lane mapping, same jump / accept logic, same counter RNG, all three sampler families, replay mode.
 #include <dlfcn.h>
@@ -102,7 +102,7 @@ std::string user_expr_source(const std::string& energy_expr, const std::string& 
   const int K = (int)st.size();
   const std::string e0 = energy0_expr.empty() ? "0.0" : energy0_expr;
   std::string s;
-  s += "#include \"elementwise.hpp\"\n";
+  s += "#include \"jump_kernel.hpp\"\n";
   s += "namespace mjhmc {\n";
   s += "// E(x) = e0(S) + sum_d e(x_d, d, S; p), dE/dx_d = g(x_d, d, S; p), S[k] = sum_d s_k(x_d, d; p): the caller's expressions\n";
   s += "struct UserExprF {\n";

@@ -5,7 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "elementwise.hpp"
+#include "sampler_args.hpp"
 
 struct mjhmc_energy;
 

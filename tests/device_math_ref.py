@@ -2,7 +2,7 @@
 runs the kernels' own functions on these inputs; tests/test_device_math_cpu.py checks this file against 200-bit mpmath).
 
 np.longdouble is the x87 80-bit format here (64-bit mantissa): 2^-11 of a double's ulp, enough to resolve the 1.5 - 2 ulp
-gates of the hand-written float64 routines of csrc/philox.hpp and csrc/elementwise.hpp."""
+gates of the hand-written float64 routines of csrc/philox.hpp and csrc/jump_math.hpp."""
 import numpy as np
 
 LD = np.longdouble

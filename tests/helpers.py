@@ -213,7 +213,7 @@ def check_control_iteration(s, o, delta_rel, x_tol, e_rtol, tag='', max_ties=Non
 
 
 def group_shape(ndims, dtype='float64'):
-    """Pure-Python restatement of pick_shape (csrc/api.hip) and of launch_jump_t's `full` (csrc/elementwise.hpp) for the
+    """Pure-Python restatement of pick_shape (csrc/api.hip) and of launch_jump_t's `full` (csrc/launchers.hpp) for the
     elementwise energies: (E, logG, full_row) -- E elements in each of the 2^logG lanes of a particle's group, and whether
     the row's 16-byte chunks fill the group exactly (the FULLROW instances; an odd ndims still leaves one padding ELEMENT
     in the last chunk, which only the dim_of masks keep out).  E = 0: more than 64 lanes x 8 chunks, the multi-pass path."""
@@ -235,7 +235,7 @@ def group_shape(ndims, dtype='float64'):
 
 
 def jump_instance(E, logG, full, fused, mode='mjhmc', block_decide=True):
-    """Restatement of launch_jump_t (csrc/elementwise.hpp) for the group form with the counter RNG: the instance
+    """Restatement of launch_jump_t (csrc/launchers.hpp) for the group form with the counter RNG: the instance
     (FULLROW, WPP) of mjhmc_jump_kernel a call takes.  (The float64 funnels and mixture at logG 1 and 2 fuse in row
     form instead: tests/test_gpu_rows_oracle.py.)"""
     if mode != 'mjhmc' or not full:

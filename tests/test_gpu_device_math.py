@@ -1,5 +1,5 @@
 """The hand-written device math against long double: neg_log_unit, sincospi_unit, box_muller (csrc/philox.hpp),
-box_muller_f32 (csrc/dense_pot.hpp), exp_normal / exp_any / exp_neg / exp_neg_k and jump_rate (csrc/elementwise.hpp),
+box_muller_f32 (csrc/dense_pot.hpp), exp_normal / exp_any / exp_neg / exp_neg_k and jump_rate (csrc/jump_math.hpp),
 called through the probe of the test build (csrc/device_math_probe.hip: the product's own inline functions, one lane per
 element), and normal_pair's keying against oracle/philox.py.  References, measure and input sets: tests/device_math_ref.py
 (checked against 200-bit mpmath by tests/test_device_math_cpu.py).  Every test prints its measured maximum (pytest -s).

@@ -185,7 +185,7 @@ def test_float32_state(kind, D, N):
 def test_compacted_inverse_pass_equals_in_kernel(kind, D, N, monkeypatch):
     """Big batches with several particles per wave run an iteration as two launches -- every trajectory (the inverse-L
     proposals of the cold caches in workgroups of their own), then the jump process with a lane per particle, whose movers
-    are the next iteration's list (elementwise.hpp: mjhmc_step_kernel); it must be invisible: state, scalars, transitions
+    are the next iteration's list (step_kernel.hpp: mjhmc_step_kernel); it must be invisible: state, scalars, transitions
     and the per-iteration counters (the cold tallies come from the list lengths) equal the jump kernel's, which does
     all of it per slot.  (Both samplers from the test build with fused launches switched off: below 160 000 particles
     the product would fuse the multi-iteration calls.)"""

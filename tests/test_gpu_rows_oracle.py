@@ -70,7 +70,7 @@ def _eps(name, L):
 
 
 def _path(name, D, L, fused):
-    """the launch path the engine selects (iterate.hip: fused_rows; schedule.hpp: select_schedule; elementwise.hpp: launch_fused_rows)"""
+    """the launch path the engine selects (iterate.hip: fused_rows; schedule.hpp: select_schedule; launchers.hpp: launch_fused_rows)"""
     rows = 9 <= D <= 32
     mm = name.startswith('mm')
     if not fused:

@@ -1,6 +1,6 @@
 """CPU: the lanes-per-particle / elements-per-lane table the group-form oracle cases (tests/test_gpu_groups_oracle.py) were
 chosen from.  tests.helpers.group_shape restates pick_shape (csrc/api.hip) and jump_instance restates launch_jump_t
-(csrc/elementwise.hpp); if a threshold moves there, the restatement is updated with it, this table fails, and the cases
+(csrc/launchers.hpp); if a threshold moves there, the restatement is updated with it, this table fails, and the cases
 must be chosen again so that every instance is still reached."""
 import pytest
 

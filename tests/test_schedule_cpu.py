@@ -16,7 +16,7 @@ from tests.helpers import group_shape
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = '/opt/rocm/lib/llvm/bin/clang++'
 K_FUSE_BELOW = 160000        # csrc/schedule.hpp: kFuseBelow (test_the_threshold_is_the_one_the_table_assumes)
-MM_RELAY_MIN_L = 4           # csrc/elementwise.hpp: MMGaussF::kRelayMinL
+MM_RELAY_MIN_L = 4           # csrc/energies.hpp: MMGaussF::kRelayMinL
 
 
 def row(kind, D, N, n_iter, L=6, mode='mjhmc', replay=False, no_fuse=False, no_compact=False, fuse_below=None,
@@ -190,5 +190,5 @@ def test_the_threshold_is_the_one_the_table_assumes():
     hpp = open(os.path.join(ROOT, 'mjhmc_amd', 'csrc', 'schedule.hpp')).read()
     assert int(re.search(r'kFuseBelow\s*=\s*(\d+)', hpp).group(1)) == K_FUSE_BELOW
     assert '#include <hip' not in hpp and 'handles.hpp' not in hpp        # nothing of HIP: the host compiler alone builds it
-    ew = open(os.path.join(ROOT, 'mjhmc_amd', 'csrc', 'elementwise.hpp')).read()
+    ew = open(os.path.join(ROOT, 'mjhmc_amd', 'csrc', 'energies.hpp')).read()
     assert int(re.search(r'struct MMGaussF.*?kRelayMinL\s*=\s*(\d+)', ew, flags=re.S).group(1)) == MM_RELAY_MIN_L

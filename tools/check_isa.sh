@@ -130,7 +130,7 @@ print('check_isa %s: %s' % (sys.argv[2], 'FAILED: %d kernel(s)' % bad if bad els
 sys.exit(1 if bad else 0)
 PY
 done
-# The row-form kernels of the funnels (elementwise.hpp): what their design promises --
+# The row-form kernels of the funnels (row_form.hpp): what their design promises --
 #   mjhmc_fused_rows_kernel / mjhmc_fused_rows_relay_kernel (the product's form since round 6: four-wave workgroups, the cold
 #   caches' inverse-L trajectories pooled): no scratch memory at all; the leapfrog-step loops -- the wave's own and the
 #   pool's two-lanes-per-particle one -- are straight vector code (<= 150 / 170 instructions for the 32-coordinate row,
