@@ -195,6 +195,35 @@ int mjhmc_energy_create_linear_tall(mjhmc_ctx* ctx, int ndims, int64_t nexperts,
                                     const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out);
 /* compile-only check of a tall linear-model energy (needs no device): 0, MJHMC_ERR_INVALID, MJHMC_ERR_UNSUPPORTED as above */
 int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
+/* Grouped linear-model energies: the tall form with a log-sum-exp over groups of experts,
+ *     E(x) = sum_{j<K} f(u_j, j) + sum_{g<G} LSE_{c<C} u_{gC+c},   dE/dx = W^T phi,   phi_j = f'(u_j, j) + [j < G C] softmax_g(u)_c
+ * -- multinomial logistic (softmax) regression: G = n_groups data rows of C = group_size classes as the FIRST G C experts
+ * (group g is the experts g C .. g C + C - 1), then plain experts (a prior) exactly as in a tall model.  2 <= C <= 16,
+ * G >= 1, G C <= nexperts <= 2^20, 1 <= ndims <= 512; nexperts <= 512 is legal.  f, f', p[k], q[m] and j (the caller's
+ * expert index) are as for the tall entry point.  The group term is float32 in one stated order: m = fmaxf over c
+ * ascending, t_c = expf(u_c - m), s = t_0 + ... + t_{C-1}, the term m + logf(s), the softmax t_c / s (IEEE division): no
+ * overflow for any finite u.  The experts are stored so that a group lies in the registers of one lane of the matrix-core
+ * tile (mjhmc_linear_grouped_layout); one fused kernel, compiled with hipRTC at creation for this C, walks the grouped
+ * blocks and then the plain ones.  The kind is MJHMC_E_LINEAR_EXPR and the sampler runs the multi-pass path with either state
+ * dtype, as for a tall model of any nexperts.  The per-expert passes (mjhmc_pointwise_create, mjhmc_influence_create) refuse
+ * a grouped energy: MJHMC_ERR_UNSUPPORTED.  group_size < 2, n_groups < 1, G C > nexperts, NULLs, more than 4 expert rows,
+ * non-finite W / b, compile errors (with the log): MJHMC_ERR_INVALID.  group_size > 16, ndims > 512, more than 2^20 slots:
+ * MJHMC_ERR_UNSUPPORTED, naming the limit. */
+int mjhmc_energy_create_linear_grouped(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
+                                       int group_size, int64_t n_groups, const char* energy_expr, const char* grad_expr,
+                                       const double* params, size_t nparams, const double* expert_params, int n_expert_rows,
+                                       const char* include_dir, mjhmc_energy** out);
+/* compile-only check of a grouped linear-model energy (needs no device): 0, MJHMC_ERR_INVALID, MJHMC_ERR_UNSUPPORTED as above */
+int mjhmc_linear_grouped_check(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* energy_expr,
+                               const char* grad_expr, const char* include_dir);
+/* The storage order of a grouped model (needs no device): *n_slots = the slots, (grouped blocks + plain blocks) * P with
+ * P = ndims padded to 128, 256 or 512, and, when slot_to_expert is not NULL (room for *n_slots entries; call once with
+ * NULL for the size), the caller's expert of every slot, -1 for padding.  Slot blk P + 32 NB w + NB r32 + r (NB = P / 128,
+ * w < 4 the wave, r32 = (q & 3) + 8 (q >> 2) + 4 h the accumulator row of register q < 16 in lane half h, r < NB) is slot
+ * s = NB q + r of lane type (w, h); a lane type of a grouped block holds Gl = floor(16 NB / C) groups, group
+ * (8 blk + 2 w + h) Gl + gl in its slots C gl .. C gl + C - 1.  The arguments are checked as by mjhmc_linear_grouped_check. */
+int mjhmc_linear_grouped_layout(int ndims, int64_t nexperts, int group_size, int64_t n_groups, int64_t* slot_to_expert,
+                                int64_t* n_slots);
 int mjhmc_energy_destroy(mjhmc_energy* e);
 
 /* One evaluation of E_val / dEdX_val (mjhmc/misc/distributions.py:66-81) on n columns.

@@ -471,6 +471,55 @@ int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr
   return rc ? fail(rc, err) : 0;
 }
 
+int mjhmc_energy_create_linear_grouped(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
+                                       int group_size, int64_t n_groups, const char* energy_expr, const char* grad_expr,
+                                       const double* params, size_t nparams, const double* expert_params, int n_expert_rows,
+                                       const char* include_dir, mjhmc_energy** out) {
+  TRY(linear_grouped_check_args(ndims, nexperts, group_size, n_groups, energy_expr, grad_expr, include_dir));
+  if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
+  if (nparams && !params) return fail(MJHMC_ERR_INVALID, "params is NULL");
+  if (n_expert_rows < 0 || n_expert_rows > 4 || (n_expert_rows && !expert_params))
+    return fail(MJHMC_ERR_INVALID, "LINEAR_EXPR takes 0 to 4 per-expert parameter rows");
+  for (size_t i = 0, n = (size_t)nexperts * ndims; i < n; ++i)
+    if (!std::isfinite(W[i])) return fail(MJHMC_ERR_INVALID, "W has a non-finite entry (row " + std::to_string(i / ndims) + ")");
+  for (int64_t j = 0; j < nexperts; ++j)
+    if (!std::isfinite(b[j])) return fail(MJHMC_ERR_INVALID, "b has a non-finite entry (" + std::to_string(j) + ")");
+  HIPCHK(hipSetDevice(ctx->device));
+  mjhmc_energy* e = new mjhmc_energy();
+  e->ctx = ctx;
+  std::memset(&e->ep, 0, sizeof(e->ep));
+  e->ep.kind = MJHMC_E_LINEAR_EXPR;
+  e->ep.ndims = ndims;
+  const int rc = linear_grouped_energy_build(e, nexperts, W, b, group_size, n_groups, energy_expr, grad_expr, params, nparams,
+                                             expert_params, n_expert_rows, include_dir);
+  if (rc) return destroy_keeping_error(e, rc);
+  *out = e;
+  return 0;
+}
+
+int mjhmc_linear_grouped_check(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* energy_expr,
+                               const char* grad_expr, const char* include_dir) {
+  TRY(linear_grouped_check_args(ndims, nexperts, group_size, n_groups, energy_expr, grad_expr, include_dir));
+  std::string err;
+  const std::vector<char>* code = nullptr;
+  const std::vector<std::string>* lowered = nullptr;
+  const int dim = linear_grouped_layout(ndims, nexperts, group_size, n_groups).P;
+  const int rc = linear_grouped_compile(energy_expr, grad_expr, dim, group_size, include_dir, &err, &code, &lowered);
+  return rc ? fail(rc, err) : 0;
+}
+
+int mjhmc_linear_grouped_layout(int ndims, int64_t nexperts, int group_size, int64_t n_groups, int64_t* slot_to_expert,
+                                int64_t* n_slots) {
+  if (!n_slots) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  TRY(linear_grouped_check_args(ndims, nexperts, group_size, n_groups, "", "", ""));
+  const LinGroupedLayout L = linear_grouped_layout(ndims, nexperts, group_size, n_groups);
+  *n_slots = L.nslots;
+  if (slot_to_expert)
+    for (int64_t s = 0; s < L.nslots; ++s) slot_to_expert[s] = linear_grouped_slot_expert(L, nexperts, group_size, n_groups, s);
+  return 0;
+}
+
 int mjhmc_energy_destroy(mjhmc_energy* e) {
   if (!e) return 0;
   user_energy_free(e);

@@ -12,7 +12,9 @@
 // and leap -- 14 kernels.  The cold-list, fix and decide kernels take no model and are the library's own.  Everything
 // else (dE/dX storage, call blocks, parts, the multi-pass path at L = 0, state operations) is ProductOfT's: is_pot().
 // Models with more experts than 512 (K <= 2^20, D <= 512) are the second half of this file: one fused kernel over expert
-// blocks (dense_lin_tall.hpp) as the force of the multi-pass path.
+// blocks (dense_lin_tall.hpp) as the force of the multi-pass path.  Grouped models (a log-sum-exp
+// over groups of experts: softmax regression) are the third part: the tall form with a permuted layout and a kernel of its
+// own (dense_lin_grouped.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "dense_lin_grouped.hpp"   // LinGroupedModel (the kernel itself is compiled by hipRTC)
 #include "handles.hpp"
 #include "linear_energy.hpp"
 
@@ -338,11 +341,175 @@ void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E
   a.first_pid = 0;
   a.D = e->ep.ndims;
   a.key = RngKey{0u, 0u, 0u, 0u};
-  const LinTallModel tm{e->pot[0], e->pot[1], e->pot[2], e->lin->tall_nblk, e->ep.ndims, e->lin->tall_K};
   const PotLinear lin = e->lin->gen.lin;
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
+  if (e->lin->grouped()) {   // lin_grouped_eval_kernel (dense_lin_grouped.hpp): the same arguments around its own model
+    const LinGroupedModel gm{e->pot[0], e->pot[1], e->pot[2], e->lin->grp_nbg, e->lin->grp_nbp, e->ep.ndims, e->lin->tall_K, e->lin->grp_G};
+    void* params[] = {(void*)&a, (void*)&gm, (void*)&lin};
+    (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
+    return;
+  }
+  const LinTallModel tm{e->pot[0], e->pot[1], e->pot[2], e->lin->tall_nblk, e->ep.ndims, e->lin->tall_K};
   void* params[] = {(void*)&a, (void*)&tm, (void*)&lin};
   (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Grouped models: the tall form plus sum_g LSE_c u_{gC+c} over the first G groups of C experts.
+// The layout: blocks of P = the pad of D; a lane type (w, h) of a block holds 16 NB slots, slot s = NB q + r at local
+// column 32 NB w + NB acc_row(q, h) + r, and takes Gl = floor(16 NB / C) whole groups, group gl in slots [C gl, C gl + C);
+// a block takes the 8 Gl groups (8 blk + 2 w + h) Gl + gl.  The plain experts follow in blocks of their own, in caller
+// order.  The energy is lin_tall() (the multi-pass path, lin_tall_eval above) with its own kernel.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+std::string linear_grouped_source(const std::string& energy_expr, const std::string& grad_expr, int group_size) {
+  std::string s;
+  s += "#include \"dense_lin_grouped.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += user_functor_source(energy_expr, grad_expr);
+  s += "constexpr int kGroupSize = " + std::to_string(group_size) + ";   // members per group: the register loops are unrolled over it\n";
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_grouped_eval_kernel(const PotEvalArgs a, const LinGroupedModel gm, const PotLinear lin) {\n";
+  s += "  __shared__ Shared<NB> sh;\n  lin_grouped_eval_tiles<NB, kGroupSize, LinUserF>(a, gm, lin, sh);\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
+}  // namespace
+
+LinGroupedLayout linear_grouped_layout(int ndims, int64_t nexperts, int group_size, int64_t n_groups) {
+  LinGroupedLayout L;
+  L.P = tall_pad(ndims);
+  L.Gl = 16 * (L.P / 128) / group_size;
+  const int64_t per_block = 8 * L.Gl, plain = nexperts - n_groups * group_size;
+  L.nbg = (int)((n_groups + per_block - 1) / per_block);
+  L.nbp = (int)((plain + L.P - 1) / L.P);
+  L.nslots = (int64_t)(L.nbg + L.nbp) * L.P;
+  return L;
+}
+
+int64_t linear_grouped_slot_expert(const LinGroupedLayout& L, int64_t nexperts, int group_size, int64_t n_groups, int64_t slot) {
+  const int NB = L.P / 128;
+  const int64_t blk = slot / L.P, local = slot % L.P;
+  if (blk >= L.nbg) {
+    const int64_t j = n_groups * group_size + (blk - L.nbg) * L.P + local;
+    return j < nexperts ? j : -1;
+  }
+  const int w = (int)local / (32 * NB), row = (int)local % (32 * NB) / NB, r = (int)local % NB;
+  const int h = (row >> 2) & 1, q = (row & 3) + 4 * (row >> 3);   // row = acc_row(q, h) = (q & 3) + 8 (q >> 2) + 4 h
+  const int s = NB * q + r, gl = s / group_size, c = s % group_size;
+  if (gl >= L.Gl) return -1;
+  const int64_t g = (8 * blk + 2 * w + h) * L.Gl + gl;
+  return g < n_groups ? g * group_size + c : -1;
+}
+
+int linear_grouped_check_args(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* energy_expr,
+                              const char* grad_expr, const char* include_dir) {
+  if (!energy_expr || !grad_expr || !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (ndims < 1 || nexperts < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "LINEAR_EXPR needs ndims >= 1 and nexperts >= 1");
+  if (group_size < 2)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "a grouped LINEAR_EXPR model needs group_size >= 2 (got " + std::to_string(group_size) + ")");
+  if (n_groups < 1)
+    return mjhmc_fail(MJHMC_ERR_INVALID, "a grouped LINEAR_EXPR model needs n_groups >= 1 (got " + std::to_string(n_groups) + ")");
+  if (group_size > kLinGroupMax)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a grouped LINEAR_EXPR model takes groups of at most 16 experts (got group_size = " +
+                                             std::to_string(group_size) + "): a group lies in one lane's 16 registers per block");
+  if (nexperts > kLinTallMaxExperts || n_groups > kLinTallMaxExperts || n_groups * group_size > nexperts)
+    return nexperts > kLinTallMaxExperts || n_groups > kLinTallMaxExperts
+               ? mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a grouped LINEAR_EXPR model takes at most 1048576 (2^20) slots (got " +
+                                                       std::to_string(nexperts) + " experts, " + std::to_string(n_groups) + " groups)")
+               : mjhmc_fail(MJHMC_ERR_INVALID, "the " + std::to_string(n_groups) + " groups of " + std::to_string(group_size) +
+                                                   " are more than the model's " + std::to_string(nexperts) + " experts");
+  if (ndims > kPotDim)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a grouped LINEAR_EXPR model takes at most 512 dims (got " + std::to_string(ndims) +
+                                             "): its expert blocks are the tile kernels' 512 x 512 at the most");
+  const LinGroupedLayout L = linear_grouped_layout(ndims, nexperts, group_size, n_groups);
+  if (L.nslots > kLinTallMaxExperts)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a grouped LINEAR_EXPR model takes at most 1048576 (2^20) slots (these " +
+                                             std::to_string(n_groups) + " groups of " + std::to_string(group_size) + " and " +
+                                             std::to_string(nexperts - n_groups * group_size) + " plain experts need " +
+                                             std::to_string(L.nslots) + " in blocks of " + std::to_string(L.P) + ")");
+  return 0;
+}
+
+int linear_grouped_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, int group_size,
+                           const std::string& include_dir, std::string* err, const std::vector<char>** code,
+                           const std::vector<std::string>** lowered) {
+  const int NB = dim / 128;
+  const std::string src = linear_grouped_source(energy_expr, grad_expr, group_size);
+  const std::string key = src + "\n// grouped, C = " + std::to_string(group_size) + ", NB = " + std::to_string(NB) + ", -I" + include_dir;
+  std::lock_guard<std::mutex> lk(g_cache_mu);
+  auto it = g_cache.find(key);
+  if (it == g_cache.end()) {
+    std::unique_ptr<Compiled> c(new Compiled());
+    const int rc = rtc_compile(src, "mjhmc_linear_grouped.hip", include_dir, {"mjhmc::lin_grouped_eval_kernel<" + std::to_string(NB) + ">"},
+                               &c->code, &c->lowered, err);
+    if (rc) return rc;
+    it = g_cache.emplace(key, std::move(c)).first;
+  }
+  *code = &it->second->code;
+  *lowered = &it->second->lowered;
+  return 0;
+}
+
+int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, int group_size,
+                                int64_t n_groups, const char* energy_expr, const char* grad_expr, const double* params,
+                                size_t nparams, const double* expert_params, int n_expert_rows, const char* include_dir) {
+  const int D = e->ep.ndims, K = (int)nexperts;
+  const LinGroupedLayout L = linear_grouped_layout(D, nexperts, group_size, n_groups);
+  const int P = L.P;
+  const size_t S = (size_t)L.nslots;
+  LinearEnergy* l = new LinearEnergy();
+  e->lin = l;
+  const std::vector<char>* code = nullptr;
+  const std::vector<std::string>* lowered = nullptr;
+  std::string err;
+  const int rc = linear_grouped_compile(energy_expr, grad_expr, P, group_size, include_dir, &err, &code, &lowered);
+  if (rc) return mjhmc_fail(rc, err);
+  HIPCHK(hipModuleLoadData(&l->module, code->data()));
+  HIPCHK(hipModuleGetFunction(&l->tall, l->module, (*lowered)[0].c_str()));
+  l->tall_nblk = L.nbg + L.nbp;
+  l->tall_K = K;
+  l->grp_C = group_size;
+  l->grp_G = (int)n_groups;
+  l->grp_nbg = L.nbg;
+  l->grp_nbp = L.nbp;
+  e->pot_dim = P;      // the state rows' pitch: the pad of D
+  e->pot_rows = D;
+
+  // W1b[blk][d][local] = W2Tb[blk][local][d] = W[expert of slot blk P + local][d], cb likewise, zero in the padding; float32
+  const size_t M = (size_t)P * P, mat_bytes = S * P * sizeof(float), nrows = (size_t)4 * S + (nparams ? nparams : 1);
+  std::vector<float> w1(S * P, 0.f), w2t(S * P, 0.f), cb(S, 0.f), rows(nrows, 0.f);
+  for (size_t slot = 0; slot < S; ++slot) {
+    const int64_t j = linear_grouped_slot_expert(L, nexperts, group_size, n_groups, (int64_t)slot);
+    if (j < 0) continue;
+    const size_t blk = slot / P, jl = slot % P;
+    cb[slot] = (float)b[j];
+    for (int d = 0; d < D; ++d) {
+      const float w = (float)W[(size_t)j * D + d];
+      w1[blk * M + (size_t)d * P + jl] = w;
+      w2t[blk * M + jl * P + d] = w;
+    }
+    for (int m = 0; m < n_expert_rows; ++m) rows[(size_t)m * S + slot] = (float)expert_params[(size_t)m * K + j];
+  }
+  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * S + k] = (float)params[k];
+  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
+  const size_t bytes[3] = {mat_bytes, mat_bytes, S * sizeof(float)};
+  for (int i = 0; i < 3; ++i) {
+    if (hipMalloc((void**)&e->pot[i], bytes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      e->pot[i] = nullptr;
+      return mjhmc_fail(MJHMC_ERR_HIP, "a grouped LINEAR_EXPR model of " + std::to_string(D) + " dims x " + std::to_string(K) +
+                                       " experts needs " + std::to_string(2 * mat_bytes) + " bytes of device memory for its matrices (" +
+                                       std::to_string(L.nbg + L.nbp) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
+                                       ", twice): the allocation failed");
+    }
+    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
+  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
+  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * S, K, (int)S};
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

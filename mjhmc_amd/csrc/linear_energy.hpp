@@ -18,6 +18,10 @@ struct LinearEnergy {
   // tile kernels of `gen` are then absent (gen.lin alone is used) and the sampler runs the multi-pass path
   hipFunction_t tall = nullptr;
   int tall_nblk = 0, tall_K = 0;
+  // a grouped model: `tall` is lin_grouped_eval_kernel, the blocks are grp_nbg grouped ones and then
+  // grp_nbp plain ones (tall_nblk in all), grp_C members per group (0: not grouped), grp_G groups
+  int grp_C = 0, grp_G = 0, grp_nbg = 0, grp_nbp = 0;
+  bool grouped() const { return grp_C != 0; }
 };
 
 constexpr int64_t kLinTallMaxExperts = (int64_t)1 << 20;
@@ -44,6 +48,26 @@ int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W,
                              int n_expert_rows, const char* include_dir);
 // E (or none) and dE/dX (or none) of float32 rows X32 [rows_pad][pad of ndims] (rows_pad a multiple of 32) on `st`
 void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st);
+
+// Grouped models: the first n_groups * group_size experts are groups under a log-sum-exp, stored so that
+// a group lies in one lane's registers (dense_lin_grouped.hpp); 2 <= group_size <= 16, at most 2^20 slots
+constexpr int kLinGroupMax = 16;
+struct LinGroupedLayout {
+  int P, Gl, nbg, nbp;   // the pad of ndims, groups per lane type, grouped blocks, plain blocks
+  int64_t nslots;        // (nbg + nbp) P
+};
+LinGroupedLayout linear_grouped_layout(int ndims, int64_t nexperts, int group_size, int64_t n_groups);
+// the caller's expert of a slot, -1 for padding
+int64_t linear_grouped_slot_expert(const LinGroupedLayout& L, int64_t nexperts, int group_size, int64_t n_groups, int64_t slot);
+int linear_grouped_check_args(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* energy_expr,
+                              const char* grad_expr, const char* include_dir);
+// the hipRTC compile of lin_grouped_eval_kernel<dim / 128> with the group size a constant of the source
+int linear_grouped_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, int group_size,
+                           const std::string& include_dir, std::string* err, const std::vector<char>** code,
+                           const std::vector<std::string>** lowered);
+int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, int group_size,
+                                int64_t n_groups, const char* energy_expr, const char* grad_expr, const double* params,
+                                size_t nparams, const double* expert_params, int n_expert_rows, const char* include_dir);
 
 // The per-expert statistics pass (dense_lin_pointwise.hpp, pointwise.hip): the padded dimension of the blocks a model of
 // (ndims, nexperts) is stored in (the tall layout beyond 512 experts, the square one otherwise; 0: no such model), and the

@@ -165,6 +165,11 @@ int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_ma
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, std::string("the pointwise statistics are those of the experts of a linear-model energy "
                                                          "(MJHMC_E_LINEAR_EXPR): the sampler's energy is MJHMC_E_") +
                                                  energy_kind_name(e->ep.kind) + ", which has no experts u = W x + b to report on");
+  if (e->lin->grouped())
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the pointwise statistics of a grouped linear model (mjhmc_energy_create_linear_grouped) "
+                                             "are not formed: its experts are stored in a permuted order and the terms of a group "
+                                             "are coupled through its log-sum-exp, while this pass reports per expert in the "
+                                             "caller's order");
   if (s->dtype != MJHMC_F64 && s->dtype != MJHMC_F32)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "linear models run with float32 or float64 state");
   if (!s->ring) return acc_no_ring(nullptr);

@@ -130,6 +130,36 @@ def tall_linear_arrays(W, b, params=(), expert_params=None):
     return linear_arrays(W, b, params, expert_params, _tall=True)
 
 
+GROUP_MAX = 16                  # mjhmc_energy_create_linear_grouped: members of a group
+
+
+def grouped_linear_arrays(W, b, groups, params=(), expert_params=None):
+    """linear_arrays for a grouped model (mjhmc_energy_create_linear_grouped) and its checked ``groups`` = (C, G): the first
+    G * C rows of W are G groups of C consecutive experts under a log-sum-exp; 2 <= C <= 16, G >= 1, G * C <= K."""
+    W, b, params, q = linear_arrays(W, b, params, expert_params, _tall=True)
+    try:
+        C, G = (int(v) for v in groups)
+    except (TypeError, ValueError):
+        raise ValueError('groups must be (C, G): the group size and the number of groups, got %r' % (groups,))
+    if C < 2 or C > GROUP_MAX:
+        raise ValueError('a grouped linear model takes groups of 2 to %d experts, got C = %d' % (GROUP_MAX, C))
+    if G < 1 or G * C > W.shape[0]:
+        raise ValueError('a grouped linear model needs 1 <= G and G * C <= K: got G = %d, C = %d, K = %d' % (G, C, W.shape[0]))
+    return W, b, params, q, (C, G)
+
+
+def grouped_linear_layout(ndims, nexperts, groups, lib=None):
+    """The storage order of a grouped model (mjhmc_linear_grouped_layout; needs no device): int64 (n_slots,), the caller's
+    expert of every slot, -1 for padding."""
+    lib = lib or _lib.load()
+    C, G = groups
+    n = ctypes.c_int64(0)
+    check(lib.mjhmc_linear_grouped_layout(int(ndims), int(nexperts), int(C), int(G), None, ctypes.byref(n)), lib)
+    out = np.empty(n.value, dtype=np.int64)
+    check(lib.mjhmc_linear_grouped_layout(int(ndims), int(nexperts), int(C), int(G), ptr(out), ctypes.byref(n)), lib)
+    return out
+
+
 def context(device=0):
     """Process-wide context per device index."""
     if device not in _contexts:
@@ -208,6 +238,30 @@ class DeviceEnergy(object):
         h = ctypes.c_void_p()
         check(ctx.lib.mjhmc_energy_create_linear_tall(
             ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), str(energy_expr).encode(), str(grad_expr).encode(),
+            ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
+            _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
+        self.handle = h
+        return self
+
+    @classmethod
+    def from_linear_grouped(cls, ctx, W, b, groups, energy_expr, grad_expr, params=(), expert_params=None):
+        """The tall form with a log-sum-exp over groups of experts (mjhmc_energy_create_linear_grouped):
+            E(x) = sum_j f(u_j, j) + sum_{g<G} LSE_{c<C} u_{gC+c},   dE/dx = W^T (f'(u) + softmax within the groups);
+        ``groups`` = (C, G): the first G * C rows of W are G groups of C consecutive experts (softmax regression: a data
+        row per group, a class per member), the rest plain experts; 2 <= C <= 16, D <= 512, K <= 2**20.  ``j`` in the
+        expressions is the caller's expert index.  Samplers of it run the engine's multi-pass path."""
+        W, b, params, q, (C, G) = grouped_linear_arrays(W, b, groups, params, expert_params)
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.kind = _lib.E_LINEAR_EXPR
+        self.nexperts, self.ndims = W.shape
+        self.params = params
+        self.W, self.b, self.expert_params = W, b, q
+        self.tall = True
+        self.groups = (C, G)
+        h = ctypes.c_void_p()
+        check(ctx.lib.mjhmc_energy_create_linear_grouped(
+            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), C, G, str(energy_expr).encode(), str(grad_expr).encode(),
             ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
             _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
         self.handle = h

@@ -47,10 +47,15 @@ class Distribution(object):
             kind, params = self.device_energy()
             if kind == _lib.E_USER_EXPR:                   # params = (energy_expr, grad_expr, float64 parameters, stats, energy0_expr)
                 self._dev = engine.DeviceEnergy.from_expr(engine.context(device), self.ndims, *params)
-            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=[, tall=])
-                make = engine.DeviceEnergy.from_linear_tall if params.get('tall') else engine.DeviceEnergy.from_linear
-                self._dev = make(engine.context(device), params['W'], params.get('b'), params['energy'], params['grad'],
-                                 params.get('params', ()), params.get('expert_params'))
+            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=[, tall=][, groups=])
+                if params.get('groups'):
+                    self._dev = engine.DeviceEnergy.from_linear_grouped(
+                        engine.context(device), params['W'], params.get('b'), params['groups'], params['energy'], params['grad'],
+                        params.get('params', ()), params.get('expert_params'))
+                else:
+                    make = engine.DeviceEnergy.from_linear_tall if params.get('tall') else engine.DeviceEnergy.from_linear
+                    self._dev = make(engine.context(device), params['W'], params.get('b'), params['energy'], params['grad'],
+                                     params.get('params', ()), params.get('expert_params'))
             elif kind == _lib.E_HOST:                      # params = (energy_func, energy_grad_func): opaque callables
                 self._dev = engine.DeviceEnergy.host(engine.context(device), self.ndims, *params)
             else:
@@ -171,11 +176,17 @@ class LambdaDistribution(Distribution):
       fused matrix-core kernel that walks the experts in blocks of the padded D (mjhmc_energy_create_linear_tall); ``j`` is
       the global expert index.  Samplers run the engine's multi-pass path with either ``state_dtype``; the callables are
       checked at the same float32-force bar;
+    * ``device_linear_grouped=dict(W=, b=, groups=(C, G), energy=, grad=, params=(), expert_params=None)``: the tall contract
+      plus a log-sum-exp over groups of experts, ``E(x) = sum_j energy(u_j, j) + sum_{g<G} LSE_{c<C} u_{gC+c}`` -- the
+      first G * C rows of W are G groups of C consecutive experts (softmax regression: a data row per group, a class per
+      member; 2 <= C <= 16), the rest plain experts -- on a fused matrix-core kernel of its own
+      (mjhmc_energy_create_linear_grouped); ``j`` is the caller's expert index.  The multi-pass path, the same bar;
     * ``device_energy=(kind, params)``: one of the built-in device energies by name.
     """
 
     def __init__(self, energy_func=None, energy_grad_func=None, init=None, name=None, device_energy=None,
-                 device_expr=None, device_params=(), device_linear=None, state_dtype='float64', device_linear_tall=None):
+                 device_expr=None, device_params=(), device_linear=None, state_dtype='float64', device_linear_tall=None,
+                 device_linear_grouped=None):
         self.energy_func = energy_func
         self.energy_grad_func = energy_grad_func
         self.init = np.array(init, dtype=np.float64)
@@ -183,9 +194,24 @@ class LambdaDistribution(Distribution):
         self._functor = device_energy
         self._checked = False
         self._bar32 = False
-        if device_linear is not None and device_linear_tall is not None:
-            raise ValueError('give device_linear or device_linear_tall, not both')
-        if device_linear is not None or device_linear_tall is not None:
+        if sum(m is not None for m in (device_linear, device_linear_tall, device_linear_grouped)) > 1:
+            raise ValueError('give device_linear or device_linear_tall, not both' if device_linear_grouped is None else
+                             'give one of device_linear, device_linear_tall and device_linear_grouped')
+        if device_linear_grouped is not None:
+            if state_dtype not in ('float32', 'float64'):
+                raise ValueError("device_linear state_dtype must be 'float32' or 'float64'")
+            self.state_dtype = state_dtype
+            lin = dict(device_linear_grouped)
+            if 'groups' not in lin:
+                raise ValueError('device_linear_grouped needs groups=(C, G)')
+            W, b, params, q, groups = engine.grouped_linear_arrays(lin['W'], lin.get('b'), lin['groups'], lin.get('params', ()),
+                                                                   lin.get('expert_params'))
+            if W.shape[1] != self.init.shape[0]:
+                raise ValueError('W has %d columns but init has %d dims' % (W.shape[1], self.init.shape[0]))
+            self._functor = (_lib.E_LINEAR_EXPR, dict(W=W, b=b, energy=str(lin['energy']), grad=str(lin['grad']), params=params,
+                                                      expert_params=q, tall=True, groups=groups))
+            self._bar32 = True
+        elif device_linear is not None or device_linear_tall is not None:
             tall = device_linear_tall is not None
             if state_dtype not in ('float32', 'float64'):
                 raise ValueError("device_linear state_dtype must be 'float32' or 'float64'")
@@ -589,6 +615,118 @@ class GeneralizedLinearModel(Distribution):
         h = hashlib.sha1()
         h.update(self.family.encode())
         for a in (self.features, self.targets, [self.prior_scale, self.noise_scale]):
+            h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        return int(h.hexdigest()[:15], 16)
+
+
+class MultinomialLogisticRegression(Distribution):
+    """Posterior of the coefficients of a multinomial logistic (softmax) regression under the prior B ~ N(0, prior_scale^2 I):
+    ``features`` (n, F), ``targets`` (n,) integers in 0 .. C - 1, ``n_classes`` = C (2 <= C <= 16).  The state is
+    x = vec(B), B (C, F) row-major, ndims = C F <= 512, and P(y = c | a) = softmax(B a)_c, so
+
+        E(x) = sum_i [ LSE_c (B a_i)_c - (B a_i)_{y_i} ] + |x|^2 / (2 prior_scale^2).
+
+    A grouped linear-model energy (mjhmc_energy_create_linear_grouped) of K = n C + C F experts: data expert i C + c has
+    the row a_i in block c of x, q[0] = [c == y_i] and q[1] = 1 with f = -q[0] u (the log-sum-exp of the group is the
+    kernel's); then the prior as C F more experts with rows I / prior_scale and f = u^2 / 2, selected by q[1] = 0 as
+    GeneralizedLinearModel selects its prior.  ``E_host`` / ``dEdX_host`` are the same energy in float64 NumPy with a stable
+    log-sum-exp; ``predict_proba(X)`` gives the class probabilities of ``features`` under coefficient vectors, on the
+    host.  ``gen_init_X`` draws N(0, init_scale^2) (from ``seed`` when given)."""
+
+    def __init__(self, features, targets, n_classes, prior_scale=1.0, nbatch=100, init_scale=0.1, seed=None,
+                 state_dtype='float64'):
+        if state_dtype not in ('float32', 'float64'):
+            raise ValueError("MultinomialLogisticRegression state_dtype must be 'float32' or 'float64'")
+        A = np.array(features, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] < 1:
+            raise ValueError('features must be an (n, F) matrix, got shape %r' % (A.shape,))
+        n, F = A.shape
+        C = int(n_classes)
+        if C != n_classes or C < 2 or C > engine.GROUP_MAX:
+            raise ValueError('n_classes must be an integer in 2 .. %d, got %r' % (engine.GROUP_MAX, n_classes))
+        y = np.asarray(targets)
+        if y.shape != (n,):
+            raise ValueError('targets must have one entry per row of features (%d), got shape %r' % (n, y.shape))
+        yi = y.astype(np.int64)
+        if not np.all(yi == y) or yi.min() < 0 or yi.max() >= C:
+            raise ValueError('targets must be integers in 0 .. n_classes - 1 = %d' % (C - 1))
+        if not prior_scale > 0:
+            raise ValueError('prior_scale must be positive')
+        if C * F > 512:
+            raise ValueError('ndims = n_classes * F = %d is more than the 512 dims a linear model takes' % (C * F))
+        self.features, self.targets, self.n_classes = A, yi, C
+        self.prior_scale, self.init_scale, self.seed = float(prior_scale), float(init_scale), seed
+        D = C * F
+        Wd = np.zeros((n, C, D))
+        for c in range(C):
+            Wd[:, c, c * F:(c + 1) * F] = A
+        self.W = np.vstack([Wd.reshape(n * C, D), np.eye(D) / self.prior_scale])
+        self.b = np.zeros(n * C + D)
+        onehot = (np.arange(C)[None, :] == yi[:, None]).astype(np.float64).reshape(-1)
+        self.q = np.vstack([np.concatenate([onehot, np.zeros(D)]), np.concatenate([np.ones(n * C), np.zeros(D)])])
+        self.groups = (C, n)
+        engine.grouped_linear_arrays(self.W, self.b, self.groups, (), self.q)       # the size limits, before anything else
+        self.nexperts = n * C + D
+        self.state_dtype = state_dtype
+        self.backend = 'hip-mfma'
+        super(MultinomialLogisticRegression, self).__init__(D, nbatch)
+
+    def device_energy(self):
+        return (_lib.E_LINEAR_EXPR, dict(W=self.W, b=self.b, energy='q[1] != 0.f ? -q[0]*u : 0.5f*u*u',
+                                         grad='q[1] != 0.f ? -q[0] : u', params=(), expert_params=self.q, tall=True,
+                                         groups=self.groups))
+
+    @property
+    def n_data(self):
+        return int(self.features.shape[0])
+
+    def _logits(self, X):
+        """(n, C, N): B a_i for every coefficient vector (column) of X"""
+        X = np.asarray(X, dtype=np.float64)
+        B = X.reshape(self.n_classes, self.features.shape[1], -1)
+        return np.einsum('if,cfn->icn', self.features, B)
+
+    @staticmethod
+    def _lse(u):
+        """stable log-sum-exp over axis 1, and the softmax"""
+        m = u.max(axis=1, keepdims=True)
+        t = np.exp(u - m)
+        s = t.sum(axis=1, keepdims=True)
+        return (m + np.log(s))[:, 0], t / s
+
+    def E_host(self, X):
+        X = np.asarray(X, dtype=np.float64)
+        u = self._logits(X)
+        lse, _ = self._lse(u)
+        own = np.take_along_axis(u, self.targets[:, None, None], axis=1)[:, 0]
+        prior = 0.5 * np.sum(X * X, axis=0) / self.prior_scale ** 2
+        return ((lse - own).sum(axis=0) + prior).reshape((1, -1))
+
+    def dEdX_host(self, X):
+        X = np.asarray(X, dtype=np.float64)
+        _, sm = self._lse(self._logits(X))
+        sm[np.arange(sm.shape[0]), self.targets] -= 1.0
+        G = np.einsum('icn,if->cfn', sm, self.features).reshape(X.shape)
+        return G + X / self.prior_scale ** 2
+
+    def predict_proba(self, X, features=None):
+        """(n, C, N): P(y = c | a_i) under every coefficient vector (column) of X (D, N); ``features``: other rows (m, F)"""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[:, None]
+        A = self.features if features is None else np.asarray(features, dtype=np.float64)
+        B = X.reshape(self.n_classes, self.features.shape[1], -1)
+        return self._lse(np.einsum('if,cfn->icn', A, B))[1]
+
+    def gen_init_X(self):
+        rs = np.random if self.seed is None else np.random.RandomState(self.seed)
+        self.Xinit = self.init_scale * rs.randn(self.ndims, self.nbatch)
+
+    def __hash__(self):
+        import hashlib
+        h = hashlib.sha1()
+        h.update(b'multinomial')
+        for a in (self.features, self.targets, [self.n_classes, self.prior_scale]):
             h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
         return int(h.hexdigest()[:15], 16)
 

@@ -644,6 +644,20 @@ class Waic(object):
         self.n_warn = int(np.sum(self.p_waic_i > 0.4))
 
 
+def refuse_grouped(distribution, what, why):
+    """ValueError when the distribution's energy is a grouped linear model (device_linear_grouped,
+    MultinomialLogisticRegression): the passes that cannot run on one name it."""
+    kind, params = distribution.device_energy()
+    if kind == _lib.E_LINEAR_EXPR and params.get('groups'):
+        raise ValueError('%s: the energy of %s is a grouped linear model (device_linear_grouped, '
+                         'MultinomialLogisticRegression: groups of %d experts under a log-sum-exp) -- %s'
+                         % (what, type(distribution).__name__, params['groups'][0], why))
+
+
+_GROUPED_PER_EXPERT = ('the per-expert passes report in the caller\'s order on terms that each see one u_j; a grouped model '
+                       'stores its experts in a permuted order and couples the members of a group')
+
+
 def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, compile_check=True):
     """The checks ``pointwise()`` makes before anything runs, none of which needs a device: returns
     (values, flags) or raises ValueError -- n_iter < 1, no value or more than 4, an energy that is not a linear model, an
@@ -657,6 +671,7 @@ def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, comp
         raise ValueError('pointwise: the per-expert statistics are those of a linear-model energy (LINEAR_EXPR: '
                          'device_linear, device_linear_tall, GeneralizedLinearModel); the energy of %s is %s'
                          % (type(distribution).__name__, names.get(kind, kind)))
+    refuse_grouped(distribution, 'pointwise', _GROUPED_PER_EXPERT)
     if values is None:
         if not hasattr(distribution, 'pointwise_values'):
             raise ValueError('pointwise: %s has no pointwise_values(); pass values=' % type(distribution).__name__)
@@ -759,6 +774,7 @@ def influence_request(distribution, n_iter, value=None, experts=None, sharded=Fa
         raise ValueError('influence: the influence of a data row is that of an expert of a linear-model energy (LINEAR_EXPR: '
                          'device_linear, device_linear_tall, GeneralizedLinearModel); the energy of %s is %s'
                          % (type(distribution).__name__, names.get(kind, kind)))
+    refuse_grouped(distribution, 'influence', _GROUPED_PER_EXPERT)
     if value is None:
         if not hasattr(distribution, 'influence_value'):
             raise ValueError('influence: %s has no influence_value(); pass value=' % type(distribution).__name__)
@@ -1320,7 +1336,8 @@ class HMCBase(object):
         promise of the error of ``mean``.
 
         ValueError, before anything runs: n_iter < 1; n_iter * nbatch <= 2 * ndims (the regression is not determined);
-        ndims > 512 or K > 512; an energy given as opaque callables; a sharded sampler (the sums are additive over ranks,
+        ndims > 512 or K > 512; an energy given as opaque callables; a grouped linear model (its sampler runs the multi-pass
+        path, which has no single-launch dE/dX; named); a sharded sampler (the sums are additive over ranks,
         but that is out of scope here: it has not been proved on a multi-rank machine)."""
         n_iter = int(n_iter)
         if n_iter < 1:
@@ -1334,6 +1351,9 @@ class HMCBase(object):
         if shift is not None and np.size(shift) != K:
             raise ValueError('shift must have %d entries' % K)
         self._check_of(of)
+        refuse_grouped(self.distribution, 'cv_expectations',
+                       'its sampler runs the multi-pass path with either state dtype, which has no single-launch '
+                       'evaluation of dE/dX to take the control variates from')
         if self.distribution.device_energy()[0] == _lib.E_HOST:
             raise ValueError('cv_expectations: the energy is a pair of opaque Python callables, which are its only '
                              'evaluation -- there is no device evaluation of dE/dX to take the control variates from')
@@ -1405,6 +1425,7 @@ class HMCBase(object):
         Vehtari (2014); the weighted population variance of the recorded states stands where they use S - 1.  The run is
         that of ``pointwise(n_iter)``.  ValueError for a distribution without those two methods."""
         d = self.distribution
+        refuse_grouped(d, 'waic', _GROUPED_PER_EXPERT)
         if not (hasattr(d, 'pointwise_values') and hasattr(d, 'log_lik_constants')):
             raise ValueError('waic: %s has no pointwise_values() / log_lik_constants() (GeneralizedLinearModel has)'
                              % type(d).__name__)
