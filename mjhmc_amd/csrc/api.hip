@@ -5,6 +5,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <functional>
 #include <vector>
 
 #include "autocor.hpp"
@@ -404,34 +405,55 @@ int mjhmc_expr_check(int ndims, const char* energy_expr, const char* grad_expr, 
   return mjhmc_expr_check_coupled(ndims, nullptr, energy_expr, nullptr, grad_expr, include_dir);
 }
 
-int mjhmc_energy_create_linear(mjhmc_ctx* ctx, int ndims, int nexperts, const double* W, const double* b,
-                               const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
-                               const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out) {
-  if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
-  TRY(linear_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+// What the three mjhmc_energy_create_linear* share; each entry point keeps its own order of checks (sizes before ctx for
+// the tall and the grouped form, after it for the square one).
+static int linear_check_model(const double* W, const double* b, const double* params, size_t nparams, const double* expert_params,
+                              int n_expert_rows) {
   if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
   if (nparams && !params) return fail(MJHMC_ERR_INVALID, "params is NULL");
   if (n_expert_rows < 0 || n_expert_rows > 4 || (n_expert_rows && !expert_params))
     return fail(MJHMC_ERR_INVALID, "LINEAR_EXPR takes 0 to 4 per-expert parameter rows");
+  return 0;
+}
+
+static int linear_check_finite(int ndims, int64_t nexperts, const double* W, const double* b) {
+  for (size_t i = 0, n = (size_t)nexperts * ndims; i < n; ++i)
+    if (!std::isfinite(W[i])) return fail(MJHMC_ERR_INVALID, "W has a non-finite entry (row " + std::to_string(i / ndims) + ")");
+  for (int64_t j = 0; j < nexperts; ++j)
+    if (!std::isfinite(b[j])) return fail(MJHMC_ERR_INVALID, "b has a non-finite entry (" + std::to_string(j) + ")");
+  return 0;
+}
+
+// a new MJHMC_E_LINEAR_EXPR energy on ctx's device, built by `build`; destroyed again, keeping the message, if that fails
+static int linear_energy_shell(mjhmc_ctx* ctx, int ndims, mjhmc_energy** out, const std::function<int(mjhmc_energy*)>& build) {
   HIPCHK(hipSetDevice(ctx->device));
   mjhmc_energy* e = new mjhmc_energy();
   e->ctx = ctx;
   std::memset(&e->ep, 0, sizeof(e->ep));
   e->ep.kind = MJHMC_E_LINEAR_EXPR;
   e->ep.ndims = ndims;
-  const int rc = linear_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params, n_expert_rows,
-                                     include_dir);
+  const int rc = build(e);
   if (rc) return destroy_keeping_error(e, rc);
   *out = e;
   return 0;
 }
 
+int mjhmc_energy_create_linear(mjhmc_ctx* ctx, int ndims, int nexperts, const double* W, const double* b,
+                               const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                               const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out) {
+  if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  TRY(linear_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  TRY(linear_check_model(W, b, params, nparams, expert_params, n_expert_rows));
+  return linear_energy_shell(ctx, ndims, out, [&](mjhmc_energy* e) {
+    return linear_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params, n_expert_rows, include_dir);
+  });
+}
+
 int mjhmc_linear_check(int ndims, int nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
   TRY(linear_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
   std::string err;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
-  const int rc = linear_compile(energy_expr, grad_expr, linear_dim(ndims, nexperts), include_dir, &err, &code, &lowered);
+  const RtcCode* c = nullptr;
+  const int rc = linear_compile(energy_expr, grad_expr, linear_dim(ndims, nexperts), include_dir, &err, &c);
   return rc ? fail(rc, err) : 0;
 }
 
@@ -440,34 +462,19 @@ int mjhmc_energy_create_linear_tall(mjhmc_ctx* ctx, int ndims, int64_t nexperts,
                                     const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out) {
   TRY(linear_tall_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
   if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
-  if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
-  if (nparams && !params) return fail(MJHMC_ERR_INVALID, "params is NULL");
-  if (n_expert_rows < 0 || n_expert_rows > 4 || (n_expert_rows && !expert_params))
-    return fail(MJHMC_ERR_INVALID, "LINEAR_EXPR takes 0 to 4 per-expert parameter rows");
-  for (size_t i = 0, n = (size_t)nexperts * ndims; i < n; ++i)
-    if (!std::isfinite(W[i])) return fail(MJHMC_ERR_INVALID, "W has a non-finite entry (row " + std::to_string(i / ndims) + ")");
-  for (int64_t j = 0; j < nexperts; ++j)
-    if (!std::isfinite(b[j])) return fail(MJHMC_ERR_INVALID, "b has a non-finite entry (" + std::to_string(j) + ")");
-  HIPCHK(hipSetDevice(ctx->device));
-  mjhmc_energy* e = new mjhmc_energy();
-  e->ctx = ctx;
-  std::memset(&e->ep, 0, sizeof(e->ep));
-  e->ep.kind = MJHMC_E_LINEAR_EXPR;
-  e->ep.ndims = ndims;
-  const int rc = linear_tall_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params,
-                                          n_expert_rows, include_dir);
-  if (rc) return destroy_keeping_error(e, rc);
-  *out = e;
-  return 0;
+  TRY(linear_check_model(W, b, params, nparams, expert_params, n_expert_rows));
+  TRY(linear_check_finite(ndims, nexperts, W, b));
+  return linear_energy_shell(ctx, ndims, out, [&](mjhmc_energy* e) {
+    return linear_tall_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params, n_expert_rows,
+                                    include_dir);
+  });
 }
 
 int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
   TRY(linear_tall_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
   std::string err;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
-  const int dim = ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim);
-  const int rc = linear_tall_compile(energy_expr, grad_expr, dim, include_dir, &err, &code, &lowered);
+  const RtcCode* c = nullptr;
+  const int rc = linear_tall_compile(energy_expr, grad_expr, tall_pad(ndims), include_dir, &err, &c);
   return rc ? fail(rc, err) : 0;
 }
 
@@ -477,35 +484,21 @@ int mjhmc_energy_create_linear_grouped(mjhmc_ctx* ctx, int ndims, int64_t nexper
                                        const char* include_dir, mjhmc_energy** out) {
   TRY(linear_grouped_check_args(ndims, nexperts, group_size, n_groups, energy_expr, grad_expr, include_dir));
   if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
-  if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
-  if (nparams && !params) return fail(MJHMC_ERR_INVALID, "params is NULL");
-  if (n_expert_rows < 0 || n_expert_rows > 4 || (n_expert_rows && !expert_params))
-    return fail(MJHMC_ERR_INVALID, "LINEAR_EXPR takes 0 to 4 per-expert parameter rows");
-  for (size_t i = 0, n = (size_t)nexperts * ndims; i < n; ++i)
-    if (!std::isfinite(W[i])) return fail(MJHMC_ERR_INVALID, "W has a non-finite entry (row " + std::to_string(i / ndims) + ")");
-  for (int64_t j = 0; j < nexperts; ++j)
-    if (!std::isfinite(b[j])) return fail(MJHMC_ERR_INVALID, "b has a non-finite entry (" + std::to_string(j) + ")");
-  HIPCHK(hipSetDevice(ctx->device));
-  mjhmc_energy* e = new mjhmc_energy();
-  e->ctx = ctx;
-  std::memset(&e->ep, 0, sizeof(e->ep));
-  e->ep.kind = MJHMC_E_LINEAR_EXPR;
-  e->ep.ndims = ndims;
-  const int rc = linear_grouped_energy_build(e, nexperts, W, b, group_size, n_groups, energy_expr, grad_expr, params, nparams,
-                                             expert_params, n_expert_rows, include_dir);
-  if (rc) return destroy_keeping_error(e, rc);
-  *out = e;
-  return 0;
+  TRY(linear_check_model(W, b, params, nparams, expert_params, n_expert_rows));
+  TRY(linear_check_finite(ndims, nexperts, W, b));
+  return linear_energy_shell(ctx, ndims, out, [&](mjhmc_energy* e) {
+    return linear_grouped_energy_build(e, nexperts, W, b, group_size, n_groups, energy_expr, grad_expr, params, nparams,
+                                       expert_params, n_expert_rows, include_dir);
+  });
 }
 
 int mjhmc_linear_grouped_check(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* energy_expr,
                                const char* grad_expr, const char* include_dir) {
   TRY(linear_grouped_check_args(ndims, nexperts, group_size, n_groups, energy_expr, grad_expr, include_dir));
   std::string err;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
+  const RtcCode* c = nullptr;
   const int dim = linear_grouped_layout(ndims, nexperts, group_size, n_groups).P;
-  const int rc = linear_grouped_compile(energy_expr, grad_expr, dim, group_size, include_dir, &err, &code, &lowered);
+  const int rc = linear_grouped_compile(energy_expr, grad_expr, dim, group_size, include_dir, &err, &c);
   return rc ? fail(rc, err) : 0;
 }
 

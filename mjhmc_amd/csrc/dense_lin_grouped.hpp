@@ -9,7 +9,7 @@
 // max, the sum of exponentials and the softmax between GEMM 1 and GEMM 2 are then an unrolled loop over registers with
 // static indices -- no cross-lane traffic, no LDS, no barrier beyond the tall kernel's two per block, and u never reaches
 // memory.  Grouped blocks come first; the plain experts follow in blocks of their own, laid out and evaluated exactly as
-// a tall model's (LinearTallExperts, dense_lin_tall.hpp).  Built from the tile kernels' parts as lin_tall_eval_tiles is.
+// a tall model's (LinearTallExperts, dense_lin_tall.hpp), through the family's block step (lin_block, dense_lin_tall.hpp).
 #pragma once
 #ifndef __HIPCC_RTC__  // hipRTC pre-includes the device runtime (linear_energy.hip)
 #include <hip/hip_runtime.h>
@@ -102,28 +102,6 @@ struct LinearGroupedExperts {
   }
 };
 
-// One block of lin_tall_eval_tiles' loop (dense_lin_tall.hpp), with the block's experts XP: cb -> LDS, u = cb + W1^T x,
-// the lane's energy terms, phi(u) published, g += W2T^T phi(u).  `next` is the matrix whose chunk 0 leaves in ar (NB > 1).
-template <int NB, class XP>
-__device__ __forceinline__ void lin_grouped_block(const PotModel& mdl, const XP& xp, const float* next, AReg<NB>& ar, Shared<NB>& sh,
-                                                  int w, int c, int h, int lane, bool want_E, float& es, Tile<NB>& g) {
-  constexpr int P = 128 * NB;
-  // sh.cb was last read in front of the previous block's GEMM 1, and every wave has passed a barrier since
-  for (int i = threadIdx.x; i < P; i += 256) sh.cb[i] = mdl.cb[i];
-  if constexpr (NB == 1) areg_load<1>(mdl, w, c, h, ar);     // both matrices of the block, register resident
-  __syncthreads();   // cb and (first block) x visible; the previous block's GEMM 2 has read its phi(u) image
-  Tile<NB> u;
-  rowvec_load<NB>(sh.cb, w, h, u);
-  if constexpr (NB == 1) gemm_any<1, false>(mdl, ar, sh.pub[0], w, c, h, lane, u);
-  else gemm_dim<NB>(mdl.W1, mdl.W2T, sh.pub[0], w, c, h, lane, ar.a0, u);
-  if (want_E) es += xp.template energy_sum<NB>(u, w, h);
-  xp.template phi<NB>(u, w, h);
-  publish<NB>(sh.pub[1][w], lane, u);
-  __syncthreads();
-  if constexpr (NB == 1) gemm_any<1, true>(mdl, ar, sh.pub[1], w, c, h, lane, g);
-  else gemm_dim<NB>(mdl.W2T, next, sh.pub[1], w, c, h, lane, ar.a0, g);
-}
-
 // E(X), dE/dX(X) of rows a.X ([32 ntiles][P] float32, rows beyond the batch zero), as lin_tall_eval_tiles: x published once
 // per tile, then the grouped blocks and the plain blocks in storage order, dE/dx accumulating in the same registers.  One
 // order of additions whatever the grid: the result depends on the model and the row alone.
@@ -157,7 +135,7 @@ __device__ __forceinline__ void lin_grouped_eval_tiles(const PotEvalArgs& a, con
       const PotModel mdl{gm.W1b + blk * MB, gm.W2Tb + blk * MB, gm.cb + (size_t)blk * P, nullptr, P, P};
       const LinearGroupedExperts<F, C> xp{lin, blk, gm.G};
       const int nxt = blk + 1 < nblk ? blk + 1 : 0;          // (the last block hands on block 0's W1: the next tile's)
-      lin_grouped_block<NB>(mdl, xp, gm.W1b + nxt * MB, ar, sh, w, c, h, lane, a.E != nullptr, es, g);
+      lin_block<NB>(mdl, xp, gm.W1b + nxt * MB, ar, sh, w, c, h, lane, a.E != nullptr, es, g);
     }
 #pragma unroll 1
     for (int pb = 0; pb < gm.nbp; ++pb) {
@@ -167,7 +145,7 @@ __device__ __forceinline__ void lin_grouped_eval_tiles(const PotEvalArgs& a, con
       const PotModel mdl{gm.W1b + blk * MB, gm.W2Tb + blk * MB, gm.cb + (size_t)blk * P, nullptr, P, gm.D > kexp ? gm.D : kexp};
       const LinearTallExperts<F> xp{plin, GC + pb * P};
       const int nxt = blk + 1 < nblk ? blk + 1 : 0;
-      lin_grouped_block<NB>(mdl, xp, gm.W1b + nxt * MB, ar, sh, w, c, h, lane, a.E != nullptr, es, g);
+      lin_block<NB>(mdl, xp, gm.W1b + nxt * MB, ar, sh, w, c, h, lane, a.E != nullptr, es, g);
     }
     if (a.E) {
       const float part = half_sum(es);

@@ -49,6 +49,32 @@ struct LinearTallExperts {
   }
 };
 
+// One block step with the block's experts XP (LinearTallExperts here, LinearGroupedExperts in dense_lin_grouped.hpp):
+// cb -> LDS, u = cb + W1^T x (GEMM 1), the lane's energy terms into a running float, phi(u) published, g += W2T^T phi(u)
+// (GEMM 2, g never zeroed between blocks).  `next` is the matrix whose chunk 0 leaves in ar (NB > 1).  The grouped kernel's
+// two loops call it.  lin_tall_eval_tiles below holds the same step as text of its own: as a callee the step compiles to
+// other code there (tools/isa_equal.py --rtc: up to 28 registers fewer at NB = 1, but 4 more and a few more instructions
+// for some expressions at NB = 2 and 4), and a listing that is higher anywhere is not taken without need.
+template <int NB, class XP>
+__device__ __forceinline__ void lin_block(const PotModel& mdl, const XP& xp, const float* next, AReg<NB>& ar, Shared<NB>& sh,
+                                          int w, int c, int h, int lane, bool want_E, float& es, Tile<NB>& g) {
+  constexpr int P = 128 * NB;
+  // sh.cb was last read in front of the previous block's GEMM 1, and every wave has passed a barrier since
+  for (int i = threadIdx.x; i < P; i += 256) sh.cb[i] = mdl.cb[i];
+  if constexpr (NB == 1) areg_load<1>(mdl, w, c, h, ar);     // both matrices of the block, register resident
+  __syncthreads();   // cb and (first block) x visible; the previous block's GEMM 2 has read its phi(u) image
+  Tile<NB> u;
+  rowvec_load<NB>(sh.cb, w, h, u);
+  if constexpr (NB == 1) gemm_any<1, false>(mdl, ar, sh.pub[0], w, c, h, lane, u);
+  else gemm_dim<NB>(mdl.W1, mdl.W2T, sh.pub[0], w, c, h, lane, ar.a0, u);
+  if (want_E) es += xp.template energy_sum<NB>(u, w, h);
+  xp.template phi<NB>(u, w, h);
+  publish<NB>(sh.pub[1][w], lane, u);
+  __syncthreads();
+  if constexpr (NB == 1) gemm_any<1, true>(mdl, ar, sh.pub[1], w, c, h, lane, g);
+  else gemm_dim<NB>(mdl.W2T, next, sh.pub[1], w, c, h, lane, ar.a0, g);
+}
+
 // The evaluation E(X), dE/dX(X) of rows a.X ([32 ntiles][P] float32, rows beyond the batch zero).  Per tile: x is published
 // once; per block: cb -> LDS, u = cb + W1[blk]^T x (GEMM 1), the lane's energy terms into a running float, phi(u) published,
 // g += W2T[blk]^T phi(u) (GEMM 2, never zeroed between blocks).  The GEMMs alternate W1[0], W2T[0], W1[1], ...: gemm_dim

@@ -20,8 +20,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -104,35 +102,12 @@ std::string functionals_source(const std::vector<std::string>& stats, const std:
   return s;
 }
 
-struct Compiled {
-  std::vector<char> code;
-  std::string lowered;
-};
-
 // one compile per (source, instantiation) and process: a driver call creates a functionals per run
-int functionals_compile(const std::string& src, int dt, bool wide, const std::string& include_dir, const Compiled** out,
+int functionals_compile(const std::string& src, int dt, bool wide, const std::string& include_dir, const RtcCode** out,
                         std::string* err) {
-  static std::mutex mu;
-  static std::map<std::string, Compiled> cache;
   const std::string name = "mjhmc::functionals_eval_kernel<" + std::to_string(dt) + ", mjhmc::UserFunctionals, " +
                            (wide ? "true" : "false") + ">";
-  std::lock_guard<std::mutex> lock(mu);
-  const std::string key = name + "\n" + include_dir + "\n" + src;
-  auto it = cache.find(key);
-  if (it == cache.end()) {
-    Compiled c;
-    std::vector<std::string> lowered;
-    const int rc = rtc_compile(src, "mjhmc_functionals.hip", include_dir, {name}, &c.code, &lowered, err);
-    if (rc) {
-      const std::string was = "the energy expressions";
-      if (err->compare(0, was.size(), was) == 0) *err = "the functional expressions" + err->substr(was.size());
-      return rc;
-    }
-    c.lowered = lowered[0];
-    it = cache.emplace(key, std::move(c)).first;
-  }
-  *out = &it->second;
-  return 0;
+  return rtc_compile_cached(src, "mjhmc_functionals.hip", {name}, include_dir, "the functional expressions do not compile", out, err);
 }
 
 int check_counts(int J, int K) {
@@ -308,7 +283,7 @@ int mjhmc_functionals_check(int ndims, const char* stats, const char* values, co
   int chunks, cw, log_cw;
   bool wide;
   row_geometry(sh.pitch, 2, &chunks, &cw, &log_cw, &wide);
-  const Compiled* c = nullptr;
+  const RtcCode* c = nullptr;
   std::string err;
   const int rc = functionals_compile(functionals_source(st, va), MJHMC_F64, wide, include_dir, &c, &err);
   return rc ? mjhmc_fail(rc, err) : 0;
@@ -332,7 +307,7 @@ int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* va
   int chunks, cw, log_cw;
   bool wide;
   row_geometry(s->sh.pitch, vec, &chunks, &cw, &log_cw, &wide);
-  const Compiled* c = nullptr;
+  const RtcCode* c = nullptr;
   std::string err;
   const int rc = functionals_compile(functionals_source(st, va), s->dtype, wide, include_dir, &c, &err);
   if (rc) return mjhmc_fail(rc, err);
@@ -347,7 +322,7 @@ int mjhmc_functionals_create(mjhmc_sampler* s, const char* stats, const char* va
   f->log_cw = log_cw;
   f->wide = wide;
   hipError_t e = hipModuleLoadData(&f->module, c->code.data());
-  if (e == hipSuccess) e = hipModuleGetFunction(&f->fn, f->module, c->lowered.c_str());
+  if (e == hipSuccess) e = hipModuleGetFunction(&f->fn, f->module, c->lowered[0].c_str());
   if (e == hipSuccess) e = hipMalloc((void**)&f->dparams, (nparams ? nparams : 1) * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&f->bad, sizeof(int));
   if (e == hipSuccess && nparams)
@@ -429,11 +404,10 @@ int mjhmc_functionals_create_linear(mjhmc_sampler* s, int n_values, const double
   TRY(pick_shape(K, MJHMC_F64, &shK));
   if (shK.pitch != (K + 1) / 2 * 2) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "unexpected row pitch of the derived ring");
   HIPCHK(hipSetDevice(s->ctx->device));
-  const void* image = nullptr;
-  const char* lowered = nullptr;
+  const RtcCode* link = nullptr;   // (none: the identity, in the library)
   if (link_expr) {
     std::string err;
-    const int rc = mjhmc::projections_link_compile(link_expr, s->dtype, K, include_dir, &image, &lowered, &err);
+    const int rc = mjhmc::projections_link_compile(link_expr, s->dtype, K, include_dir, &link, &err);
     if (rc) return mjhmc_fail(rc, err);
   }
   // A transposed and zero-padded to whole tiles and d chunks (projections.hpp: ProjArgs), b padded with zeros
@@ -453,9 +427,9 @@ int mjhmc_functionals_create_linear(mjhmc_sampler* s, int n_values, const double
   row_geometry(s->sh.pitch, vec, &f->chunks, &f->cw, &f->log_cw, &f->wide);
   const int no_bad = mjhmc::kProjNoBad;
   hipError_t e = hipSuccess;
-  if (image) {
-    e = hipModuleLoadData(&f->module, image);
-    if (e == hipSuccess) e = hipModuleGetFunction(&f->fn, f->module, lowered);
+  if (link) {
+    e = hipModuleLoadData(&f->module, link->code.data());
+    if (e == hipSuccess) e = hipModuleGetFunction(&f->fn, f->module, link->lowered[0].c_str());
   }
   if (e == hipSuccess) e = hipMalloc((void**)&f->lin_At, At.size() * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&f->lin_b, bp.size() * sizeof(double));

@@ -138,9 +138,8 @@ int mjhmc_influence_check(int ndims, int64_t nexperts, const char* value, const 
                                                  std::to_string(ndims) + " x " + std::to_string(nexperts) + ")");
   std::string v, err;
   TRY(checked_value(value, &v));
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
-  const int rc = linear_values_compile(v, linear_pointwise_dim(ndims, nexperts), include_dir, &err, &code, &lowered);
+  const RtcCode* code = nullptr;
+  const int rc = linear_values_compile(v, linear_pointwise_dim(ndims, nexperts), include_dir, &err, &code);
   return rc ? mjhmc_fail(rc, err) : 0;
 }
 
@@ -170,9 +169,8 @@ int mjhmc_influence_create(mjhmc_sampler* s, const char* value, int64_t j0, int6
   if (s->sh.pitch != P) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows do not have the model's padded pitch");
   HIPCHK(hipSetDevice(s->ctx->device));
   std::string err;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
-  const int rc = linear_values_compile(v, P, include_dir, &err, &code, &lowered);
+  const RtcCode* code = nullptr;
+  const int rc = linear_values_compile(v, P, include_dir, &err, &code);
   if (rc) return mjhmc_fail(rc, err);
   const RingSource src = ring_source(s, nullptr);
   mjhmc_influence* h = new mjhmc_influence("influence", "influence handle", s, nullptr, src);
@@ -203,8 +201,8 @@ int mjhmc_influence_create(mjhmc_sampler* s, const char* value, int64_t j0, int6
   const bool f64 = s->dtype == MJHMC_F64;
   h->scratch_bytes = panel_elems * sizeof(float) * (f64 ? 2 : 1) + (f64 ? panel_elems * sizeof(double) : 0) +
                      (xpart_elems + h->xplan.moment_partial_elems + h->tplan.moment_partial_elems) * sizeof(double);
-  hipError_t he = hipModuleLoadData(&h->module, code->data());
-  if (he == hipSuccess) he = hipModuleGetFunction(&h->fn, h->module, (*lowered)[0].c_str());
+  hipError_t he = hipModuleLoadData(&h->module, code->code.data());
+  if (he == hipSuccess) he = hipModuleGetFunction(&h->fn, h->module, code->lowered[0].c_str());
   if (he == hipSuccess && f64) he = hipMalloc((void**)&h->X32, panel_elems * sizeof(float));
   if (he == hipSuccess && f64) he = hipMalloc((void**)&h->T64, panel_elems * sizeof(double));
   if (he == hipSuccess) he = hipMalloc((void**)&h->T, panel_elems * sizeof(float));

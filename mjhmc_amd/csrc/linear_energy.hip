@@ -15,13 +15,15 @@
 // blocks (dense_lin_tall.hpp) as the force of the multi-pass path.  Grouped models (a log-sum-exp
 // over groups of experts: softmax regression) are the third part: the tall form with a permuted layout and a kernel of its
 // own (dense_lin_grouped.hpp).
+// What the forms share stands once: every compile is "source, name expressions, rtc_compile_cached" (user_expr.hpp: one
+// cache for the process), every builder loads its module through linear_module_load and puts its model on the device through
+// linear_model_upload (slots in blocks of P and a slot -> expert map: one block and the identity for the square form, the
+// identity for the tall one, linear_grouped_slot_expert for the grouped one).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -30,14 +32,6 @@
 #include "linear_energy.hpp"
 
 namespace {
-
-struct Compiled {
-  std::vector<char> code;
-  std::vector<std::string> lowered;
-};
-
-std::mutex g_cache_mu;
-std::map<std::string, std::unique_ptr<Compiled>> g_cache;   // generated source + NB -> code object (never evicted)
 
 // E = sum_j f(u_j, j), dE/dx = W^T f'(u): the caller's expressions as a functor (shared by both generated sources)
 std::string user_functor_source(const std::string& energy_expr, const std::string& grad_expr) {
@@ -139,8 +133,6 @@ std::string linear_values_source(const std::string& value) {
   return s;
 }
 
-int tall_pad(int ndims) { return ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim); }
-
 int resident_cus() {
   int dev = 0, cus = 0;
   (void)hipGetDevice(&dev);
@@ -165,69 +157,90 @@ int linear_check_args(int ndims, int nexperts, const char* energy_expr, const ch
   return 0;
 }
 
-int linear_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
-                   std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered) {
-  const int NB = dim / 128;
-  const std::string src = linear_source(energy_expr, grad_expr);
-  const std::string key = src + "\n// NB = " + std::to_string(NB) + ", -I" + include_dir;
-  std::lock_guard<std::mutex> lk(g_cache_mu);   // (one compile at a time: a second thread asking for the same code waits for it)
-  auto it = g_cache.find(key);
-  if (it == g_cache.end()) {
-    std::unique_ptr<Compiled> c(new Compiled());
-    const int rc = rtc_compile(src, "mjhmc_linear_energy.hip", include_dir, linear_kernel_names(NB), &c->code, &c->lowered, err);
-    if (rc) return rc;
-    it = g_cache.emplace(key, std::move(c)).first;
-  }
-  *code = &it->second->code;
-  *lowered = &it->second->lowered;
+int tall_pad(int ndims) { return ndims <= 128 ? 128 : (ndims <= 256 ? 256 : kPotDim); }
+
+namespace {
+
+const char* const kEnergyWords = "the energy expressions do not compile";
+
+// the compiled code as e->lin's module, and its kernels by lowered name: fns in the order of the name expressions
+int linear_module_load(LinearEnergy* l, const RtcCode& c, const std::vector<hipFunction_t*>& fns) {
+  HIPCHK(hipModuleLoadData(&l->module, c.code.data()));
+  for (size_t k = 0; k < fns.size(); ++k) HIPCHK(hipModuleGetFunction(fns[k], l->module, c.lowered[k].c_str()));
   return 0;
+}
+
+// The model on the device, float32, in the blocked layout: S slots in blocks of P (the state rows' pitch), slot
+// blk P + local holding the caller's expert j = expert(slot), -1 for padding (zero):
+//     W1b[blk][d][local] = W2Tb[blk][local][d] = W[j][d]     (u = W1b[blk]^T x + cb[blk]; dE/dx += W2Tb[blk]^T phi(u))
+// cb = b and the per-expert rows q[m] (rows of S floats) in slot order, the shared parameters behind them.  One block and
+// the identity map are a <= 512 model in ProductOfT's own layout.  `form` words the allocation failure ("a tall").
+int linear_model_upload(mjhmc_energy* e, int P, size_t S, int K, const double* W, const double* b, const double* params,
+                        size_t nparams, const double* expert_params, int n_expert_rows,
+                        const std::function<int64_t(int64_t)>& expert, const char* form) {
+  const int D = e->ep.ndims;
+  LinearEnergy* l = e->lin;
+  e->pot_dim = P;
+  const size_t M = (size_t)P * P, mat_bytes = S * P * sizeof(float), nrows = (size_t)4 * S + (nparams ? nparams : 1);
+  std::vector<float> w1(S * P, 0.f), w2t(S * P, 0.f), cb(S, 0.f), rows(nrows, 0.f);
+  for (size_t slot = 0; slot < S; ++slot) {
+    const int64_t j = expert((int64_t)slot);
+    if (j < 0) continue;
+    const size_t blk = slot / P, jl = slot % P;
+    cb[slot] = (float)b[j];
+    for (int d = 0; d < D; ++d) {
+      const float w = (float)W[(size_t)j * D + d];
+      w1[blk * M + (size_t)d * P + jl] = w;
+      w2t[blk * M + jl * P + d] = w;
+    }
+    for (int m = 0; m < n_expert_rows; ++m) rows[(size_t)m * S + slot] = (float)expert_params[(size_t)m * K + j];
+  }
+  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * S + k] = (float)params[k];
+  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
+  const size_t bytes[3] = {mat_bytes, mat_bytes, S * sizeof(float)};
+  for (int i = 0; i < 3; ++i) {
+    if (hipMalloc((void**)&e->pot[i], bytes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      e->pot[i] = nullptr;
+      return mjhmc_fail(MJHMC_ERR_HIP, std::string(form) + " LINEAR_EXPR model of " + std::to_string(D) + " dims x " + std::to_string(K) +
+                                       " experts needs " + std::to_string(2 * mat_bytes) + " bytes of device memory for its matrices (" +
+                                       std::to_string(S / P) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
+                                       ", twice): the allocation failed");
+    }
+    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
+  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
+  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * S, K, (int)S};
+  return 0;
+}
+
+}  // namespace
+
+int linear_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
+                   std::string* err, const RtcCode** out) {
+  return rtc_compile_cached(linear_source(energy_expr, grad_expr), "mjhmc_linear_energy.hip", linear_kernel_names(dim / 128),
+                            include_dir, kEnergyWords, out, err);
 }
 
 int linear_energy_build(mjhmc_energy* e, int nexperts, const double* W, const double* b, const char* energy_expr,
                         const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
                         int n_expert_rows, const char* include_dir) {
   const int D = e->ep.ndims, K = nexperts, DIM = linear_dim(D, K);
-  LinearEnergy* l = new LinearEnergy();
-  e->lin = l;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
+  LinearEnergy* l = e->lin = new LinearEnergy();
+  const RtcCode* c = nullptr;
   std::string err;
-  const int rc = linear_compile(energy_expr, grad_expr, DIM, include_dir, &err, &code, &lowered);
+  const int rc = linear_compile(energy_expr, grad_expr, DIM, include_dir, &err, &c);
   if (rc) return mjhmc_fail(rc, err);
-  HIPCHK(hipModuleLoadData(&l->module, code->data()));
-  for (int k = 0; k < 12; ++k) {
-    hipFunction_t* f = k < 6 ? &l->gen.jump32[k / 2][k % 2] : &l->gen.jump64[(k - 6) / 2][k % 2];
-    HIPCHK(hipModuleGetFunction(f, l->module, (*lowered)[(size_t)k].c_str()));
-  }
-  HIPCHK(hipModuleGetFunction(&l->gen.eval, l->module, (*lowered)[12].c_str()));
-  HIPCHK(hipModuleGetFunction(&l->gen.leap, l->module, (*lowered)[13].c_str()));
-
-  // the model in ProductOfT's layout, float32 (W1 = W^T: u = W1^T x + cb; W2T = W: dE/dx = W2T^T phi(u))
-  e->pot_dim = DIM;
+  std::vector<hipFunction_t*> fns;   // the order of linear_kernel_names
+  for (int k = 0; k < 12; ++k) fns.push_back(k < 6 ? &l->gen.jump32[k / 2][k % 2] : &l->gen.jump64[(k - 6) / 2][k % 2]);
+  fns.push_back(&l->gen.eval);
+  fns.push_back(&l->gen.leap);
+  TRY(linear_module_load(l, *c, fns));
   e->pot_rows = D > K ? D : K;
-  const size_t M = (size_t)DIM * DIM, nrows = (size_t)4 * DIM + (nparams ? nparams : 1);
-  std::vector<float> w1(M, 0.f), w2t(M, 0.f), cb(DIM, 0.f), rows(nrows, 0.f);
-  for (int j = 0; j < K; ++j) {
-    cb[j] = (float)b[j];
-    for (int d = 0; d < D; ++d) {
-      const float w = (float)W[(size_t)j * D + d];
-      w1[(size_t)d * DIM + j] = w;
-      w2t[(size_t)j * DIM + d] = w;
-    }
-  }
-  for (int m = 0; m < n_expert_rows; ++m)
-    for (int j = 0; j < K; ++j) rows[(size_t)m * DIM + j] = (float)expert_params[(size_t)m * K + j];
-  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * DIM + k] = (float)params[k];
-  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
-  const size_t bytes[3] = {M * 4, M * 4, (size_t)DIM * 4};
-  for (int i = 0; i < 3; ++i) {
-    HIPCHK(hipMalloc((void**)&e->pot[i], bytes[i]));
-    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
-  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
-  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * DIM, K, DIM};
-  return 0;
+  // ProductOfT's layout (W1 = W^T: u = W1^T x + cb; W2T = W: dE/dx = W2T^T phi(u)): one block of DIM slots
+  return linear_model_upload(e, DIM, (size_t)DIM, K, W, b, params, nparams, expert_params, n_expert_rows,
+                             [K](int64_t slot) { return slot < K ? slot : -1; }, "a");
 }
 
 void linear_energy_free(mjhmc_energy* e) {
@@ -257,75 +270,26 @@ int linear_tall_check_args(int ndims, int64_t nexperts, const char* energy_expr,
 }
 
 int linear_tall_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
-                        std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered) {
-  const int NB = dim / 128;
-  const std::string src = linear_tall_source(energy_expr, grad_expr);
-  const std::string key = src + "\n// tall, NB = " + std::to_string(NB) + ", -I" + include_dir;
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  auto it = g_cache.find(key);
-  if (it == g_cache.end()) {
-    std::unique_ptr<Compiled> c(new Compiled());
-    const int rc = rtc_compile(src, "mjhmc_linear_tall.hip", include_dir, {"mjhmc::lin_tall_eval_kernel<" + std::to_string(NB) + ">"},
-                               &c->code, &c->lowered, err);
-    if (rc) return rc;
-    it = g_cache.emplace(key, std::move(c)).first;
-  }
-  *code = &it->second->code;
-  *lowered = &it->second->lowered;
-  return 0;
+                        std::string* err, const RtcCode** out) {
+  return rtc_compile_cached(linear_tall_source(energy_expr, grad_expr), "mjhmc_linear_tall.hip",
+                            {"mjhmc::lin_tall_eval_kernel<" + std::to_string(dim / 128) + ">"}, include_dir, kEnergyWords, out, err);
 }
 
 int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, const char* energy_expr,
                              const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
                              int n_expert_rows, const char* include_dir) {
   const int D = e->ep.ndims, K = (int)nexperts, P = tall_pad(D), nblk = (K + P - 1) / P;
-  const size_t KP = (size_t)nblk * P;
-  LinearEnergy* l = new LinearEnergy();
-  e->lin = l;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
+  LinearEnergy* l = e->lin = new LinearEnergy();
+  const RtcCode* c = nullptr;
   std::string err;
-  const int rc = linear_tall_compile(energy_expr, grad_expr, P, include_dir, &err, &code, &lowered);
+  const int rc = linear_tall_compile(energy_expr, grad_expr, P, include_dir, &err, &c);
   if (rc) return mjhmc_fail(rc, err);
-  HIPCHK(hipModuleLoadData(&l->module, code->data()));
-  HIPCHK(hipModuleGetFunction(&l->tall, l->module, (*lowered)[0].c_str()));
+  TRY(linear_module_load(l, *c, {&l->tall}));
   l->tall_nblk = nblk;
   l->tall_K = K;
-  e->pot_dim = P;      // the state rows' pitch: the pad of D
   e->pot_rows = D;
-
-  // W1b[blk][d][j] = W2Tb[blk][j][d] = W[blk P + j][d], cb = b, zero padded; float32
-  const size_t M = (size_t)P * P, mat_bytes = KP * P * sizeof(float), nrows = (size_t)4 * KP + (nparams ? nparams : 1);
-  std::vector<float> w1(KP * P, 0.f), w2t(KP * P, 0.f), cb(KP, 0.f), rows(nrows, 0.f);
-  for (int j = 0; j < K; ++j) {
-    const size_t blk = (size_t)j / P, jl = (size_t)j % P;
-    cb[j] = (float)b[j];
-    for (int d = 0; d < D; ++d) {
-      const float w = (float)W[(size_t)j * D + d];
-      w1[blk * M + (size_t)d * P + jl] = w;
-      w2t[blk * M + jl * P + d] = w;
-    }
-  }
-  for (int m = 0; m < n_expert_rows; ++m)
-    for (int j = 0; j < K; ++j) rows[(size_t)m * KP + j] = (float)expert_params[(size_t)m * K + j];
-  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * KP + k] = (float)params[k];
-  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
-  const size_t bytes[3] = {mat_bytes, mat_bytes, KP * sizeof(float)};
-  for (int i = 0; i < 3; ++i) {
-    if (hipMalloc((void**)&e->pot[i], bytes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      e->pot[i] = nullptr;
-      return mjhmc_fail(MJHMC_ERR_HIP, "a tall LINEAR_EXPR model of " + std::to_string(D) + " dims x " + std::to_string(K) +
-                                       " experts needs " + std::to_string(2 * mat_bytes) + " bytes of device memory for its matrices (" +
-                                       std::to_string(nblk) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
-                                       ", twice): the allocation failed");
-    }
-    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
-  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
-  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * KP, K, (int)KP};
-  return 0;
+  return linear_model_upload(e, P, (size_t)nblk * P, K, W, b, params, nparams, expert_params, n_expert_rows,
+                             [K](int64_t slot) { return slot < K ? slot : -1; }, "a tall");
 }
 
 void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st) {
@@ -343,14 +307,10 @@ void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E
   a.key = RngKey{0u, 0u, 0u, 0u};
   const PotLinear lin = e->lin->gen.lin;
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
-  if (e->lin->grouped()) {   // lin_grouped_eval_kernel (dense_lin_grouped.hpp): the same arguments around its own model
-    const LinGroupedModel gm{e->pot[0], e->pot[1], e->pot[2], e->lin->grp_nbg, e->lin->grp_nbp, e->ep.ndims, e->lin->tall_K, e->lin->grp_G};
-    void* params[] = {(void*)&a, (void*)&gm, (void*)&lin};
-    (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
-    return;
-  }
+  // lin_tall_eval_kernel or lin_grouped_eval_kernel (dense_lin_grouped.hpp): the same arguments around the kernel's own model
   const LinTallModel tm{e->pot[0], e->pot[1], e->pot[2], e->lin->tall_nblk, e->ep.ndims, e->lin->tall_K};
-  void* params[] = {(void*)&a, (void*)&tm, (void*)&lin};
+  const LinGroupedModel gm{e->pot[0], e->pot[1], e->pot[2], e->lin->grp_nbg, e->lin->grp_nbp, e->ep.ndims, e->lin->tall_K, e->lin->grp_G};
+  void* params[] = {(void*)&a, e->lin->grouped() ? (void*)&gm : (void*)&tm, (void*)&lin};
   (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
 }
 
@@ -433,23 +393,9 @@ int linear_grouped_check_args(int ndims, int64_t nexperts, int group_size, int64
 }
 
 int linear_grouped_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, int group_size,
-                           const std::string& include_dir, std::string* err, const std::vector<char>** code,
-                           const std::vector<std::string>** lowered) {
-  const int NB = dim / 128;
-  const std::string src = linear_grouped_source(energy_expr, grad_expr, group_size);
-  const std::string key = src + "\n// grouped, C = " + std::to_string(group_size) + ", NB = " + std::to_string(NB) + ", -I" + include_dir;
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  auto it = g_cache.find(key);
-  if (it == g_cache.end()) {
-    std::unique_ptr<Compiled> c(new Compiled());
-    const int rc = rtc_compile(src, "mjhmc_linear_grouped.hip", include_dir, {"mjhmc::lin_grouped_eval_kernel<" + std::to_string(NB) + ">"},
-                               &c->code, &c->lowered, err);
-    if (rc) return rc;
-    it = g_cache.emplace(key, std::move(c)).first;
-  }
-  *code = &it->second->code;
-  *lowered = &it->second->lowered;
-  return 0;
+                           const std::string& include_dir, std::string* err, const RtcCode** out) {
+  return rtc_compile_cached(linear_grouped_source(energy_expr, grad_expr, group_size), "mjhmc_linear_grouped.hip",
+                            {"mjhmc::lin_grouped_eval_kernel<" + std::to_string(dim / 128) + ">"}, include_dir, kEnergyWords, out, err);
 }
 
 int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, int group_size,
@@ -457,59 +403,22 @@ int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double*
                                 size_t nparams, const double* expert_params, int n_expert_rows, const char* include_dir) {
   const int D = e->ep.ndims, K = (int)nexperts;
   const LinGroupedLayout L = linear_grouped_layout(D, nexperts, group_size, n_groups);
-  const int P = L.P;
-  const size_t S = (size_t)L.nslots;
-  LinearEnergy* l = new LinearEnergy();
-  e->lin = l;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
+  LinearEnergy* l = e->lin = new LinearEnergy();
+  const RtcCode* c = nullptr;
   std::string err;
-  const int rc = linear_grouped_compile(energy_expr, grad_expr, P, group_size, include_dir, &err, &code, &lowered);
+  const int rc = linear_grouped_compile(energy_expr, grad_expr, L.P, group_size, include_dir, &err, &c);
   if (rc) return mjhmc_fail(rc, err);
-  HIPCHK(hipModuleLoadData(&l->module, code->data()));
-  HIPCHK(hipModuleGetFunction(&l->tall, l->module, (*lowered)[0].c_str()));
+  TRY(linear_module_load(l, *c, {&l->tall}));
   l->tall_nblk = L.nbg + L.nbp;
   l->tall_K = K;
   l->grp_C = group_size;
   l->grp_G = (int)n_groups;
   l->grp_nbg = L.nbg;
   l->grp_nbp = L.nbp;
-  e->pot_dim = P;      // the state rows' pitch: the pad of D
   e->pot_rows = D;
-
-  // W1b[blk][d][local] = W2Tb[blk][local][d] = W[expert of slot blk P + local][d], cb likewise, zero in the padding; float32
-  const size_t M = (size_t)P * P, mat_bytes = S * P * sizeof(float), nrows = (size_t)4 * S + (nparams ? nparams : 1);
-  std::vector<float> w1(S * P, 0.f), w2t(S * P, 0.f), cb(S, 0.f), rows(nrows, 0.f);
-  for (size_t slot = 0; slot < S; ++slot) {
-    const int64_t j = linear_grouped_slot_expert(L, nexperts, group_size, n_groups, (int64_t)slot);
-    if (j < 0) continue;
-    const size_t blk = slot / P, jl = slot % P;
-    cb[slot] = (float)b[j];
-    for (int d = 0; d < D; ++d) {
-      const float w = (float)W[(size_t)j * D + d];
-      w1[blk * M + (size_t)d * P + jl] = w;
-      w2t[blk * M + jl * P + d] = w;
-    }
-    for (int m = 0; m < n_expert_rows; ++m) rows[(size_t)m * S + slot] = (float)expert_params[(size_t)m * K + j];
-  }
-  for (size_t k = 0; k < nparams; ++k) rows[(size_t)4 * S + k] = (float)params[k];
-  const void* src[3] = {w1.data(), w2t.data(), cb.data()};
-  const size_t bytes[3] = {mat_bytes, mat_bytes, S * sizeof(float)};
-  for (int i = 0; i < 3; ++i) {
-    if (hipMalloc((void**)&e->pot[i], bytes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      e->pot[i] = nullptr;
-      return mjhmc_fail(MJHMC_ERR_HIP, "a grouped LINEAR_EXPR model of " + std::to_string(D) + " dims x " + std::to_string(K) +
-                                       " experts needs " + std::to_string(2 * mat_bytes) + " bytes of device memory for its matrices (" +
-                                       std::to_string(L.nbg + L.nbp) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
-                                       ", twice): the allocation failed");
-    }
-    HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMalloc((void**)&l->rows, nrows * sizeof(float)));
-  HIPCHK(hipMemcpy(l->rows, rows.data(), nrows * sizeof(float), hipMemcpyHostToDevice));
-  l->gen.lin = PotLinear{l->rows, l->rows + (size_t)4 * S, K, (int)S};
-  return 0;
+  return linear_model_upload(e, L.P, (size_t)L.nslots, K, W, b, params, nparams, expert_params, n_expert_rows,
+                             [&](int64_t slot) { return linear_grouped_slot_expert(L, nexperts, group_size, n_groups, slot); },
+                             "a grouped");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -520,52 +429,18 @@ int linear_pointwise_dim(int ndims, int64_t nexperts) {
 }
 
 int linear_pointwise_compile(const std::vector<std::string>& values, int dim, const std::string& include_dir,
-                             std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered) {
-  const int NB = dim / 128;
-  const std::string src = linear_pointwise_source(values);
-  const std::string key = src + "\n// pointwise, NB = " + std::to_string(NB) + ", -I" + include_dir;
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  auto it = g_cache.find(key);
-  if (it == g_cache.end()) {
-    std::unique_ptr<Compiled> c(new Compiled());
-    const int rc = rtc_compile(src, "mjhmc_linear_pointwise.hip", include_dir, {"mjhmc::lin_pointwise_kernel<" + std::to_string(NB) + ">"},
-                               &c->code, &c->lowered, err);
-    if (rc) {
-      const std::string energy_words = "the energy expressions do not compile:";
-      if (err->compare(0, energy_words.size(), energy_words) == 0)
-        *err = "the value expressions do not compile:" + err->substr(energy_words.size());
-      return rc;
-    }
-    it = g_cache.emplace(key, std::move(c)).first;
-  }
-  *code = &it->second->code;
-  *lowered = &it->second->lowered;
-  return 0;
+                             std::string* err, const RtcCode** out) {
+  return rtc_compile_cached(linear_pointwise_source(values), "mjhmc_linear_pointwise.hip",
+                            {"mjhmc::lin_pointwise_kernel<" + std::to_string(dim / 128) + ">"}, include_dir,
+                            "the value expressions do not compile", out, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The values of one block of experts, stored: the first half of the influence pass (dense_lin_values.hpp, influence.hip)
 // ---------------------------------------------------------------------------------------------------------------------
 int linear_values_compile(const std::string& value, int dim, const std::string& include_dir, std::string* err,
-                          const std::vector<char>** code, const std::vector<std::string>** lowered) {
-  const int NB = dim / 128;
-  const std::string src = linear_values_source(value);
-  const std::string key = src + "\n// values, NB = " + std::to_string(NB) + ", -I" + include_dir;
-  std::lock_guard<std::mutex> lk(g_cache_mu);
-  auto it = g_cache.find(key);
-  if (it == g_cache.end()) {
-    std::unique_ptr<Compiled> c(new Compiled());
-    const int rc = rtc_compile(src, "mjhmc_linear_values.hip", include_dir, {"mjhmc::lin_values_kernel<" + std::to_string(NB) + ">"},
-                               &c->code, &c->lowered, err);
-    if (rc) {
-      const std::string energy_words = "the energy expressions do not compile:";
-      if (err->compare(0, energy_words.size(), energy_words) == 0)
-        *err = "the value expression does not compile:" + err->substr(energy_words.size());
-      return rc;
-    }
-    it = g_cache.emplace(key, std::move(c)).first;
-  }
-  *code = &it->second->code;
-  *lowered = &it->second->lowered;
-  return 0;
+                          const RtcCode** out) {
+  return rtc_compile_cached(linear_values_source(value), "mjhmc_linear_values.hip",
+                            {"mjhmc::lin_values_kernel<" + std::to_string(dim / 128) + ">"}, include_dir,
+                            "the value expression does not compile", out, err);
 }

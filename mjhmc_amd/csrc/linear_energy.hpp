@@ -9,6 +9,7 @@
 #include "dense_pot.hpp"
 
 struct mjhmc_energy;
+struct RtcCode;   // user_expr.hpp: a cached hipRTC compile, {code, lowered names}
 
 struct LinearEnergy {
   hipModule_t module = nullptr;
@@ -30,19 +31,20 @@ constexpr int64_t kLinTallMaxExperts = (int64_t)1 << 20;
 int linear_dim(int ndims, int nexperts);
 // argument checks shared by creation and the device-free check (records the message, returns the error code)
 int linear_check_args(int ndims, int nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
-// the hipRTC compile of the 14 kernels for one padded dimension; code objects are cached per process by source
+// the hipRTC compile of the 14 kernels for one padded dimension (every compile here: rtc_compile_cached, user_expr.hpp)
 int linear_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
-                   std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered);
+                   std::string* err, const RtcCode** out);
 int linear_energy_build(mjhmc_energy* e, int nexperts, const double* W, const double* b, const char* energy_expr,
                         const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
                         int n_expert_rows, const char* include_dir);
 void linear_energy_free(mjhmc_energy* e);
 
 // Tall models: 1 <= ndims <= 512, 1 <= nexperts <= 2^20 (kLinTallMaxExperts), experts in blocks of the pad of ndims
+int tall_pad(int ndims);   // 128, 256 or 512
 int linear_tall_check_args(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
 // the hipRTC compile of lin_tall_eval_kernel<dim / 128>: its own small source, its own cache key
 int linear_tall_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, const std::string& include_dir,
-                        std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered);
+                        std::string* err, const RtcCode** out);
 int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, const char* energy_expr,
                              const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
                              int n_expert_rows, const char* include_dir);
@@ -63,8 +65,7 @@ int linear_grouped_check_args(int ndims, int64_t nexperts, int group_size, int64
                               const char* grad_expr, const char* include_dir);
 // the hipRTC compile of lin_grouped_eval_kernel<dim / 128> with the group size a constant of the source
 int linear_grouped_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, int group_size,
-                           const std::string& include_dir, std::string* err, const std::vector<char>** code,
-                           const std::vector<std::string>** lowered);
+                           const std::string& include_dir, std::string* err, const RtcCode** out);
 int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, int group_size,
                                 int64_t n_groups, const char* energy_expr, const char* grad_expr, const double* params,
                                 size_t nparams, const double* expert_params, int n_expert_rows, const char* include_dir);
@@ -75,9 +76,9 @@ int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double*
 // a launch argument) -- its own source and cache key: creating an energy compiles none of it
 int linear_pointwise_dim(int ndims, int64_t nexperts);
 int linear_pointwise_compile(const std::vector<std::string>& values, int dim, const std::string& include_dir,
-                             std::string* err, const std::vector<char>** code, const std::vector<std::string>** lowered);
+                             std::string* err, const RtcCode** out);
 
 // The values of one block of experts, stored (dense_lin_values.hpp, influence.hip): the hipRTC compile of
 // lin_values_kernel<dim / 128> around ONE value expression, dim from linear_pointwise_dim -- its own source and cache key
 int linear_values_compile(const std::string& value, int dim, const std::string& include_dir, std::string* err,
-                          const std::vector<char>** code, const std::vector<std::string>** lowered);
+                          const RtcCode** out);

@@ -152,9 +152,8 @@ int mjhmc_pointwise_check(int ndims, int64_t nexperts, const char* values, const
   std::vector<std::string> v;
   TRY(checked_values(values, &v));
   std::string err;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
-  const int rc = linear_pointwise_compile(v, linear_pointwise_dim(ndims, nexperts), include_dir, &err, &code, &lowered);
+  const RtcCode* code = nullptr;
+  const int rc = linear_pointwise_compile(v, linear_pointwise_dim(ndims, nexperts), include_dir, &err, &code);
   return rc ? mjhmc_fail(rc, err) : 0;
 }
 
@@ -183,9 +182,8 @@ int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_ma
   if (s->sh.pitch != P) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows do not have the model's padded pitch");
   HIPCHK(hipSetDevice(s->ctx->device));
   std::string err;
-  const std::vector<char>* code = nullptr;
-  const std::vector<std::string>* lowered = nullptr;
-  const int rc = linear_pointwise_compile(v, P, include_dir, &err, &code, &lowered);
+  const RtcCode* code = nullptr;
+  const int rc = linear_pointwise_compile(v, P, include_dir, &err, &code);
   if (rc) return mjhmc_fail(rc, err);
   const RingSource src = ring_source(s, nullptr);
   mjhmc_pointwise* h = new mjhmc_pointwise("pointwise", "pointwise handle", s, nullptr, src);
@@ -197,8 +195,8 @@ int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_ma
   h->ntiles = (int)((s->N + mjhmc::kP - 1) / mjhmc::kP);
   h->nstrips = (h->ntiles + mjhmc::kPwStripTiles - 1) / mjhmc::kPwStripTiles;
   const size_t KP = (size_t)h->nblk * P;
-  hipError_t he = hipModuleLoadData(&h->module, code->data());
-  if (he == hipSuccess) he = hipModuleGetFunction(&h->fn, h->module, (*lowered)[0].c_str());
+  hipError_t he = hipModuleLoadData(&h->module, code->code.data());
+  if (he == hipSuccess) he = hipModuleGetFunction(&h->fn, h->module, code->lowered[0].c_str());
   if (he == hipSuccess && s->dtype == MJHMC_F64) he = hipMalloc((void**)&h->X32, (size_t)s->Npad * P * sizeof(float));
   if (he == hipSuccess) he = hipMalloc((void**)&h->part, (size_t)h->nstrips * 4 * M * KP * sizeof(double));
   if (he == hipSuccess) he = hipMalloc((void**)&h->partW, (size_t)h->nstrips * sizeof(double));

@@ -4,8 +4,6 @@
 // (mjhmc_functionals_create_linear).
 #include "projections.hpp"
 
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -40,11 +38,6 @@ std::string link_source(const std::string& link) {
   return s;
 }
 
-struct Compiled {
-  std::vector<char> code;
-  std::string lowered;
-};
-
 }  // namespace
 
 bool projections_launch(const ProjArgs& a, int state_dtype, hipStream_t stream) {
@@ -56,10 +49,8 @@ bool projections_launch(const ProjArgs& a, int state_dtype, hipStream_t stream) 
   return true;
 }
 
-int projections_link_compile(const std::string& link, int state_dtype, int K, const std::string& include_dir, const void** image,
-                             const char** lowered, std::string* err) {
-  static std::mutex mu;
-  static std::map<std::string, Compiled> cache;
+int projections_link_compile(const std::string& link, int state_dtype, int K, const std::string& include_dir, const RtcCode** out,
+                             std::string* err) {
   bool blank = true;
   for (char ch : link) blank = blank && (ch == ' ' || ch == '\t' || ch == '\n');
   if (blank || link.find(';') != std::string::npos) {
@@ -68,24 +59,7 @@ int projections_link_compile(const std::string& link, int state_dtype, int K, co
   }
   const std::string name = "mjhmc::projections_kernel<" + std::to_string(state_dtype) + ", " + std::to_string(proj_lane_values(K)) +
                            ", mjhmc::UserLink>";
-  std::lock_guard<std::mutex> lock(mu);
-  const std::string key = name + "\n" + include_dir + "\n" + link;
-  auto it = cache.find(key);
-  if (it == cache.end()) {
-    Compiled c;
-    std::vector<std::string> low;
-    const int rc = rtc_compile(link_source(link), "mjhmc_projections.hip", include_dir, {name}, &c.code, &low, err);
-    if (rc) {
-      const std::string was = "the energy expressions do not compile";
-      if (err->compare(0, was.size(), was) == 0) *err = "the link expression does not compile" + err->substr(was.size());
-      return rc;
-    }
-    c.lowered = low[0];
-    it = cache.emplace(key, std::move(c)).first;
-  }
-  *image = it->second.code.data();
-  *lowered = it->second.lowered.c_str();
-  return 0;
+  return rtc_compile_cached(link_source(link), "mjhmc_projections.hip", {name}, include_dir, "the link expression does not compile", out, err);
 }
 
 }  // namespace mjhmc
@@ -98,10 +72,9 @@ int mjhmc_projections_check(int n_values, const char* link_expr, const char* inc
                                              "], got " + std::to_string(n_values));
   if (!link_expr) return 0;   // the identity is in the library
   if (!include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
-  const void* image = nullptr;
-  const char* lowered = nullptr;
+  const RtcCode* c = nullptr;
   std::string err;
-  const int rc = mjhmc::projections_link_compile(link_expr, MJHMC_F64, n_values, include_dir, &image, &lowered, &err);
+  const int rc = mjhmc::projections_link_compile(link_expr, MJHMC_F64, n_values, include_dir, &c, &err);
   return rc ? mjhmc_fail(rc, err) : 0;
 }
 

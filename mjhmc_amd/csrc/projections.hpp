@@ -36,6 +36,8 @@
 #include <stdint.h>
 
 #include <string>
+
+struct RtcCode;   // user_expr.hpp
 #endif
 
 #include "functionals.hpp"
@@ -207,11 +209,11 @@ __global__ __launch_bounds__(256) void projections_kernel(ProjArgs a, L link) {
 // projections.hip: one launch on `stream` for the n slots of `a`, identity link.  state_dtype: MJHMC_F64 / _F32 / _BF16
 // (0 / 1 / 2); the tile is chosen from a.K (proj_lane_values).  Returns false for a state type there is no kernel for.
 bool projections_launch(const ProjArgs& a, int state_dtype, hipStream_t stream);
-// the image and the lowered kernel name of projections_kernel<state_dtype, proj_lane_values(K), link> for the C expression
-// `link` of u, k and p[m], compiled with hipRTC once per process and (expression, instantiation); 0 or an MJHMC_ERR_* code
-// with *err the message (MJHMC_ERR_INVALID: the compiler's log)
-int projections_link_compile(const std::string& link, int state_dtype, int K, const std::string& include_dir, const void** image,
-                             const char** lowered, std::string* err);
+// the code object and the lowered kernel name of projections_kernel<state_dtype, proj_lane_values(K), link> for the C
+// expression `link` of u, k and p[m], compiled with hipRTC once per process and (expression, instantiation)
+// (rtc_compile_cached, user_expr.hpp); 0 or an MJHMC_ERR_* code with *err the message (MJHMC_ERR_INVALID: the compiler's log)
+int projections_link_compile(const std::string& link, int state_dtype, int K, const std::string& include_dir, const ::RtcCode** out,
+                             std::string* err);
 #endif
 
 }  // namespace mjhmc

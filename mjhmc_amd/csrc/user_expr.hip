@@ -14,10 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <atomic>
+#include <cstdio>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "handles.hpp"
+#include "sampler_internal.hpp"   // test_env
 #include "user_expr.hpp"
 
 namespace {
@@ -162,13 +167,34 @@ std::vector<std::string> user_expr_kernel_names(int E) {
   return n;
 }
 
+// Test build only (libmjhmc_hip_test.so): when MJHMC_RTC_KEEP names a directory, every source that is actually compiled
+// is kept there as <file_name>_<running number>.hip, followed by one line per name expression that forces its
+// instantiation -- so that hipcc compiles the file offline to the kernels hipRTC built (tools/isa_equal.py --rtc).
+static void rtc_keep(const std::string& src, const char* file_name, const std::vector<std::string>& names) {
+  const char* dir = test_env("MJHMC_RTC_KEEP");
+  if (!dir) return;
+  static std::atomic<int> kept{0};
+  std::string stem = file_name;
+  if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".hip") == 0) stem.resize(stem.size() - 4);
+  char number[16];
+  std::snprintf(number, sizeof(number), "_%04d", kept++);
+  FILE* f = std::fopen((std::string(dir) + "/" + stem + number + ".hip").c_str(), "w");
+  if (!f) return;
+  std::string text = src;
+  for (size_t i = 0; i < names.size(); ++i)
+    text += "__attribute__((used)) static void* const mjhmc_keep_" + std::to_string(i) + " = (void*)&" + names[i] + ";\n";
+  std::fwrite(text.data(), 1, text.size(), f);
+  std::fclose(f);
+}
+
 int rtc_compile(const std::string& src, const char* file_name, const std::string& include_dir, const std::vector<std::string>& names,
-                std::vector<char>* code, std::vector<std::string>* lowered, std::string* err) {
+                const char* failure, std::vector<char>* code, std::vector<std::string>* lowered, std::string* err) {
   Rtc& r = rtc();
   if (!r.err.empty()) {
     *err = r.err;
     return MJHMC_ERR_HIP;
   }
+  rtc_keep(src, file_name, names);
   hiprtcProgram prog;
   if (r.CreateProgram(&prog, src.c_str(), file_name, 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
     *err = "hiprtcCreateProgram failed";
@@ -185,7 +211,7 @@ int rtc_compile(const std::string& src, const char* file_name, const std::string
     r.GetProgramLogSize(prog, &ls);
     std::string log(ls, '\0');
     if (ls) r.GetProgramLog(prog, &log[0]);
-    *err = "the energy expressions do not compile:\n" + log;
+    *err = std::string(failure) + ":\n" + log;
     r.DestroyProgram(&prog);
     return MJHMC_ERR_INVALID;
   }
@@ -209,7 +235,27 @@ int rtc_compile(const std::string& src, const char* file_name, const std::string
 
 int user_expr_compile(const std::string& src, const std::string& include_dir, int E, std::vector<char>* code,
                       std::vector<std::string>* lowered, std::string* err) {
-  return rtc_compile(src, "mjhmc_user_energy.hip", include_dir, user_expr_kernel_names(E), code, lowered, err);
+  return rtc_compile(src, "mjhmc_user_energy.hip", include_dir, user_expr_kernel_names(E), "the energy expressions do not compile",
+                     code, lowered, err);
+}
+
+int rtc_compile_cached(const std::string& src, const char* file_name, const std::vector<std::string>& names,
+                       const std::string& include_dir, const char* failure, const RtcCode** out, std::string* err) {
+  static std::mutex mu;
+  static std::map<std::string, RtcCode> cache;   // (a map's entries stay where they are: the pointers handed out hold)
+  std::string key = std::string(file_name) + "\n-I" + include_dir + "\n";
+  for (const std::string& n : names) key += n + "\n";
+  key += src;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(key);
+  if (it == cache.end()) {
+    RtcCode c;
+    const int rc = rtc_compile(src, file_name, include_dir, names, failure, &c.code, &c.lowered, err);
+    if (rc) return rc;
+    it = cache.emplace(std::move(key), std::move(c)).first;
+  }
+  *out = &it->second;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -22,9 +22,18 @@ struct UserEnergy {
 std::string user_expr_source(const std::string& energy_expr, const std::string& grad_expr, const std::string& stats = "",
                              const std::string& energy0_expr = "");
 std::vector<std::string> user_expr_kernel_names(int E);
-// hipRTC with the library's build flags; `names`: name expressions whose lowered names are returned in *lowered
+// hipRTC with the library's build flags; `names`: name expressions whose lowered names are returned in *lowered;
+// `failure`: what a compile error says before the compiler's log ("the energy expressions do not compile")
 int rtc_compile(const std::string& src, const char* file_name, const std::string& include_dir, const std::vector<std::string>& names,
-                std::vector<char>* code, std::vector<std::string>* lowered, std::string* err);
+                const char* failure, std::vector<char>* code, std::vector<std::string>* lowered, std::string* err);
+// The same, compiled once per process: one mutex (a second thread asking for the same code waits for it) and one
+// never-evicting map, keyed by everything that decides the code -- source, file name, name expressions, include directory.
+struct RtcCode {
+  std::vector<char> code;
+  std::vector<std::string> lowered;   // of `names`, in their order
+};
+int rtc_compile_cached(const std::string& src, const char* file_name, const std::vector<std::string>& names,
+                       const std::string& include_dir, const char* failure, const RtcCode** out, std::string* err);
 int user_expr_compile(const std::string& src, const std::string& include_dir, int E, std::vector<char>* code,
                       std::vector<std::string>* lowered, std::string* err);
 

@@ -207,40 +207,16 @@ class DeviceEnergy(object):
         include/mjhmc_hip.h):  E(x) = sum_j f(u_j, j),  u = W x + b,  dE/dx = W^T f'(u);  W (K, D), b (K,), f / f'
         C expressions of ``u``, ``j``, ``p[k]`` (``params``) and ``q[m]`` (row m of ``expert_params``, (M <= 4, K)),
         evaluated in float32.  1 <= D, K <= 512."""
-        W, b, params, q = linear_arrays(W, b, params, expert_params)
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self.kind = _lib.E_LINEAR_EXPR
-        self.nexperts, self.ndims = W.shape
-        self.params = params
-        self.W, self.b, self.expert_params = W, b, q
-        h = ctypes.c_void_p()
-        check(ctx.lib.mjhmc_energy_create_linear(
-            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), str(energy_expr).encode(), str(grad_expr).encode(),
-            ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
-            _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
-        self.handle = h
-        return self
+        return cls._linear(ctx, 'mjhmc_energy_create_linear', linear_arrays(W, b, params, expert_params), energy_expr, grad_expr)
 
     @classmethod
     def from_linear_tall(cls, ctx, W, b, energy_expr, grad_expr, params=(), expert_params=None):
         """The same form with more experts than the tile kernels hold (mjhmc_energy_create_linear_tall): W (K, D),
         1 <= D <= 512, 1 <= K <= 2**20, the experts in blocks of the padded D under one fused matrix-core kernel; ``j`` in
         the expressions is the global expert index.  Samplers of it run the engine's multi-pass path."""
-        W, b, params, q = tall_linear_arrays(W, b, params, expert_params)
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self.kind = _lib.E_LINEAR_EXPR
-        self.nexperts, self.ndims = W.shape
-        self.params = params
-        self.W, self.b, self.expert_params = W, b, q
+        self = cls._linear(ctx, 'mjhmc_energy_create_linear_tall', tall_linear_arrays(W, b, params, expert_params), energy_expr,
+                           grad_expr)
         self.tall = True
-        h = ctypes.c_void_p()
-        check(ctx.lib.mjhmc_energy_create_linear_tall(
-            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), str(energy_expr).encode(), str(grad_expr).encode(),
-            ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
-            _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
-        self.handle = h
         return self
 
     @classmethod
@@ -250,18 +226,26 @@ class DeviceEnergy(object):
         ``groups`` = (C, G): the first G * C rows of W are G groups of C consecutive experts (softmax regression: a data
         row per group, a class per member), the rest plain experts; 2 <= C <= 16, D <= 512, K <= 2**20.  ``j`` in the
         expressions is the caller's expert index.  Samplers of it run the engine's multi-pass path."""
-        W, b, params, q, (C, G) = grouped_linear_arrays(W, b, groups, params, expert_params)
+        W, b, params, q, groups = grouped_linear_arrays(W, b, groups, params, expert_params)
+        self = cls._linear(ctx, 'mjhmc_energy_create_linear_grouped', (W, b, params, q), energy_expr, grad_expr, groups)
+        self.tall = True
+        self.groups = groups
+        return self
+
+    @classmethod
+    def _linear(cls, ctx, create, arrays, energy_expr, grad_expr, groups=()):
+        """Behind from_linear, from_linear_tall and from_linear_grouped: the checked arrays (W, b, params, expert_params)
+        handed to the entry point ``create``, which takes ``groups`` (C, G; the grouped form alone) behind b."""
+        W, b, params, q = arrays
         self = cls.__new__(cls)
         self.ctx = ctx
         self.kind = _lib.E_LINEAR_EXPR
         self.nexperts, self.ndims = W.shape
         self.params = params
         self.W, self.b, self.expert_params = W, b, q
-        self.tall = True
-        self.groups = (C, G)
         h = ctypes.c_void_p()
-        check(ctx.lib.mjhmc_energy_create_linear_grouped(
-            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), C, G, str(energy_expr).encode(), str(grad_expr).encode(),
+        check(getattr(ctx.lib, create)(
+            ctx.handle, self.ndims, self.nexperts, ptr(W), ptr(b), *groups, str(energy_expr).encode(), str(grad_expr).encode(),
             ptr(params) if params.size else None, params.size, ptr(q) if q.size else None, q.shape[0],
             _lib.KERNEL_HEADERS.encode(), ctypes.byref(h)), ctx.lib)
         self.handle = h

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Machine-code identity of two source trees, kernel by kernel.
 
-  tools/isa_equal.py compile OUT [--tree ROOT] [--jobs N] [TU.hip ...]
+  tools/isa_equal.py compile OUT [TU.hip ...] [--tree ROOT] [--jobs N] [--rtc DIR]
       compiles every translation unit of the Makefile's SRCS, plus device_math_probe.hip (or the ones named), of the
       tree ROOT (default: the tree this file lies in) to gfx950 device-only assembly OUT/<TU>.s, with the Makefile's own
-      flags (make print-flags) plus --cuda-device-only -S, at most 16 compiles at a time.
+      flags (make print-flags) plus --cuda-device-only -S, at most 16 compiles at a time.  --rtc DIR: also every DIR/*.hip,
+      a source hipRTC compiled at run time as the test build kept it (MJHMC_RTC_KEEP, tools/rtc_sources.py), with the same
+      flags against ROOT's headers, to OUT/rtc_<name>.s -- one DIR compiled against two trees compares their headers.
   tools/isa_equal.py compare A B [--allow REGEX]
       compares two such directories.  Per translation unit the sets of kernel names must be equal; per kernel (keyed by
       its mangled name: instantiation order follows include order, so a whole-file diff will not do) the instruction
@@ -25,22 +27,25 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FIGURES = ('vgpr_count', 'sgpr_spill_count', 'vgpr_spill_count', 'private_segment_fixed_size', 'group_segment_fixed_size')
 
 
-def compile_tree(root, out, jobs, only):
+def compile_tree(root, out, jobs, only, rtc=None):
     csrc = os.path.join(root, 'mjhmc_amd', 'csrc')
     flags = subprocess.check_output(['make', '-s', 'print-flags'], cwd=csrc, text=True).split()
     srcs = re.search(r'^SRCS\s*=\s*(.*)$', open(os.path.join(csrc, 'Makefile')).read(), flags=re.M).group(1).split()
     srcs = only or srcs + ['device_math_probe.hip']
     os.makedirs(out, exist_ok=True)
 
+    kept = {f: os.path.join(os.path.abspath(rtc), f) for f in sorted(os.listdir(rtc)) if f.endswith('.hip')} if rtc else {}
+
     def one(tu):
-        dst = os.path.join(os.path.abspath(out), tu[:-4] + '.s')
-        r = subprocess.run([HIPCC] + flags + ['--cuda-device-only', '-S', tu, '-o', dst], cwd=csrc,
+        dst = os.path.join(os.path.abspath(out), ('rtc_' if tu in kept else '') + tu[:-4] + '.s')
+        r = subprocess.run([HIPCC] + flags + ['--cuda-device-only', '-S', '-I', os.path.abspath(csrc), kept.get(tu, tu), '-o', dst], cwd=csrc,
                            stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
         return tu, r.returncode, r.stderr
 
     failed = 0
     # longest first: the energies' translation units bound the wall time
     srcs.sort(key=lambda tu: (not tu.startswith('energy_'), not tu.startswith('dense_')))
+    srcs += list(kept)
     with concurrent.futures.ThreadPoolExecutor(max(1, min(jobs, 16))) as pool:
         for tu, rc, err in pool.map(one, srcs):
             print('%-28s %s' % (tu, 'ok' if rc == 0 else 'FAILED\n' + err), flush=True)
@@ -139,6 +144,7 @@ def main():
     c.add_argument('out')
     c.add_argument('--tree', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
     c.add_argument('--jobs', type=int, default=min(16, os.cpu_count() or 1))
+    c.add_argument('--rtc')
     c.add_argument('tus', nargs='*')
     d = sub.add_parser('compare')
     d.add_argument('a')
@@ -146,7 +152,7 @@ def main():
     d.add_argument('--allow')
     args = ap.parse_args()
     if args.cmd == 'compile':
-        return compile_tree(args.tree, args.out, args.jobs, args.tus)
+        return compile_tree(args.tree, args.out, args.jobs, args.tus, args.rtc)
     return compare(args.a, args.b, args.allow)
 
 
