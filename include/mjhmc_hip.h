@@ -206,7 +206,7 @@ int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr
  * tile (mjhmc_linear_grouped_layout); one fused kernel, compiled with hipRTC at creation for this C, walks the grouped
  * blocks and then the plain ones.  The kind is MJHMC_E_LINEAR_EXPR and the sampler runs the multi-pass path with either state
  * dtype, as for a tall model of any nexperts.  The per-expert passes (mjhmc_pointwise_create, mjhmc_influence_create) refuse
- * a grouped energy: MJHMC_ERR_UNSUPPORTED.  group_size < 2, n_groups < 1, G C > nexperts, NULLs, more than 4 expert rows,
+ * a grouped energy: MJHMC_ERR_UNSUPPORTED; its per-row pass is mjhmc_pointwise_create_grouped.  group_size < 2, n_groups < 1, G C > nexperts, NULLs, more than 4 expert rows,
  * non-finite W / b, compile errors (with the log): MJHMC_ERR_INVALID.  group_size > 16, ndims > 512, more than 2^20 slots:
  * MJHMC_ERR_UNSUPPORTED, naming the limit. */
 int mjhmc_energy_create_linear_grouped(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
@@ -722,6 +722,37 @@ int mjhmc_pointwise_read(mjhmc_pointwise* h, double* W, double* S1, double* S2, 
 int mjhmc_pointwise_reset(mjhmc_pointwise* h);
 /* frees the handle's device memory and its sums (NULL: nothing) */
 int mjhmc_pointwise_destroy(mjhmc_pointwise* h);
+
+/* Per-group ("per data row") statistics of a GROUPED linear-model energy (mjhmc_energy_create_linear_grouped), on the
+ * device (csrc/dense_lin_group_pointwise.hpp): what mjhmc_pointwise_create does for the experts of a square or tall model,
+ * for the G groups of C members of a grouped one -- the rows of a softmax regression.  A value is a float32 C expression
+ * evaluated at a grouped expert j = g C + c (the caller's index): it sees what a mjhmc_pointwise value sees (u, j, p[k],
+ * q[m]) and three names more,
+ *   lse  the group's log-sum-exp, formed exactly as the energy forms it (float32, contraction off: m = fmaxf over c
+ *        ascending, t_c = expf(u_c - m), s = t_0 + ... + t_{C-1} ascending, lse = m + logf(s)),
+ *   sm   the member's softmax t_c / s,
+ *   c    the member index 0 .. C - 1 (int).
+ * Bit m of member_mask gives the kind of value m.  Clear -- PER GROUP: the value of group g is the float32 sum of the
+ * expression over the group's members in ascending c (s = c ? s + t : t), one number per data row; q[0]*(u - lse) with a
+ * one-hot q[0] is the row's log-likelihood, q[0]*sm the probability of its observed class.  Set -- PER MEMBER: one number
+ * per grouped expert, column g C + c; sm alone is the fitted class probabilities.  The handle's column count
+ * (mjhmc_pointwise_info: nexperts) is G C when a value is per member and G otherwise; a per-group value fills the first G
+ * columns of its row and the columns behind them read as empty: S1 = S2 = 0, (mx, se) = (-inf, 0).  The sums, the
+ * log-mean-exp pairs asked for by lme_mask, their order, the selection of weight-0 states and the refusals of
+ * mjhmc_pointwise_accumulate ("expert" in its message: the column) are those of the per-expert pass; mjhmc_pointwise_accumulate,
+ * _reset, _read, _info and _destroy serve the handle unchanged.  The plain experts behind the groups (the prior) are not
+ * reported on.  The kernel is compiled with hipRTC for the model's C and the values' kinds when the handle is created.
+ * mjhmc_pointwise_grouped_check: the compile alone, for a model of ndims x nexperts with n_groups groups of group_size,
+ * with no device; the model's arguments are checked as by mjhmc_linear_grouped_check.
+ * MJHMC_ERR_INVALID: NULL arguments, no sample ring yet, no value or more than 4, an empty value, lme_mask or member_mask
+ * bits beyond the M values, an expression that does not compile (the message is the compiler's log), group_size < 2,
+ * n_groups < 1, G C > nexperts; MJHMC_ERR_UNSUPPORTED: an energy that is not a grouped linear model (the message names
+ * mjhmc_pointwise_create, the pass of the other linear models), a state that is not float32 / float64, group_size > 16,
+ * ndims > 512, more than 2^20 slots. */
+int mjhmc_pointwise_grouped_check(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* values,
+                                  unsigned member_mask, const char* include_dir);
+int mjhmc_pointwise_create_grouped(mjhmc_sampler* s, const char* values, unsigned lme_mask, unsigned member_mask,
+                                   const char* include_dir, mjhmc_pointwise** out);
 
 /* Data-row influence of a linear-model energy, on the device (csrc/influence.hip, csrc/dense_lin_values.hpp): what ties a
  * data row to a coefficient.  For an energy E(x) = sum_{j<K} f(u_j, j), u = W x + b (MJHMC_E_LINEAR_EXPR, square or tall),

@@ -162,6 +162,10 @@ PROTOTYPES = {
     'mjhmc_pointwise_read': (ctypes.c_int, [_P, _dp, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
     'mjhmc_pointwise_reset': (ctypes.c_int, [_P]),
     'mjhmc_pointwise_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_pointwise_grouped_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p,
+                                                     ctypes.c_uint, ctypes.c_char_p]),
+    'mjhmc_pointwise_create_grouped': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_uint, ctypes.c_uint, ctypes.c_char_p,
+                                                      ctypes.POINTER(_P)]),
     'mjhmc_influence_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_influence_create': (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_char_p,
                                               ctypes.POINTER(_P)]),

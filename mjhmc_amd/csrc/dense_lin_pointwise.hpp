@@ -38,6 +38,7 @@ constexpr int kPwStripTiles = 32;          // tiles of 32 particles per strip: a
 constexpr int kPwMaxValues = 4;
 constexpr int kPwNoBad = 0x7FFFFFFF;       // *flags when every value is finite
 constexpr int kPwExpertBits = 20;          // *flags = (m << 20) | j; j < 2^20 (kLinTallMaxExperts)
+constexpr int kPwDead = 0x7FFFFFFF;        // the column of an entry that belongs to no column: below no K
 
 struct PwArgs {
   const float* X;     // [32 ntiles][P] float32 rows of one slot, rows beyond the batch zero
@@ -79,12 +80,46 @@ struct PwAcc {
   double s1[M][4], s2[M][4], mx[M][4], se[M][4];
 };
 
+// The image of value MI (sh.pub[1], published by the caller) summed over the tile's 32 particles into acc, between two
+// barriers of its own.  jq: the column of each of the thread's four entries; an entry whose column is not below K (a
+// padded expert; kPwDead) is dead -- in no sum, in no check, never stored.
+template <int NB, int M, int MI>
+__device__ __forceinline__ void pw_reduce(Shared<NB>& sh, const double* wts, int g, int sub, const int (&jq)[4], int K, unsigned lme,
+                                          PwAcc<M>& acc, int& bad) {
+  constexpr int PS = 4 * NB;   // particles of a subset
+  __syncthreads();
+  const f32x4* img = &sh.pub[1][0].v[0][0][0] + (g >> 1) * 64 + (g & 1) * 32 + sub * PS;
+  const int rot = g & (PS - 1);
+  const bool keep = (lme >> MI) & 1u;   // (wave-uniform)
+#pragma unroll 1
+  for (int i = 0; i < PS; ++i) {
+    const int cc = (i + rot) & (PS - 1);
+    const f32x4 t4 = img[cc];
+    const double wp = wts[sub * PS + cc];
+    const bool on = wp > 0.0;
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      const double t = (double)t4[qq];
+      const bool live = on && jq[qq] < K, fin = pw_finite(t);
+      if (live && !fin) {
+        const int code = (MI << kPwExpertBits) | jq[qq];
+        bad = code < bad ? code : bad;
+      }
+      const bool use = live && fin;
+      const double wt = wp * t;
+      acc.s1[MI][qq] = acc.s1[MI][qq] + (use ? wt : 0.0);
+      acc.s2[MI][qq] = acc.s2[MI][qq] + (use ? wt * t : 0.0);
+      if (keep) pw_lme_add(acc.mx[MI][qq], acc.se[MI][qq], t, wp, use);
+    }
+  }
+  __syncthreads();   // the image is read: the next value (or the next tile's) may take it
+}
+
 // value MI of the tile whose u sits in the accumulator registers, and the values after it
 template <int NB, class H, int MI>
 struct PwValue {
   static __device__ __forceinline__ void run(const Tile<NB>& u, const PotLinear& lin, Shared<NB>& sh, const double* wts, int j0,
                                             int w, int h, int lane, int g, int sub, const int (&jq)[4], unsigned lme, PwAcc<H::kM>& acc, int& bad) {
-    constexpr int PS = 4 * NB;   // particles of a subset
     {
       Tile<NB> v;
 #pragma unroll
@@ -93,103 +128,104 @@ struct PwValue {
         for (int r = 0; r < NB; ++r) {
           const int j = j0 + 32 * NB * w + NB * acc_row(q, h) + r;
           // (padded experts j >= K are not masked here -- 16 NB loop-invariant predicates would sit in scalar registers
-          // across the strip: the reduction below never reads their entries into a sum, and nothing stores them)
+          // across the strip: the reduction never reads their entries into a sum, and nothing stores them)
           v.b[r][q] = H::template h<MI>(u.b[r][q], j, lin.p, LinQ{lin.q, lin.stride, j});
         }
       publish<NB>(sh.pub[1][w], lane, v);
     }
-    __syncthreads();
-    const f32x4* img = &sh.pub[1][0].v[0][0][0] + (g >> 1) * 64 + (g & 1) * 32 + sub * PS;
-    const int rot = g & (PS - 1);
-    const bool keep = (lme >> MI) & 1u;   // (wave-uniform)
-#pragma unroll 1
-    for (int i = 0; i < PS; ++i) {
-      const int cc = (i + rot) & (PS - 1);
-      const f32x4 t4 = img[cc];
-      const double wp = wts[sub * PS + cc];
-      const bool on = wp > 0.0;
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const double t = (double)t4[qq];
-        const bool live = on && jq[qq] < lin.K, fin = pw_finite(t);
-        if (live && !fin) {
-          const int code = (MI << kPwExpertBits) | jq[qq];
-          bad = code < bad ? code : bad;
-        }
-        const bool use = live && fin;
-        const double wt = wp * t;
-        acc.s1[MI][qq] = acc.s1[MI][qq] + (use ? wt : 0.0);
-        acc.s2[MI][qq] = acc.s2[MI][qq] + (use ? wt * t : 0.0);
-        if (keep) pw_lme_add(acc.mx[MI][qq], acc.se[MI][qq], t, wp, use);
-      }
-    }
-    __syncthreads();   // the image is read: the next value (or the next tile's) may take it
+    pw_reduce<NB, H::kM, MI>(sh, wts, g, sub, jq, lin.K, lme, acc, bad);
     if constexpr (MI + 1 < H::kM) PwValue<NB, H, MI + 1>::run(u, lin, sh, wts, j0, w, h, lane, g, sub, jq, lme, acc, bad);
   }
 };
 
-// the particle subsets of value MI combined in ascending sub through red[16][256] (LDS), the experts j < K stored
+// the particle subsets of value MI combined in ascending sub through red[16][256] (LDS), the columns jq < K stored
+template <int NB, int M, int MI>
+__device__ __forceinline__ void pw_store_one(const PwArgs& a, int K, double* red, size_t KP, int strip, int g, int sub,
+                                             const int (&jq)[4], PwAcc<M>& acc) {
+  constexpr int NG = 32 * NB, SPLIT = 256 / NG;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    red[(0 + qq) * 256 + tid] = acc.s1[MI][qq];
+    red[(4 + qq) * 256 + tid] = acc.s2[MI][qq];
+    red[(8 + qq) * 256 + tid] = acc.mx[MI][qq];
+    red[(12 + qq) * 256 + tid] = acc.se[MI][qq];
+  }
+  __syncthreads();
+  if (sub == 0) {
+    double* out = a.part + (size_t)strip * (4 * M) * KP;
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      double s1 = acc.s1[MI][qq], s2 = acc.s2[MI][qq], mx = acc.mx[MI][qq], se = acc.se[MI][qq];
+      for (int o = 1; o < SPLIT; ++o) {
+        const int t = g + o * NG;
+        s1 = s1 + red[(0 + qq) * 256 + t];
+        s2 = s2 + red[(4 + qq) * 256 + t];
+        if ((a.lme >> MI) & 1u) pw_lme_merge(mx, se, red[(8 + qq) * 256 + t], red[(12 + qq) * 256 + t]);
+      }
+      if (jq[qq] < K) {
+        out[(size_t)(0 * M + MI) * KP + jq[qq]] = s1;
+        out[(size_t)(1 * M + MI) * KP + jq[qq]] = s2;
+        out[(size_t)(2 * M + MI) * KP + jq[qq]] = mx;
+        out[(size_t)(3 * M + MI) * KP + jq[qq]] = se;
+      }
+    }
+  }
+  __syncthreads();
+}
+
 template <int NB, class H, int MI>
 struct PwStore {
   static __device__ __forceinline__ void run(const PwArgs& a, const PotLinear& lin, double* red, size_t KP, int strip, int g, int sub,
                                             const int (&jq)[4], PwAcc<H::kM>& acc) {
-    constexpr int M = H::kM, NG = 32 * NB, SPLIT = 256 / NG;
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      red[(0 + qq) * 256 + tid] = acc.s1[MI][qq];
-      red[(4 + qq) * 256 + tid] = acc.s2[MI][qq];
-      red[(8 + qq) * 256 + tid] = acc.mx[MI][qq];
-      red[(12 + qq) * 256 + tid] = acc.se[MI][qq];
-    }
-    __syncthreads();
-    if (sub == 0) {
-      double* out = a.part + (size_t)strip * (4 * M) * KP;
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        double s1 = acc.s1[MI][qq], s2 = acc.s2[MI][qq], mx = acc.mx[MI][qq], se = acc.se[MI][qq];
-        for (int o = 1; o < SPLIT; ++o) {
-          const int t = g + o * NG;
-          s1 = s1 + red[(0 + qq) * 256 + t];
-          s2 = s2 + red[(4 + qq) * 256 + t];
-          if ((a.lme >> MI) & 1u) pw_lme_merge(mx, se, red[(8 + qq) * 256 + t], red[(12 + qq) * 256 + t]);
-        }
-        if (jq[qq] < lin.K) {
-          out[(size_t)(0 * M + MI) * KP + jq[qq]] = s1;
-          out[(size_t)(1 * M + MI) * KP + jq[qq]] = s2;
-          out[(size_t)(2 * M + MI) * KP + jq[qq]] = mx;
-          out[(size_t)(3 * M + MI) * KP + jq[qq]] = se;
-        }
-      }
-    }
-    __syncthreads();
+    pw_store_one<NB, H::kM, MI>(a, lin.K, red, KP, strip, g, sub, jq, acc);
     if constexpr (MI + 1 < H::kM) PwStore<NB, H, MI + 1>::run(a, lin, red, KP, strip, g, sub, jq, acc);
   }
 };
 
-// H: kM values, h<MI>(u, j, p, q) the caller's expressions (linear_energy.hip)
+// The experts of one block as this pass sees them -- B: kM values; set(blk, g) the columns of reduction thread g's four
+// entries; values(u, ...) every value published and reduced; store(...) the strip's sums.  Here the block of a square or
+// tall model: expert j0 + local in the caller's order, every value per expert (H: kM values, h<MI>(u, j, p, q) the
+// caller's expressions, linear_energy.hip).  The grouped model's is GpBlock (dense_lin_group_pointwise.hpp).
 template <int NB, class H>
-__device__ __forceinline__ void lin_pointwise_items(const PwArgs& a, const LinTallModel& tm, const PotLinear& lin, Shared<NB>& sh,
-                                                    double* wts /* [32] LDS */) {
-  constexpr int P = 128 * NB, M = H::kM, NG = 32 * NB;
+struct PwTallBlock {
+  static constexpr int kM = H::kM;
+  const PotLinear& lin;
+  int j0;
+  int jq[4];
+  __device__ __forceinline__ void set(int blk, int g) {
+    // group g = ((w' NB + r) 4 + q4) 2 + h' of the image: its four experts are rows 8 q4 + 4 h' + qq of wave w', block r
+    const int e0 = 32 * NB * ((g >> 3) / NB) + NB * (8 * ((g >> 1) & 3) + 4 * (g & 1)) + ((g >> 3) % NB);
+    j0 = blk * (128 * NB);
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) jq[qq] = j0 + e0 + NB * qq;
+  }
+  __device__ __forceinline__ void values(const Tile<NB>& u, Shared<NB>& sh, const double* wts, int w, int h, int lane, int g, int sub,
+                                         unsigned lme, PwAcc<kM>& acc, int& bad) const {
+    PwValue<NB, H, 0>::run(u, lin, sh, wts, j0, w, h, lane, g, sub, jq, lme, acc, bad);
+  }
+  __device__ __forceinline__ void store(const PwArgs& a, double* red, size_t KP, int strip, int g, int sub, PwAcc<kM>& acc) const {
+    PwStore<NB, H, 0>::run(a, lin, red, KP, strip, g, sub, jq, acc);
+  }
+};
+
+// the items (strip, block) over nblk blocks stored at W1b / cbb like a tall model's; KP: the column pitch of a.part
+template <int NB, class B>
+__device__ __forceinline__ void pw_items(const PwArgs& a, const float* W1b, const float* cbb, int nblk, size_t KP, B& bv, Shared<NB>& sh,
+                                         double* wts /* [32] LDS */) {
+  constexpr int P = 128 * NB, M = B::kM, NG = 32 * NB;
   constexpr size_t MB = (size_t)P * P;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
   const int g = tid % NG, sub = tid / NG;
-  // group g = ((w' NB + r) 4 + q4) 2 + h' of the image: its four experts are rows 8 q4 + 4 h' + qq of wave w', block r
-  const int e0 = 32 * NB * ((g >> 3) / NB) + NB * (8 * ((g >> 1) & 3) + 4 * (g & 1)) + ((g >> 3) % NB);
-  const size_t KP = (size_t)tm.nblk * P;
-  const int nitems = a.nstrips * tm.nblk;
+  const int nitems = a.nstrips * nblk;
   int bad = kPwNoBad;
   for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
-    const int strip = item / tm.nblk, blk = item - strip * tm.nblk;
-    const int j0 = blk * P;
-    const float* W1 = tm.W1b + (size_t)blk * MB;
+    const int strip = item / nblk, blk = item - strip * nblk;
+    const float* W1 = W1b + (size_t)blk * MB;
     // GEMM 1 alone.  ndims = P: NB = 1's skip of the k-row groups beyond D (gemm_any) is folded away -- its 16 predicates are
     // loop invariant here and would hold 32 scalar registers across the strip (30 - 35 of them spilled)
-    const PotModel mdl{W1, W1, tm.cb + (size_t)blk * P, nullptr, P, P};
-    int jq[4];
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) jq[qq] = j0 + e0 + NB * qq;
+    const PotModel mdl{W1, W1, cbb + (size_t)blk * P, nullptr, P, P};
+    bv.set(blk, g);
     // (the previous item's last LDS reads lie before its closing barrier)
     for (int i = tid; i < P; i += 256) sh.cb[i] = mdl.cb[i];
     AReg<NB> ar;
@@ -227,10 +263,10 @@ __device__ __forceinline__ void lin_pointwise_items(const PwArgs& a, const LinTa
       rowvec_load<NB>(sh.cb, w, h, u);
       if constexpr (NB == 1) gemm_any<1, false>(mdl, ar, sh.pub[0], w, c, h, lane, u);
       else gemm_dim<NB>(W1, W1, sh.pub[0], w, c, h, lane, ar.a0, u);   // (hands on chunk 0 of the same block: the next tile's)
-      PwValue<NB, H, 0>::run(u, lin, sh, wts, j0, w, h, lane, g, sub, jq, a.lme, acc, bad);
+      bv.values(u, sh, wts, w, h, lane, g, sub, a.lme, acc, bad);
     }
     // both images are free behind the last value's closing barrier: 16 x 256 doubles = 32 KB <= sizeof(sh.pub)
-    PwStore<NB, H, 0>::run(a, lin, reinterpret_cast<double*>(&sh.pub[0][0]), KP, strip, g, sub, jq, acc);
+    bv.store(a, reinterpret_cast<double*>(&sh.pub[0][0]), KP, strip, g, sub, acc);
     if (blk == 0 && w == 0) {   // the strip's weights: lane l takes p = 32 t0 + l + 64 i, then the butterfly
       double s = 0.0;
       for (int i = 0; i < kPwStripTiles / 2; ++i) {
@@ -243,6 +279,13 @@ __device__ __forceinline__ void lin_pointwise_items(const PwArgs& a, const LinTa
     }
   }
   if (bad != kPwNoBad) atomicMin(a.flags, bad);
+}
+
+template <int NB, class H>
+__device__ __forceinline__ void lin_pointwise_items(const PwArgs& a, const LinTallModel& tm, const PotLinear& lin, Shared<NB>& sh,
+                                                    double* wts /* [32] LDS */) {
+  PwTallBlock<NB, H> bv{lin};
+  pw_items<NB>(a, tm.W1b, tm.cb, tm.nblk, (size_t)tm.nblk * (128 * NB), bv, sh, wts);
 }
 
 }  // namespace mjhmc

@@ -392,6 +392,42 @@ int linear_grouped_check_args(int ndims, int64_t nexperts, int group_size, int64
   return 0;
 }
 
+// The per-group statistics pass of a grouped model (dense_lin_group_pointwise.hpp): the caller's M
+// value expressions as a functor -- they see lse, sm and c beside what a pointwise value sees -- with the group size and
+// the values' kinds as constants of the source, and the one kernel around it
+namespace {
+
+std::string linear_group_pointwise_source(const std::vector<std::string>& values, int group_size, unsigned member_mask) {
+  std::string s;
+  s += "#include \"dense_lin_group_pointwise.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += "constexpr int kGroupSize = " + std::to_string(group_size) + ";   // members per group: the register loops are unrolled over it\n";
+  s += "// the caller's value expressions h_m(u, j; p, q; lse, sm, c) (u, lse, sm float; j, c int; p[k], q[m])\n";
+  s += "struct GpUserH {\n";
+  s += "  static constexpr int kM = " + std::to_string(values.size()) + ";\n";
+  s += "  static constexpr unsigned kMemberMask = " + std::to_string(member_mask) + "u;   // bit m: value m is per member\n";
+  s += "  template <int MI>\n";
+  s += "  static __device__ __forceinline__ float h(float u, int j, const float* __restrict__ p, LinQ q, float lse, float sm, int c) {\n";
+  s += "    (void)u; (void)j; (void)p; (void)q; (void)lse; (void)sm; (void)c;\n";
+  for (size_t m = 0; m < values.size(); ++m)
+    s += std::string(m ? "    else " : "    ") + "if constexpr (MI == " + std::to_string(m) + ") return (float)(" + values[m] + ");\n";
+  s += "    else return 0.f;\n  }\n";
+  s += "};\n";
+  s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_group_pointwise_kernel(const PwArgs a, const LinGroupedModel gm, const PotLinear lin) {\n";
+  s += "  __shared__ Shared<NB> sh;\n  __shared__ double wts[kP];\n  lin_group_pointwise_items<NB, kGroupSize, GpUserH>(a, gm, lin, sh, wts);\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
+}  // namespace
+
+int linear_group_pointwise_compile(const std::vector<std::string>& values, int dim, int group_size, unsigned member_mask,
+                                   const std::string& include_dir, std::string* err, const RtcCode** out) {
+  return rtc_compile_cached(linear_group_pointwise_source(values, group_size, member_mask), "mjhmc_linear_group_pointwise.hip",
+                            {"mjhmc::lin_group_pointwise_kernel<" + std::to_string(dim / 128) + ">"}, include_dir,
+                            "the value expressions do not compile", out, err);
+}
+
 int linear_grouped_compile(const std::string& energy_expr, const std::string& grad_expr, int dim, int group_size,
                            const std::string& include_dir, std::string* err, const RtcCode** out) {
   return rtc_compile_cached(linear_grouped_source(energy_expr, grad_expr, group_size), "mjhmc_linear_grouped.hip",

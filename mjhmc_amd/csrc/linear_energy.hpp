@@ -70,6 +70,12 @@ int linear_grouped_energy_build(mjhmc_energy* e, int64_t nexperts, const double*
                                 int64_t n_groups, const char* energy_expr, const char* grad_expr, const double* params,
                                 size_t nparams, const double* expert_params, int n_expert_rows, const char* include_dir);
 
+// The per-group statistics pass of a grouped model (dense_lin_group_pointwise.hpp, pointwise.hip): the hipRTC compile of
+// lin_group_pointwise_kernel<dim / 128> around 1 .. 4 value expressions, dim = linear_grouped_layout's P; the group size and
+// the values' kinds (bit m of member_mask: value m is per member) are constants of the source and so of the cache key
+int linear_group_pointwise_compile(const std::vector<std::string>& values, int dim, int group_size, unsigned member_mask,
+                                   const std::string& include_dir, std::string* err, const RtcCode** out);
+
 // The per-expert statistics pass (dense_lin_pointwise.hpp, pointwise.hip): the padded dimension of the blocks a model of
 // (ndims, nexperts) is stored in (the tall layout beyond 512 experts, the square one otherwise; 0: no such model), and the
 // hipRTC compile of lin_pointwise_kernel<dim / 128> around 1 .. 4 value expressions (which of them keep a log-mean-exp is

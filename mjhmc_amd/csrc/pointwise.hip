@@ -13,6 +13,11 @@
 // the call's one read-back shows no flag: a refused call (a weight that is negative or not finite, a value that is not
 // finite) has added nothing.  Every slot goes onto the totals separately and in slot order, so the sums do not depend on
 // how a run is cut into calls.
+// A grouped model's handle (mjhmc_pointwise_create_grouped; the kernel in dense_lin_group_pointwise.hpp, DESIGN.md section
+// 3.3o) is the same handle with columns in place of experts: G C of them when a value is per member, G otherwise, the
+// grouped blocks alone as its items.  The kernel writes the columns a value has; the partials are set empty once, at
+// creation, so the columns G .. G C - 1 of a per-group value stay (0, 0, -inf, 0) through every fold.
+#include "dense_lin_group_pointwise.hpp"
 #include "dense_lin_pointwise.hpp"
 
 #include <algorithm>
@@ -33,6 +38,14 @@ __global__ __launch_bounds__(256) void pw_init_kernel(double* __restrict__ tot, 
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < kPwTotHead) tot[i] = 0.0;
   if (i < 4 * MK) tot[kPwTotHead + i] = (i >= 2 * MK && i < 3 * MK) ? -__builtin_huge_val() : 0.0;
+}
+
+// every strip's partials [4 M][KP] empty: (0, 0, -inf, 0)
+__global__ __launch_bounds__(256) void pw_part_empty_kernel(double* __restrict__ part, size_t total, size_t MKP) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const size_t r = i % (4 * MKP);
+  part[i] = (r >= 2 * MKP && r < 3 * MKP) ? -__builtin_huge_val() : 0.0;
 }
 
 // flags[0] = 1 when one of the n * N weights of the call is negative or not finite
@@ -99,17 +112,26 @@ int checked_values(const char* values, std::vector<std::string>* out) {
   return 0;
 }
 
+int checked_mask(const char* what, unsigned mask, int M) {
+  if (mask >> M)
+    return mjhmc_fail(MJHMC_ERR_INVALID, std::string("the ") + what + " mask " + std::to_string(mask) + " has bits beyond the " +
+                                             std::to_string(M) + " values");
+  return 0;
+}
+
 }  // namespace
 
 struct mjhmc_pointwise : RingAccumulator {
   using RingAccumulator::RingAccumulator;
-  int M = 0, K = 0, P = 0, nblk = 0;   // values, experts, the blocks' side and count
+  int M = 0, K = 0, P = 0, nblk = 0;   // values, experts (columns), the blocks' side and count
+  bool grouped = false;                // a grouped model's handle: columns are groups or members, nblk its grouped blocks
+  size_t KP = 0;                       // the column pitch of `part`: nblk P, or K for a grouped model
   unsigned lme = 0;
   int ntiles = 0, nstrips = 0;
   hipModule_t module = nullptr;
   hipFunction_t fn = nullptr;
   float* X32 = nullptr;                // [Npad][P]: the float32 rows of a float64 slot
-  double* part = nullptr;              // [nstrips][4 M][nblk P]
+  double* part = nullptr;              // [nstrips][4 M][KP]
   double* partW = nullptr;             // [nstrips]
   double* tot[2] = {nullptr, nullptr}; // the totals and the copy a call works on
   int cur = 0;
@@ -137,6 +159,42 @@ hipError_t pw_zero_sums(mjhmc_pointwise* h) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = pw_clear_flags(h);
   return e;
+}
+
+// the handle of M values over `cols` columns in nblk blocks of P around the compiled kernel, its buffers and empty sums
+int pw_new_handle(mjhmc_sampler* s, const RtcCode& code, int M, unsigned lme_mask, int P, int nblk, int cols, bool grouped,
+                  mjhmc_pointwise** out) {
+  const RingSource src = ring_source(s, nullptr);
+  mjhmc_pointwise* h = new mjhmc_pointwise("pointwise", "pointwise handle", s, nullptr, src);
+  h->M = M;
+  h->lme = lme_mask;
+  h->P = P;
+  h->nblk = nblk;
+  h->K = cols;
+  h->grouped = grouped;
+  h->KP = grouped ? (size_t)cols : (size_t)nblk * P;
+  h->ntiles = (int)((s->N + mjhmc::kP - 1) / mjhmc::kP);
+  h->nstrips = (h->ntiles + mjhmc::kPwStripTiles - 1) / mjhmc::kPwStripTiles;
+  const size_t MKP = (size_t)M * h->KP, part_elems = (size_t)h->nstrips * 4 * MKP;
+  hipError_t he = hipModuleLoadData(&h->module, code.code.data());
+  if (he == hipSuccess) he = hipModuleGetFunction(&h->fn, h->module, code.lowered[0].c_str());
+  if (he == hipSuccess && s->dtype == MJHMC_F64) he = hipMalloc((void**)&h->X32, (size_t)s->Npad * P * sizeof(float));
+  if (he == hipSuccess) he = hipMalloc((void**)&h->part, part_elems * sizeof(double));
+  if (he == hipSuccess) he = hipMalloc((void**)&h->partW, (size_t)h->nstrips * sizeof(double));
+  if (he == hipSuccess) he = hipMalloc((void**)&h->tot[0], h->tot_elems() * sizeof(double));
+  if (he == hipSuccess) he = hipMalloc((void**)&h->tot[1], h->tot_elems() * sizeof(double));
+  if (he == hipSuccess) he = hipMalloc((void**)&h->bad, 2 * sizeof(int));
+  if (he == hipSuccess && grouped) {   // (a per-group value's kernel leaves the columns behind its G untouched)
+    hipLaunchKernelGGL(pw_part_empty_kernel, dim3((unsigned)((part_elems + 255) / 256)), dim3(256), 0, s->stream, h->part, part_elems, MKP);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = pw_zero_sums(h);
+  if (he != hipSuccess) {
+    delete h;
+    (void)hipGetLastError();
+    return mjhmc_fail(MJHMC_ERR_HIP, std::string("pointwise buffers: ") + hipGetErrorString(he));
+  }
+  return acc_created(h, out);
 }
 
 }  // namespace
@@ -168,16 +226,14 @@ int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_ma
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the pointwise statistics of a grouped linear model (mjhmc_energy_create_linear_grouped) "
                                              "are not formed: its experts are stored in a permuted order and the terms of a group "
                                              "are coupled through its log-sum-exp, while this pass reports per expert in the "
-                                             "caller's order");
+                                             "caller's order (its per-row pass is mjhmc_pointwise_create_grouped)");
   if (s->dtype != MJHMC_F64 && s->dtype != MJHMC_F32)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "linear models run with float32 or float64 state");
   if (!s->ring) return acc_no_ring(nullptr);
   std::vector<std::string> v;
   TRY(checked_values(values, &v));
   const int M = (int)v.size();
-  if (lme_mask >> M)
-    return mjhmc_fail(MJHMC_ERR_INVALID, "the log-mean-exp mask " + std::to_string(lme_mask) + " has bits beyond the " +
-                                             std::to_string(M) + " values");
+  TRY(checked_mask("log-mean-exp", lme_mask, M));
   const int P = e->pot_dim;
   if (s->sh.pitch != P) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows do not have the model's padded pitch");
   HIPCHK(hipSetDevice(s->ctx->device));
@@ -185,31 +241,52 @@ int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_ma
   const RtcCode* code = nullptr;
   const int rc = linear_pointwise_compile(v, P, include_dir, &err, &code);
   if (rc) return mjhmc_fail(rc, err);
-  const RingSource src = ring_source(s, nullptr);
-  mjhmc_pointwise* h = new mjhmc_pointwise("pointwise", "pointwise handle", s, nullptr, src);
-  h->M = M;
-  h->lme = lme_mask;
-  h->P = P;
-  h->nblk = e->lin_tall() ? e->lin->tall_nblk : 1;
-  h->K = e->lin->gen.lin.K;
-  h->ntiles = (int)((s->N + mjhmc::kP - 1) / mjhmc::kP);
-  h->nstrips = (h->ntiles + mjhmc::kPwStripTiles - 1) / mjhmc::kPwStripTiles;
-  const size_t KP = (size_t)h->nblk * P;
-  hipError_t he = hipModuleLoadData(&h->module, code->code.data());
-  if (he == hipSuccess) he = hipModuleGetFunction(&h->fn, h->module, code->lowered[0].c_str());
-  if (he == hipSuccess && s->dtype == MJHMC_F64) he = hipMalloc((void**)&h->X32, (size_t)s->Npad * P * sizeof(float));
-  if (he == hipSuccess) he = hipMalloc((void**)&h->part, (size_t)h->nstrips * 4 * M * KP * sizeof(double));
-  if (he == hipSuccess) he = hipMalloc((void**)&h->partW, (size_t)h->nstrips * sizeof(double));
-  if (he == hipSuccess) he = hipMalloc((void**)&h->tot[0], h->tot_elems() * sizeof(double));
-  if (he == hipSuccess) he = hipMalloc((void**)&h->tot[1], h->tot_elems() * sizeof(double));
-  if (he == hipSuccess) he = hipMalloc((void**)&h->bad, 2 * sizeof(int));
-  if (he == hipSuccess) he = pw_zero_sums(h);
-  if (he != hipSuccess) {
-    delete h;
-    (void)hipGetLastError();
-    return mjhmc_fail(MJHMC_ERR_HIP, std::string("pointwise buffers: ") + hipGetErrorString(he));
-  }
-  return acc_created(h, out);
+  return pw_new_handle(s, *code, M, lme_mask, P, e->lin_tall() ? e->lin->tall_nblk : 1, e->lin->gen.lin.K, false, out);
+}
+
+int mjhmc_pointwise_grouped_check(int ndims, int64_t nexperts, int group_size, int64_t n_groups, const char* values,
+                                  unsigned member_mask, const char* include_dir) {
+  if (!values || !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  TRY(linear_grouped_check_args(ndims, nexperts, group_size, n_groups, "", "", ""));
+  std::vector<std::string> v;
+  TRY(checked_values(values, &v));
+  TRY(checked_mask("per-member", member_mask, (int)v.size()));
+  std::string err;
+  const RtcCode* code = nullptr;
+  const int rc = linear_group_pointwise_compile(v, tall_pad(ndims), group_size, member_mask, include_dir, &err, &code);
+  return rc ? mjhmc_fail(rc, err) : 0;
+}
+
+int mjhmc_pointwise_create_grouped(mjhmc_sampler* s, const char* values, unsigned lme_mask, unsigned member_mask,
+                                   const char* include_dir, mjhmc_pointwise** out) {
+  if (!s || !values || !include_dir || !out) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  const mjhmc_energy* e = s->en;
+  if (e->ep.kind != MJHMC_E_LINEAR_EXPR || !e->lin || !e->lin->grouped())
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED,
+                      std::string("the per-group statistics are those of the groups of a grouped linear model "
+                                  "(mjhmc_energy_create_linear_grouped): the sampler's energy is ") +
+                          (e->ep.kind == MJHMC_E_LINEAR_EXPR && e->lin
+                               ? "a linear model without groups, whose per-expert pass is mjhmc_pointwise_create"
+                               : std::string("MJHMC_E_") + energy_kind_name(e->ep.kind) +
+                                     ", which has no groups of experts to report on (mjhmc_pointwise_create is the pass of "
+                                     "the linear models without groups)"));
+  if (s->dtype != MJHMC_F64 && s->dtype != MJHMC_F32)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "linear models run with float32 or float64 state");
+  if (!s->ring) return acc_no_ring(nullptr);
+  std::vector<std::string> v;
+  TRY(checked_values(values, &v));
+  const int M = (int)v.size();
+  TRY(checked_mask("log-mean-exp", lme_mask, M));
+  TRY(checked_mask("per-member", member_mask, M));
+  const int P = e->pot_dim;
+  if (s->sh.pitch != P) return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the sampler's rows do not have the model's padded pitch");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  std::string err;
+  const RtcCode* code = nullptr;
+  const int rc = linear_group_pointwise_compile(v, P, e->lin->grp_C, member_mask, include_dir, &err, &code);
+  if (rc) return mjhmc_fail(rc, err);
+  const int cols = member_mask ? e->lin->grp_G * e->lin->grp_C : e->lin->grp_G;
+  return pw_new_handle(s, *code, M, lme_mask, P, e->lin->grp_nbg, cols, true, out);
 }
 
 int mjhmc_pointwise_destroy(mjhmc_pointwise* h) { return acc_destroy(h); }
@@ -242,9 +319,11 @@ int mjhmc_pointwise_accumulate(mjhmc_pointwise* h, int x_slot0, int w_slot0, int
     hipLaunchKernelGGL(pw_check_weights_kernel, dim3((unsigned)std::min<int64_t>(1024, ((int64_t)n * s->N + 255) / 256)), dim3(256),
                        0, s->stream, acc_weights(h, w_slot0), s->Npad, s->N, n, h->bad);
   const mjhmc_energy* e = s->en;
+  // lin_pointwise_kernel or lin_group_pointwise_kernel: the same arguments around the kernel's own model
   const mjhmc::LinTallModel tm{e->pot[0], e->pot[1], e->pot[2], h->nblk, s->D, h->K};
+  const mjhmc::LinGroupedModel gm{e->pot[0], e->pot[1], e->pot[2], e->lin->grp_nbg, e->lin->grp_nbp, s->D, e->lin->tall_K, e->lin->grp_G};
   const mjhmc::PotLinear lin = e->lin->gen.lin;
-  const size_t KP = (size_t)h->nblk * h->P;
+  const size_t KP = h->KP;
   const int64_t nitems = (int64_t)h->nstrips * h->nblk;
   const unsigned grid = (unsigned)std::min<int64_t>(nitems, std::max(1, s->ctx->prop.multiProcessorCount));
   for (int k = 0; k < n; ++k) {
@@ -264,7 +343,7 @@ int mjhmc_pointwise_accumulate(mjhmc_pointwise* h, int x_slot0, int w_slot0, int
     a.ntiles = h->ntiles;
     a.nstrips = h->nstrips;
     a.lme = h->lme;
-    void* params[] = {(void*)&a, (void*)&tm, (void*)&lin};
+    void* params[] = {(void*)&a, h->grouped ? (void*)&gm : (void*)&tm, (void*)&lin};
     HIPCHK(hipModuleLaunchKernel(h->fn, grid, 1, 1, 256, 1, 1, 0, s->stream, params, nullptr));
     hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)((h->K + 255) / 256)), dim3(256), 0, s->stream, h->part, h->partW,
                        h->nstrips, h->M, h->lme, KP, h->K, work);

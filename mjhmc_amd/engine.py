@@ -540,6 +540,13 @@ class DeviceSampler(object):
         ``log_mean_exp`` (one flag per value) asks.  The ring must exist (ring_alloc); another energy is refused."""
         return DevicePointwise(self, values, log_mean_exp)
 
+    def group_pointwise(self, values, log_mean_exp=None, per=None):
+        """Per-group ("per data row") sums of 1 .. 4 value expressions of a GROUPED linear-model energy over blocks of this
+        sampler's ring (mjhmc_pointwise_create_grouped): the values see ``lse``, ``sm`` and ``c`` beside ``u``, ``j``,
+        ``p[k]``, ``q[m]``; ``per`` gives each value's kind, 'group' (the default: summed over the group's members) or
+        'member'.  The ring must exist (ring_alloc); an energy that is not a grouped linear model is refused."""
+        return DevicePointwise(self, values, log_mean_exp, per=per, grouped=True)
+
     def influence(self, value, experts=None):
         """The cross moments of the state with one value h(u, j) per expert of a linear-model energy over blocks of this
         sampler's ring (mjhmc_influence_*): what Cov(x_d, h(u_j)) is made of.  ``experts``: (j0, j1), None for all.  The
@@ -690,6 +697,33 @@ def pointwise_check(ndims, nexperts, values):
                                                  _lib.KERNEL_HEADERS.encode()))
 
 
+GROUP_POINTWISE_KINDS = ('group', 'member')
+
+
+def group_pointwise_args(values, log_mean_exp=None, per=None):
+    """(the ';'-separated bytes of 1 .. 4 value expressions, the log-mean-exp bit mask, the per-member bit mask) of a
+    grouped DevicePointwise; ValueError as pointwise_args, and for a ``per`` that does not pair with the values or holds a
+    word other than 'group' / 'member' (None: every value per group)"""
+    exprs, lme = pointwise_args(values, log_mean_exp)
+    n = 1 if isinstance(values, str) else len(values)
+    kinds = ['group'] * n if per is None else ([per] if isinstance(per, str) else [str(k) for k in per])
+    if len(kinds) != n:
+        raise ValueError('per must have one kind per value (%d), got %d' % (n, len(kinds)))
+    for k in kinds:
+        if k not in GROUP_POINTWISE_KINDS:
+            raise ValueError("per: a value is per 'group' or per 'member', got %r" % (k,))
+    return exprs, lme, sum(1 << m for m, k in enumerate(kinds) if k == 'member')
+
+
+def group_pointwise_check(ndims, nexperts, groups, values, per=None):
+    """Compile the per-group kernel of an (ndims, nexperts) linear model with ``groups`` = (C, G) around ``values`` with no
+    device (mjhmc_pointwise_grouped_check); a refused or uncompilable expression raises ValueError with the compiler's
+    message."""
+    exprs, _, member = group_pointwise_args(values, None, per)
+    check_args(_lib.load().mjhmc_pointwise_grouped_check(int(ndims), int(nexperts), int(groups[0]), int(groups[1]), exprs,
+                                                         member, _lib.KERNEL_HEADERS.encode()))
+
+
 class DevicePointwise(_RingAccumulator):
     """Per expert j of a linear-model energy and per value m: W = sum w, S1 = sum w t, S2 = sum (w t) t and, where
     ``log_mean_exp`` asks, (mx, se) with mx = max t and se = sum w exp(t - mx), t = h_m(u_j, j) over the (slot, particle)
@@ -699,12 +733,27 @@ class DevicePointwise(_RingAccumulator):
     raises EngineError (status -5) and adds nothing."""
     _kind = 'pointwise'
 
-    def __init__(self, dev, values, log_mean_exp=None):
-        exprs, mask = pointwise_args(values, log_mean_exp)
-        self._create(dev, None, exprs, mask, _lib.KERNEL_HEADERS.encode(), checker=check_args)
+    def __init__(self, dev, values, log_mean_exp=None, per=None, grouped=False):
+        """``grouped``: the per-group pass of a grouped linear model (mjhmc_pointwise_create_grouped) with the kinds ``per``
+        of its values -- the same handle with columns in place of experts: ``nexperts`` is G C when a value is per member
+        and G otherwise, a per-group value fills the first G columns of its row and the rest read as empty"""
+        if grouped:
+            exprs, mask, member = group_pointwise_args(values, log_mean_exp, per)
+            self.member_mask = member
+            self._create_grouped(dev, exprs, mask, member)
+        else:
+            exprs, mask = pointwise_args(values, log_mean_exp)
+            self._create(dev, None, exprs, mask, _lib.KERNEL_HEADERS.encode(), checker=check_args)
         m, k, t = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
         self._call('info', ctypes.byref(m), ctypes.byref(k), ctypes.byref(t))
         self.n_values, self.nexperts, self.strip_tiles = int(m.value), int(k.value), int(t.value)
+
+    def _create_grouped(self, dev, exprs, mask, member):
+        self.dev, self.lib, self.on = dev, dev.lib, None
+        h = ctypes.c_void_p()
+        check_args(self.lib.mjhmc_pointwise_create_grouped(dev.handle, exprs, mask, member, _lib.KERNEL_HEADERS.encode(),
+                                                           ctypes.byref(h)), self.lib)
+        self.handle = h
 
     def read(self):
         """(W, S1 (M, K), S2 (M, K), lme_max (M, K), lme_sum (M, K), n_states)"""

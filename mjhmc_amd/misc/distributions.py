@@ -631,7 +631,8 @@ class MultinomialLogisticRegression(Distribution):
     kernel's); then the prior as C F more experts with rows I / prior_scale and f = u^2 / 2, selected by q[1] = 0 as
     GeneralizedLinearModel selects its prior.  ``E_host`` / ``dEdX_host`` are the same energy in float64 NumPy with a stable
     log-sum-exp; ``predict_proba(X)`` gives the class probabilities of ``features`` under coefficient vectors, on the
-    host.  ``gen_init_X`` draws N(0, init_scale^2) (from ``seed`` when given)."""
+    host; ``group_values()`` / ``log_lik_constants()`` are what ``sampler.group_waic()`` asks the data rows on the device.
+    ``gen_init_X`` draws N(0, init_scale^2) (from ``seed`` when given)."""
 
     def __init__(self, features, targets, n_classes, prior_scale=1.0, nbatch=100, init_scale=0.1, seed=None,
                  state_dtype='float64'):
@@ -679,6 +680,17 @@ class MultinomialLogisticRegression(Distribution):
     @property
     def n_data(self):
         return int(self.features.shape[0])
+
+    def group_values(self):
+        """(values, log_mean_exp flags, per) of ``sampler.group_pointwise()`` / ``group_waic()`` over the n data rows: value 0
+        is the row's log-likelihood u_y - LSE_c u_c, as q[0]*(u - lse) summed over the row's classes (q[0] one-hot: one
+        term is not zero), per group, with log-mean-exp on; value 1 is the softmax ``sm``, per member -- the fitted class
+        probabilities."""
+        return ['q[0]*(u - lse)', 'sm'], [True, False], ['group', 'member']
+
+    def log_lik_constants(self):
+        """the n per-row constants of log p(y_i | x) that value 0 of ``group_values()`` leaves out: none"""
+        return np.zeros(self.features.shape[0])
 
     def _logits(self, X):
         """(n, C, N): B a_i for every coefficient vector (column) of X"""

@@ -599,7 +599,9 @@ class PointwiseStatistics(object):
                                                             underflows; NaN in the rows that did not ask for it, -inf
                                                             for an expert that has seen no weight
 
-    plus ``n_states``, the number of (slot, particle) states, ``total_weight`` = W and ``flags`` (which rows asked)."""
+    plus ``n_states``, the number of (slot, particle) states, ``total_weight`` = W and ``flags`` (which rows asked).
+    ``group_pointwise()`` returns one of these per value, with the arrays of that value alone: (G,) per group, (G, C) per
+    member."""
 
     def __init__(self, W, S1, S2, lme_max, lme_sum, n_states, log_mean_exp):
         self.W, self.S1, self.S2, self.lme_max, self.lme_sum = float(W), S1, S2, lme_max, lme_sum
@@ -609,7 +611,11 @@ class PointwiseStatistics(object):
             self.mean = S1 / self.W
             self.var = np.maximum(S2 / self.W - self.mean * self.mean, 0.0)
             self.log_mean_exp = np.where(np.isneginf(lme_max), -np.inf, np.log(lme_sum / self.W) + lme_max)
-        self.log_mean_exp[~self.flags] = np.nan
+        if self.flags.size == 1:            # (one value, and the arrays may be its own: group_pointwise()'s (G,) and (G, C))
+            if not self.flags[0]:
+                self.log_mean_exp[...] = np.nan
+        else:
+            self.log_mean_exp[~self.flags] = np.nan
 
 
 class Waic(object):
@@ -655,7 +661,8 @@ def refuse_grouped(distribution, what, why):
 
 
 _GROUPED_PER_EXPERT = ('the per-expert passes report in the caller\'s order on terms that each see one u_j; a grouped model '
-                       'stores its experts in a permuted order and couples the members of a group')
+                       'stores its experts in a permuted order and couples the members of a group (its per-row pass is '
+                       'group_pointwise() / group_waic())')
 
 
 def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, compile_check=True):
@@ -685,6 +692,40 @@ def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, comp
         K, D = np.shape(params['W'])
         engine.pointwise_check(D, K, values)
     return values, flags
+
+
+def group_pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, per=None, compile_check=True):
+    """The checks ``group_pointwise()`` makes before anything runs, none of which needs a device: returns
+    (values, flags, per) or raises ValueError -- n_iter < 1, no value or more than 4, flags or ``per`` that do not pair with
+    the values, a kind other than 'group' / 'member', an energy that is not a linear model or is one without groups, an
+    expression that does not compile (with the compiler's message, mjhmc_pointwise_grouped_check)."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError('n_iter must be >= 1, got %d' % n_iter)
+    kind, params = distribution.device_energy()
+    if kind != _lib.E_LINEAR_EXPR:
+        names = dict((getattr(_lib, n), n[2:]) for n in dir(_lib) if n.startswith('E_') and isinstance(getattr(_lib, n), int))
+        raise ValueError('group_pointwise: the per-group statistics are those of a grouped linear-model energy (LINEAR_EXPR '
+                         'with groups: device_linear_grouped, MultinomialLogisticRegression); the energy of %s is %s'
+                         % (type(distribution).__name__, names.get(kind, kind)))
+    if not params.get('groups'):
+        raise ValueError('group_pointwise: the energy of %s is a linear model without groups (device_linear, '
+                         'device_linear_tall, GeneralizedLinearModel): its experts are its data rows and pointwise() / '
+                         'waic() report on them' % type(distribution).__name__)
+    if values is None:
+        if not hasattr(distribution, 'group_values'):
+            raise ValueError('group_pointwise: %s has no group_values(); pass values=' % type(distribution).__name__)
+        if log_mean_exp is not None or per is not None:
+            raise ValueError('log_mean_exp and per belong to values=: the distribution\'s own values carry theirs')
+        values, log_mean_exp, per = distribution.group_values()
+    values = [values] if isinstance(values, str) else [str(v) for v in values]
+    engine.group_pointwise_args(values, log_mean_exp, per)
+    flags = [False] * len(values) if log_mean_exp is None else [bool(f) for f in np.atleast_1d(log_mean_exp)]
+    per = ['group'] * len(values) if per is None else ([per] if isinstance(per, str) else [str(k) for k in per])
+    if compile_check:
+        K, D = np.shape(params['W'])
+        engine.group_pointwise_check(D, K, params['groups'], values, per)
+    return values, flags, per
 
 
 class Influence(object):
@@ -1434,6 +1475,69 @@ class HMCBase(object):
         n = const.shape[0]
         fitted = d.fitted_from_value(pw.mean[1, :n]) if hasattr(d, 'fitted_from_value') else None
         return Waic(pw, n, const, fitted)
+
+    def group_pointwise(self, n_iter, values=None, log_mean_exp=None, per=None, block=None):
+        """Statistics of the DATA ROWS of a grouped linear model (softmax regression: a row is a GROUP of C experts under a
+        log-sum-exp) over ``n_iter`` consecutive states of every particle -- what ``pointwise()`` is to the experts of the
+        other linear models.  The 1 .. 4 ``values`` are float32 C expressions at a grouped expert: they see what a
+        ``pointwise`` value sees (``u``, ``j`` = g C + c, ``p[k]``, ``q[m]``) and ``lse`` (the group's log-sum-exp, formed as
+        the energy forms it), ``sm`` (the member's softmax) and ``c`` (the member index).  ``per`` gives each value's kind:
+        'group' (the default) -- the float32 sum of the expression over the group's members in ascending c, one number per
+        row -- or 'member' -- one number per grouped expert.  The logits are formed on the matrix cores by the force's own
+        first GEMM and never stored (csrc/dense_lin_group_pointwise.hpp).  ``values=None`` takes
+        ``self.distribution.group_values()``.
+
+        Returns one ``PointwiseStatistics`` per value, in a list: the arrays of a per-group value have shape (G,), those of
+        a per-member value (G, C) -- row g the group, column c the member.  The plain experts behind the groups (a prior)
+        are not reported on.
+
+        The run is that of ``expectations(n_iter)``, exactly as for ``pointwise()``: the same iterations, weights,
+        counters, ``dwelling_times`` and final state, bit for bit; nothing is added to ``E_count`` / ``dEdX_count``; the
+        results do not depend on ``block``, bit for bit.
+
+        ValueError, before anything runs: n_iter < 1, no value or more than 4, flags or kinds that do not pair with the
+        values, an energy that is not a grouped linear model, an expression that does not compile (with the compiler's
+        message), a sharded sampler (summing over ranks is out of scope here)."""
+        values, flags, per = group_pointwise_request(self.distribution, n_iter, values, log_mean_exp, per)
+        n_iter = int(n_iter)
+        if self._comm is not None:
+            raise ValueError('group_pointwise: a sharded sampler (comm set) is not supported -- the sums are additive over '
+                             'ranks, but summing them is out of scope here')
+        C, G = (int(v) for v in self.distribution.device_energy()[1]['groups'])
+
+        def reserve():
+            # the handle's float32 rows are at most one slot; its partials are (strips x 4 M x columns) doubles
+            strips = (int(self.nbatch) + 1023) // 1024
+            return self._dev.ring_slot_bytes() + 32 * len(values) * (strips + 2) * (G * C + 512)
+
+        with self._RecordedRun(self, [n_iter], block, reserve_bytes=reserve) as run:
+            pw = run.own(self._dev.group_pointwise(values, flags, per))
+            for _, k in run.blocks():
+                pw.accumulate(0, k, w_slot0=run.w_slot0)
+            run.finish()
+            W, S1, S2, mx, se, n_states = pw.read()
+        out = []
+        for m, kind in enumerate(per):
+            shape, n = ((G, C), G * C) if kind == 'member' else ((G,), G)
+            out.append(PointwiseStatistics(W, *([a[m, :n].reshape(shape).copy() for a in (S1, S2, mx, se)] + [n_states, [flags[m]]])))
+        return out
+
+    def group_waic(self, n_iter, block=None):
+        """WAIC of a grouped model from ``group_pointwise(n_iter)`` with the distribution's own values
+        (``distribution.group_values()``): value 0 the log-likelihood of every data row (per group, log-mean-exp on), value 1
+        the fitted class probabilities (per member); the constants from ``distribution.log_lik_constants()``.  Returns a
+        ``Waic`` with ``n_data`` = G rows and ``fitted`` the (G, C) posterior-mean class probabilities; its ``pointwise`` is
+        value 0's statistics with the arrays as (1, G).  Definitions as for ``waic()``; the run is that of
+        ``group_pointwise(n_iter)``.  ValueError for a distribution without those two methods."""
+        d = self.distribution
+        if not (hasattr(d, 'group_values') and hasattr(d, 'log_lik_constants')):
+            raise ValueError('group_waic: %s has no group_values() / log_lik_constants() (MultinomialLogisticRegression has)'
+                             % type(d).__name__)
+        const = np.asarray(d.log_lik_constants(), dtype=np.float64)
+        ll, fit = self.group_pointwise(n_iter, block=block)[:2]
+        rows = PointwiseStatistics(ll.W, ll.S1[None, :], ll.S2[None, :], ll.lme_max[None, :], ll.lme_sum[None, :], ll.n_states,
+                                   ll.flags)
+        return Waic(rows, const.shape[0], const, fit.mean)
 
     def influence(self, n_iter, value=None, experts=None, block=None, shift=None):
         """How the DATA ROWS of a linear model move its coefficients, over ``n_iter`` consecutive states of every particle:

@@ -6,8 +6,8 @@
 Loads the test build of the library with MJHMC_RTC_KEEP=DIR (csrc/user_expr.hip: rtc_keep) and calls the device-free
 *_check entry points; every source hipRTC actually compiles lands in DIR under its file name and a running number, each
 followed by the lines that force its kernels' instantiation offline.  No GPU needed.  The list is fixed and walked in one
-order, so two libraries that generate the same texts leave byte-identical directories.  tools/pointwise_regs.py and
-tools/influence_regs.py take their sources through keep() below."""
+order, so two libraries that generate the same texts leave byte-identical directories.  tools/pointwise_regs.py,
+tools/group_pointwise_regs.py and tools/influence_regs.py take their sources through keep() below."""
 import argparse
 import ctypes
 import os
@@ -29,6 +29,9 @@ POINTWISE_SETS = {   # the value sets of the table of DESIGN.md section 3.3m
     'u, softplus': ['u', SOFTPLUS],
     '4 values': ['u', SOFTPLUS, 'expf(u)', 'q[0]*u*u'],
 }
+GROUP_POINTWISE_VALUES = ['q[0]*(u - lse)', 'sm']   # the table of DESIGN.md section 3.3o: a row's log-likelihood (per group,
+GROUP_POINTWISE_MEMBER = 2                          # log-mean-exp on) and the fitted class probabilities (per member)
+GROUP_SIZES = (2, 10, 16)
 INFLUENCE_VALUES = {'u': 'u', 'glm logistic l': LOGISTIC_L}   # those of the table of section 3.3n
 NB_DIMS = {1: 100, 2: 200, 4: 400}   # ndims that pads to 128 NB
 TALL_K = 600                         # more experts than a square model takes: the blocked layout
@@ -66,6 +69,9 @@ def instances():
     for values in POINTWISE_SETS.values():
         for nb, d in NB_DIMS.items():
             yield 'mjhmc_pointwise_check', d, TALL_K, ';'.join(values)
+    for c in GROUP_SIZES:
+        for nb, d in NB_DIMS.items():
+            yield 'mjhmc_pointwise_grouped_check', d, 40 * c + TALL_K, c, 40, ';'.join(GROUP_POINTWISE_VALUES), GROUP_POINTWISE_MEMBER
     for value in INFLUENCE_VALUES.values():
         for nb, d in NB_DIMS.items():
             yield 'mjhmc_influence_check', d, TALL_K, value
