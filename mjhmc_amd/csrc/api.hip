@@ -535,7 +535,7 @@ int mjhmc_sampler_destroy(mjhmc_sampler* s) {
   accumulators_free_all(s);
   timegrid_free_all(s);
   stein_free_all(s);
-  void* ptrs[] = {s->flf_list, s->call_block, s->Hpre, s->Hwork, s->cold_list, s->pot64_scratch, s->Hspec[0], s->Hspec[1], s->Hspec_dump, s->Gbuf[0], s->Gbuf[1], s->Xbuf[0], s->Xbuf[1], s->Vbuf[0],  s->Vbuf[1], s->EX[0],     s->EX[1],  s->EV[0],
+  void* ptrs[] = {s->flf_list, s->call_block, s->Hpre, s->Hwork, s->cold_list, s->Hspec[0], s->Hspec[1], s->Hspec_dump, s->Gbuf[0], s->Gbuf[1], s->Xbuf[0], s->Xbuf[1], s->Vbuf[0],  s->Vbuf[1], s->EX[0],     s->EX[1],  s->EV[0],
                   s->EV[1],   s->Hflf[0], s->Hflf[1],  s->dwell,  s->dwell_scratch,  s->trans,
                   s->ring,     s->dwell_ring, s->stage,  s->noise,  s->rexp,
                   s->runif,   s->scratch,  s->ck[0],    s->ck[1],    s->ck[2],   s->ck[3],  s->ck[4],
@@ -610,8 +610,6 @@ int mjhmc_sampler_create(mjhmc_ctx* ctx, mjhmc_energy* e, int64_t nparticles, in
           HIPCHK(hipMalloc((void**)&s->Hwork, s->Npad * ssize(s)));  // float32, or float64 for ProductOfT's float64 state
           HIPCHK(hipMemsetAsync(s->Hwork, 0, s->Npad * ssize(s), s->stream));   // (padding rows read it and ignore it)
           HIPCHK(hipMalloc((void**)&s->cold_list, (2 * s->Npad + 3 * kMaxDenseParts) * sizeof(int)));  // two lists (iterations alternate) + [part][3] counters
-          if (e->is_pot() && dtype == MJHMC_F64 && !e->pot_big() && !e->lin_tall())   // working rows of the tile kernel, one set per concurrent launch
-            HIPCHK(hipMalloc((void**)&s->pot64_scratch, (size_t)kMaxDenseParts * pot64_scratch_workgroups() * 2 * 32 * row_bytes(s)));
         }
         HIPCHK(hipMalloc(&s->Hspec[i], s->Npad * ssize(s)));
         HIPCHK(hipMemsetAsync(s->Hspec[i], 0xFF, s->Npad * ssize(s), s->stream));   // NaN: nothing handed on

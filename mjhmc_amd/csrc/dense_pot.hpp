@@ -207,7 +207,6 @@ inline void pot_launch_generated(hipFunction_t f, unsigned grid, hipStream_t st,
   void* params[] = {(void*)&a, (void*)&mdl, (void*)&lin};
   (void)hipModuleLaunchKernel(f, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
 }
-int pot64_scratch_workgroups();  // workgroups a pot64 launch may run: rows of Pot64JumpArgs::scratch to provide per launch
 #endif
 
 }  // namespace mjhmc

@@ -3,22 +3,18 @@
 //
 //   V += (-eps/2) * dEdX ;  X += eps * V ;  dEdX = float64( force32( float32(X) ) ) ;  V += (-eps/2) * dEdX     (hmc_state.py:86-91)
 //
-// The tile kernel of dense_pot.hip keeps X, V as float32 accumulator tiles in registers.  Here they live in HBM / MALL
-// as float64 rows and never as register tiles: the wave's 128 registers of x / v tiles become the STAGING registers of
-// a streamed epilogue.  After the second GEMM of a gradient the wave walks its accumulator (dE/dX, float32) in four
-// chunks of 16 elements per lane: load the float64 V and X elements of the chunk (the next chunk's loads are in flight
-// while this one is worked on), V += c g (twice between two drifts: the closing half kick of a step and the opening one
-// of the next are two roundings, as in the reference), X += eps V in float64, store both, and write float32(X) straight
-// into the LDS B-fragment image the first GEMM of the next gradient reads.  dE/dX stays float32 (the reference's force
-// output, widened exactly where the reference assigns it into its float64 dEdX array, hmc_state.py:52-53).
+// The tile kernel of dense_pot.hip keeps X, V as float32 accumulator tiles in registers.  Here they are float64 tiles in
+// registers for the whole trajectory (2 x 128 registers at NB = 4; the GEMMs run with half-chunk A-row sets there to make
+// the room: dense_pot_tile.hpp, gemm_dim_half).  After the second GEMM of a gradient the wave walks its accumulator (dE/dX,
+// float32) in four chunks of 16 elements per lane: V += c g (twice between two drifts: the closing half kick of a step
+// and the opening one of the next are two roundings, as in the reference), X += eps V in float64, and float32(X) goes
+// straight into the LDS B-fragment image the first GEMM of the next gradient reads.  dE/dX stays float32 (the reference's
+// force output, widened exactly where the reference assigns it into its float64 dEdX array, hmc_state.py:52-53).
 //
-// Working copy: between the passes of a trajectory the wave's X and V elements live in a per-workgroup scratch (2 x 32
-// rows = 256 KB per workgroup, 64 MB per launch: MALL-resident) in LANE-LINEAR 16-byte pieces, so the per-step passes are
-// fully coalesced (see Work<NB>); the particle rows are read at the start of a trajectory and written at its end only,
-// staged through the idle B-operand images in LDS so that those accesses are coalesced too (staged_start, staged_end_*).  A particle that takes the L move is finished when the trajectory is; one that does not
-// gets its pre-move rows copied over at the end.
-// Traffic: 32 particles x 512 dims x 8 B x (X, V) x (read + write) = 512 KB per tile and leapfrog step = 3.5 B/clk/CU
-// beside ~146 000 cycles of gradient; at the CU's 64 B/clk vector-memory port that is 8 192 cycles per step.
+// The particle rows are read at the start of a trajectory and written at its end only, staged through the idle B-operand
+// images in LDS so that those accesses are coalesced (staged_start, staged_end_*); a leapfrog step touches no state in
+// memory.  A particle that takes the L move is finished when the trajectory is; one that does not gets its pre-move rows
+// copied over at the end.
 //
 // Same operations in the same order as the multi-pass path this replaces on the sampling path (host_energy.hip:
 // hk_pot_kick_drift / pot_eval_kernel) and the same GEMM code: results are bit-identical to it
@@ -136,8 +132,6 @@ static int resident_cus64() {
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   return std::max(1, cus);
 }
-
-int pot64_scratch_workgroups() { return resident_cus64(); }
 
 template <int NB, int MODE>
 static void launch64_mode(const Pot64JumpArgs& a, const PotModel& mdl, unsigned grid, hipStream_t st, const PotGenerated* gen) {

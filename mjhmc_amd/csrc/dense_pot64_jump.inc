@@ -16,10 +16,9 @@
   // live across every GEMM loop and streamed pass of the kernel: [0..3] counts, [4] some particle met a non-finite rate
   __shared__ unsigned tally[5];
   if (threadIdx.x < 5) tally[threadIdx.x] = 0;
-  AReg<NB> ar;
+  AReg64<NB> ar;
   areg_load<NB>(mdl, w, c, h, ar);
   stage_bias<NB>(mdl, sh.s);
-  const Work<NB> wk = work_of<NB>(a.scratch, blockIdx.x, w, lane);
   for (int64_t item = blockIdx.x; item < nft + a.ntiles; item += gridDim.x) {
     const bool inverse = item < nft;   // (uniform over the workgroup)
     [[maybe_unused]] const int istamp_item = (int)(item / gridDim.x) & 15;   // (the timing build's POT_ISTAMP)
@@ -32,18 +31,18 @@
     };
     // (everything that is not needed during the trajectory -- the scalars of the decision, the output rows' addresses --
     // is fetched / formed after it: the kernel sits at its 512-register budget, and what is live across the GEMM loops
-    // and the streamed passes decides whether those spill; tools/check_isa.sh gates both.  That includes the column's own
+    // and the per-step passes decides whether those spill; tools/check_isa.sh gates both.  That includes the column's own
     // index: it is looked up again behind the trajectory, through an item number the compiler cannot see through)
     Tile<NB> g;
-    VTile<NB> v;
+    VTile<NB> v, x;
     float exl = 0.f;
     double EVL;
     {
       const int64_t p = column_of(item);
       POT_ISTAMP(0);
-      staged_start<NB>(sh.s, wk, a.X_in, a.V_in, a.G_in, p, w, c, h, g, v, inverse);
+      staged_start<NB>(sh.s, a.X_in, a.V_in, a.G_in, p, w, c, h, g, v, x, inverse);
       POT_ISTAMP(1);
-      EVL = pot64_trajectory<NB>(mdl, xp, ar, sh, w, c, h, lane, wk, g, v, a.L, a.eps, a.chalf, &exl);
+      EVL = pot64_trajectory<NB>(mdl, xp, ar, sh, w, c, h, lane, g, v, x, a.L, a.eps, a.chalf, &exl);
       POT_ISTAMP(2);
     }
     int64_t item_again = item;
@@ -51,9 +50,9 @@
     const int64_t p = column_of(item_again);
     const bool alive = p < a.N;
     const size_t roff = (size_t)p * (128 * NB) + 32 * NB * w + 4 * NB * h;
-    // the end point's position: into the output rows -- an inverse-L item's is wanted by nobody and stays in the working
-    // copy (its last list tile is padded with a repeated column: two lanes' rows would be the same row)
-    if (!inverse) staged_end_x<NB>(sh.s, wk, a.X_out, p, w, c, h);
+    // the end point's position: into the output rows -- an inverse-L item's is wanted by nobody and is dropped (its last
+    // list tile is padded with a repeated column: two lanes' rows would be the same row)
+    if (!inverse) staged_end_x<NB>(sh.s, a.X_out, p, w, c, h, x);
     POT_ISTAMP(3);
     const double EXL = (double)exl;
     const double HL = EXL + EVL;

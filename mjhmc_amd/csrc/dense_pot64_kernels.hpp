@@ -1,4 +1,4 @@
-// The float64-state tile kernel's building blocks (the reference's arithmetic: float64 rows streamed through the epilogue
+// The float64-state tile kernel's building blocks (the reference's arithmetic: float64 register tiles integrated in the epilogue
 // around the float32 force; dense_pot64.hip has the design), the trajectory templated on the experts of the force
 // (dense_pot_tile.hpp).  The kernel's body is the fragment dense_pot64_jump.inc, included inside the kernel definition:
 // ProductOfT's pot64_jump_kernel in dense_pot64.hip, a linear-model energy's in linear_energy.hip's hipRTC unit.
@@ -61,6 +61,13 @@ __device__ __forceinline__ void dv_store(double* lrow, int q, const typename DVe
   *reinterpret_cast<typename DVecN<NB>::type*>(lrow + q_off<NB>(q)) = v;
 }
 
+// A rows per register set of the GEMMs (dense_pot_tile.hpp): NB = 4 runs the half-depth form, gemm_dim_half -- its 64
+// registers are what lets the position live in registers; NB = 1, 2 have registers to spare and keep whole chunks
+template <int NB>
+constexpr int kA64 = NB == 4 ? 8 : 16;
+template <int NB>
+using AReg64 = AReg<NB, kA64<NB>>;
+
 constexpr int kPark = 8;   // momentum elements per lane that sit out the GEMM loops in LDS (see pot64_trajectory)
 template <int NB>
 struct Shared64 {
@@ -70,70 +77,8 @@ struct Shared64 {
   f32x4 park[kPark / 2][256];
 };
 
-// The wave's working copy of its X and V elements between the passes of a trajectory, in the workgroup's scratch
-// (2 x 32 x DIM float64): LANE-LINEAR pieces [wave][array][piece][lane] of 16 bytes (8 at NB = 1), so every access of the
-// per-step passes is 64 lanes x 16 B = 1 KB contiguous.  In the particle-major rows themselves a wave instruction
-// touches 64 different 128-byte lines (lane = particle, 4 KB apart): the address pipe takes ~64 cycles per instruction
-// and, with 128 of them per wave and step, a first form that integrated in the rows spent 40 000 cycles per step there
-// (C3 21.3 ms instead of 16.6).  Rows are touched once per trajectory, read and written through LDS (staged_start,
-// staged_end_x, staged_end_vg).
-// Accesses go through a buffer resource: scalar base + the lane's constant offset + a scalar piece offset.
-template <int NB>
-struct Work {
-  static constexpr int PB = NB == 1 ? 8 : 16;        // piece bytes
-  static constexpr int PQ = NB * 8 / PB;             // pieces per register index
-  static constexpr unsigned kArea = 16u * PQ * 64u * PB;  // one wave's X (or V) elements: 8192 NB bytes
-  __amdgpu_buffer_rsrc_t rs;
-  unsigned voff;   // the lane's piece inside the wave's area: w * kArea + lane * PB (vector register)
-  static constexpr unsigned xb = 0;   // X areas of the four waves, then (kept for a momentum working copy) the V areas
-  static constexpr unsigned vb = 4 * kArea;
-};
-template <int NB>
-__device__ __forceinline__ Work<NB> work_of(double* scratch, unsigned wg, int w, int lane) {
-  Work<NB> k;
-  char* base = (char*)scratch + (size_t)wg * (8 * Work<NB>::kArea);
-  k.rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 8 * Work<NB>::kArea, 0x00020000);
-  // (the wave index is threadIdx-derived: a vector value to the compiler.  In the scalar offset of a buffer access it
-  // would force a readfirstlane loop around every load and store)
-  k.voff = (unsigned)w * Work<NB>::kArea + (unsigned)lane * Work<NB>::PB;
-  return k;
-}
 using uvec4 = __attribute__((ext_vector_type(4))) unsigned;
-using uvec2 = __attribute__((ext_vector_type(2))) unsigned;
 using f64x2 = __attribute__((ext_vector_type(2))) double;
-template <int NB>
-__device__ __forceinline__ typename DVecN<NB>::type wk_load(const Work<NB>& k, unsigned area, int q) {
-  if constexpr (NB == 1) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(k.rs, k.voff, area + (unsigned)q * 512u, 0));
-  } else if constexpr (NB == 2) {
-    return __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(k.rs, k.voff, area + (unsigned)q * 1024u, 0));
-  } else {
-    const f64x2 lo = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(k.rs, k.voff, area + (unsigned)q * 2048u, 0));
-    const f64x2 hi = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(k.rs, k.voff, area + (unsigned)q * 2048u + 1024u, 0));
-    typename DVecN<4>::type v;
-    v[0] = lo[0];
-    v[1] = lo[1];
-    v[2] = hi[0];
-    v[3] = hi[1];
-    return v;
-  }
-}
-template <int NB>
-__device__ __forceinline__ void wk_store(const Work<NB>& k, unsigned area, int q, const typename DVecN<NB>::type& v) {
-  if constexpr (NB == 1) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uvec2, v), k.rs, k.voff, area + (unsigned)q * 512u, 0);
-  } else if constexpr (NB == 2) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, v), k.rs, k.voff, area + (unsigned)q * 1024u, 0);
-  } else {
-    f64x2 lo, hi;
-    lo[0] = v[0];
-    lo[1] = v[1];
-    hi[0] = v[2];
-    hi[1] = v[3];
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, lo), k.rs, k.voff, area + (unsigned)q * 2048u, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, hi), k.rs, k.voff, area + (unsigned)q * 2048u + 1024u, 0);
-  }
-}
 
 // The particle rows at the two ends of a trajectory, staged through the B-operand images (Shared<NB>::pub: 32 KB x NB,
 // exactly the tile's 32 rows of DIM float64), which are idle there.  Read in the lanes' own accumulator layout a wave
@@ -149,6 +94,14 @@ template <>
 struct PieceOf<1> {
   using type = unsigned long long;
 };
+// A lane constant the compiler must form where it is used.  The staging addresses below are functions of the thread
+// index alone: hoisted out of the kernel's item loop they are ~45 values held across every trajectory, and the kernel has
+// no register for them (they went to scratch, each reload awaited on its own in front of its LDS access); formed in place
+// they are two vector instructions per piece.
+__device__ __forceinline__ int here(int lane_const) {
+  asm volatile("" : "+v"(lane_const));
+  return lane_const;
+}
 template <int NB>
 struct Stage {
   using P = typename PieceOf<NB>::type;
@@ -166,7 +119,7 @@ template <int NB>
 __device__ __forceinline__ void stage_rows_in(const double* rows, int64_t p, char* img) {
   using S = Stage<NB>;
   using P = typename S::P;
-  const int t = threadIdx.x;
+  const int t = here(threadIdx.x);
 #pragma unroll 1
   for (int i0 = 0; i0 < S::K; i0 += S::KB) {
     P buf[S::KB];
@@ -188,7 +141,7 @@ template <int NB>
 __device__ __forceinline__ void stage_rows_out(double* rows, int64_t p, const char* img) {
   using S = Stage<NB>;
   using P = typename S::P;
-  const int t = threadIdx.x;
+  const int t = here(threadIdx.x);
 #pragma unroll 1
   for (int i0 = 0; i0 < S::K; i0 += S::KB) {
 #pragma unroll
@@ -240,31 +193,27 @@ __device__ __forceinline__ char* stage_image(Shared<NB>& s) {
   return reinterpret_cast<char*>(&s.pub[0][0]);
 }
 
-// the wave's momentum elements, float64, in registers for the whole trajectory (accumulator layout: 2 x 16 NB registers)
+// the wave's elements of a float64 state array in registers for the whole trajectory (accumulator layout: 2 x 16 NB
+// registers): the momentum and the position
 template <int NB>
 struct VTile {
   double b[NB][16];
 };
 
-// One kick / drift pass over this wave's elements of the tile.  The momentum stays in registers; the position is
-// streamed through registers from the working copy in four chunks of four register indices (double buffered: chunk
-// n + 1 is in flight while chunk n is worked on).
+// One kick / drift pass over this wave's elements of the tile, in registers alone:
 //   NKICK = 1: v = v + c g                          (the first step of a trajectory: v holds [-]V_in, staged_start)
 //   NKICK = 2: v = (v + c g) + c g                  (closing half kick of a step, opening one of the next)
-//   x = X + eps v ;  store x to the working copy ;  float32(x) -> the X image of GEMM 1
-// (the last drift's X is the end point: the caller takes it from the working copy, staged_end_x)
+//   x = x + eps v ;  float32(x) -> this lane's slot of the X image of GEMM 1
+// (the last drift's x is the end point: staged_end_x takes it to the rows)
 // Every product is rounded before its sum (the library is built with -ffp-contract=off): NumPy's V += c * g.
+// (A form that streamed the position through a per-workgroup working copy in memory, 128 KB in and out per step at
+// NB = 4, took ~6 000 cycles per pass: DESIGN.md 3.4b.)
 template <int NB, int NKICK>
-__device__ __forceinline__ void kick_drift_pass(const Work<NB>& wk, const Tile<NB>& g, VTile<NB>& v, double c, double eps,
+__device__ __forceinline__ void kick_drift_pass(const Tile<NB>& g, VTile<NB>& v, VTile<NB>& x, double c, double eps,
                                                 PubWave<NB>* pub0, int w, int lane) {
-  using DV = typename DVecN<NB>::type;
-  DV xa[4], xb[4];
-  auto load4 = [&](int q4, DV(&x)[4]) {
 #pragma unroll
-    for (int qq = 0; qq < 4; ++qq) x[qq] = wk_load<NB>(wk, wk.xb, 4 * q4 + qq);
-  };
-  // the momentum first: it needs no memory, so it runs while the X loads are in flight
-  auto kick4 = [&](int q4) {
+  for (int q4 = 0; q4 < 4; ++q4) {
+    f32x4 px[NB];
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq) {
       const int q = 4 * q4 + qq;
@@ -275,57 +224,15 @@ __device__ __forceinline__ void kick_drift_pass(const Work<NB>& wk, const Tile<N
         vv = vv + t;
         if constexpr (NKICK == 2) vv = vv + t;
         v.b[r][q] = vv;
-      }
-    }
-  };
-  auto drift4 = [&](int q4, DV(&x)[4]) {
-    f32x4 px[NB];
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      const int q = 4 * q4 + qq;
-#pragma unroll
-      for (int r = 0; r < NB; ++r) {
-        const double xx = dget<NB>(x[qq], r) + eps * v.b[r][q];
-        dset<NB>(x[qq], r, xx);
+        const double xx = x.b[r][q] + eps * vv;
+        x.b[r][q] = xx;
         px[r][qq] = (float)xx;
       }
-      wk_store<NB>(wk, wk.xb, q, x[qq]);
     }
-    if constexpr (NB == 4) {
-      // this lane's slot of the X image, formed from the working copy's lane offset (which every load and store of the
-      // pass holds in a register anyway): voff = w * 32 KB + lane * 16 -> w * 16 KB + lane * 16.  As a loop-invariant
-      // address it was one more value held -- in scratch -- across the GEMM loops, and its reload in front of the first
-      // publish of a pass stood behind an s_waitcnt vmcnt(0) that drained the pass's loads.
-      unsigned off = ((wk.voff >> 1) & 0xFFFFC000u) | (wk.voff & 0x3FFu);
-      asm volatile("" : "+v"(off));
-      char* img = reinterpret_cast<char*>(pub0) + off;
 #pragma unroll
-      for (int r = 0; r < NB; ++r) *reinterpret_cast<f32x4*>(img + (size_t)(r * 4 + q4) * 1024) = px[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < NB; ++r) pub0[w].v[r][q4][lane] = px[r];
-    }
-  };
-  // (Measured: all four kick4 first, in the shadow of the first X loads, then the drifts -- more registers live across
-  // the pass, 119 -> 283 spilled, C3 in this arithmetic 17.6 -> 18.7 ms.)
-  load4(0, xa);
-  load4(1, xb);
-  __builtin_amdgcn_sched_barrier(0);
-  kick4(0);
-  drift4(0, xa);
-  __builtin_amdgcn_sched_barrier(0);
-  load4(2, xa);
-  __builtin_amdgcn_sched_barrier(0);
-  kick4(1);
-  drift4(1, xb);
-  __builtin_amdgcn_sched_barrier(0);
-  load4(3, xb);
-  __builtin_amdgcn_sched_barrier(0);
-  kick4(2);
-  drift4(2, xa);
-  __builtin_amdgcn_sched_barrier(0);
-  kick4(3);
-  drift4(3, xb);
+    for (int r = 0; r < NB; ++r) pub0[w].v[r][q4][lane] = px[r];
+    __builtin_amdgcn_sched_barrier(0);   // chunk by chunk: what is live beside the tiles stays one chunk's temporaries
+  }
 }
 
 // The closing half kick of the trajectory, v += c g, and this lane's part of sum(v^2)
@@ -355,18 +262,22 @@ __device__ __forceinline__ double column_sum(SH& sh, int w, int c, int h, double
   return tot;
 }
 
-// The start of a trajectory: the tile's rows (p: this lane's column's particle) through the staging image -- X into the
-// working copy, the stored dE/dX (float64 rows holding float32 values) into g, [-]V into v (neg: the F of F L F).
+// The start of a trajectory: the tile's rows (p: this lane's column's particle) through the staging image -- X into
+// x, the stored dE/dX (float64 rows holding float32 values) into g, [-]V into v (neg: the F of F L F).
 // Barriers: the image is free on entry (the caller's last read of it stands behind a barrier) and on return.
 template <int NB>
-__device__ __forceinline__ void staged_start(Shared<NB>& s, const Work<NB>& wk, const double* xin, const double* vin,
-                                             const double* gin, int64_t p, int w, int c, int h, Tile<NB>& g, VTile<NB>& v,
-                                             bool neg) {
+__device__ __forceinline__ void staged_start(Shared<NB>& s, const double* xin, const double* vin, const double* gin, int64_t p,
+                                             int w, int c, int h, Tile<NB>& g, VTile<NB>& v, VTile<NB>& x, bool neg) {
   char* img = stage_image<NB>(s);
+  c = here(c), w = here(w), h = here(h);
   stage_rows_in<NB>(xin, p, img);
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) wk_store<NB>(wk, wk.xb, q, stage_get<NB>(img, w, c, h, q));
+  for (int q = 0; q < 16; ++q) {
+    const typename DVecN<NB>::type xx = stage_get<NB>(img, w, c, h, q);
+#pragma unroll
+    for (int r = 0; r < NB; ++r) x.b[r][q] = dget<NB>(xx, r);
+  }
   __syncthreads();
   stage_rows_in<NB>(gin, p, img);
   __syncthreads();
@@ -388,13 +299,19 @@ __device__ __forceinline__ void staged_start(Shared<NB>& s, const Work<NB>& wk, 
   __syncthreads();
 }
 
-// Rows out through the staging image: the end point's position (from the working copy, where the last drift left it),
-// its momentum, its dE/dX.  Barriers as staged_start's.
+// Rows out through the staging image: the end point's position (the tile the last drift left), its momentum, its
+// dE/dX.  Barriers as staged_start's.
 template <int NB>
-__device__ __forceinline__ void staged_end_x(Shared<NB>& s, const Work<NB>& wk, double* xout, int64_t p, int w, int c, int h) {
+__device__ __forceinline__ void staged_end_x(Shared<NB>& s, double* xout, int64_t p, int w, int c, int h, const VTile<NB>& x) {
   char* img = stage_image<NB>(s);
+  c = here(c), w = here(w), h = here(h);
 #pragma unroll
-  for (int q = 0; q < 16; ++q) stage_put<NB>(img, w, c, h, q, wk_load<NB>(wk, wk.xb, q));
+  for (int q = 0; q < 16; ++q) {
+    typename DVecN<NB>::type xx;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) dset<NB>(xx, r, x.b[r][q]);
+    stage_put<NB>(img, w, c, h, q, xx);
+  }
   __syncthreads();
   stage_rows_out<NB>(xout, p, img);
   __syncthreads();
@@ -404,6 +321,7 @@ __device__ __forceinline__ void staged_end_vg(Shared<NB>& s, double* vout, doubl
                                               const VTile<NB>& v, const Tile<NB>& g) {
   using DV = typename DVecN<NB>::type;
   char* img = stage_image<NB>(s);
+  c = here(c), w = here(w), h = here(h);
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     DV vv;
@@ -426,23 +344,23 @@ __device__ __forceinline__ void staged_end_vg(Shared<NB>& s, double* vout, doubl
   __syncthreads();
 }
 
-// L >= 1 leapfrog steps (hmc_state.py:86-100) from the position in the working copy, the momentum in v and the stored
-// dE/dX in g (staged_start).  On return the end point's position is in the working copy (staged_end_x takes it to the
-// rows), its momentum in v, g holds its dE/dX (float32), *ex its energy (float32, from the last gradient's u), and the
-// return value is its kinetic energy sum(V^2) / 2 (all lanes of column c).
+// L >= 1 leapfrog steps (hmc_state.py:86-100) from the position in x, the momentum in v and the stored dE/dX in g
+// (staged_start).  On return the end point's position is in x (staged_end_x takes it to the rows), its momentum in v,
+// g holds its dE/dX (float32), *ex its energy (float32, from the last gradient's u), and the return value is its
+// kinetic energy sum(V^2) / 2 (all lanes of column c).
 template <int NB, class XP>
-__device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP& xp, AReg<NB>& ar, Shared64<NB>& sh, int w, int c, int h,
-                                                   int lane, const Work<NB>& wk, Tile<NB>& g, VTile<NB>& v, int L, double eps,
+__device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP& xp, AReg64<NB>& ar, Shared64<NB>& sh, int w, int c, int h,
+                                                   int lane, Tile<NB>& g, VTile<NB>& v, VTile<NB>& x, int L, double eps,
                                                    double chalf, float* ex) {
   PubWave<NB>* pub0 = sh.s.pub[0];   // the X images of the four waves (this wave's: pub0[w])
-  kick_drift_pass<NB, 1>(wk, g, v, chalf, eps, pub0, w, lane);
+  kick_drift_pass<NB, 1>(g, v, x, chalf, eps, pub0, w, lane);
   for (int s = 0; s < L; ++s) {
     [[maybe_unused]] const int stamp_slot = s;
     POT_STAMP(0);
-    // The momentum (32 NB registers) is not touched by the gradient, whose GEMM loops run at the register budget: the
-    // allocator spills a few of its elements across them and reloads them inside the streamed pass, where a scratch
-    // reload is a counted load whose wait drains the pass's own loads.  A few elements sit the gradient out in LDS
-    // instead (lane-linear, conflict-free; an LDS wait drains nothing).
+    // Neither the momentum nor the position (2 x 32 NB registers) is touched by the gradient, whose GEMM loops run at
+    // the register budget.  A few momentum elements sit the gradient out in LDS (lane-linear, conflict-free): without
+    // them the allocator keeps as many values in scratch across the whole trajectory (the bench instance: 33 spilled
+    // registers, a step 700 cycles longer, nearly all of it in GEMM 2: 70 140 against 69 480; with them: none).
     if constexpr (NB == 4) {
 #pragma unroll
       for (int k = 0; k < kPark / 2; ++k) {
@@ -461,14 +379,14 @@ __device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP
         v.b[NB - 1][14 - 2 * k] = two[1];
       }
       // (whatever the allocator still keeps of the momentum in scratch across the GEMM loops comes back HERE, in front of
-      // the pass's loads, not between them)
+      // the pass, not inside it)
 #pragma unroll
       for (int r = 0; r < NB; ++r)
 #pragma unroll
         for (int q = 0; q < 16; ++q) use_here(v.b[r][q]);
     }
     POT_STAMP(6);
-    if (s < L - 1) kick_drift_pass<NB, 2>(wk, g, v, chalf, eps, pub0, w, lane);
+    if (s < L - 1) kick_drift_pass<NB, 2>(g, v, x, chalf, eps, pub0, w, lane);
     POT_STAMP(7);
   }
   const double part = closing_kick<NB>(g, v, chalf);

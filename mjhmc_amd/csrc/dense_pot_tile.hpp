@@ -106,13 +106,13 @@ __device__ __forceinline__ void publish(PubWave<NB>& dst, int lane, const Tile<N
 // The k-range is walked in 4*NB chunks of 16 k-pairs (one published block (ws, r) each).  With one wave
 // per SIMD nothing else hides the L2 latency of the A rows, so they are software-pipelined by hand:
 // chunk n+1's sixteen A loads are issued (and fenced against sinking) before chunk n's 16*NB MFMAs start.
-template <int NB>
-__device__ __forceinline__ void a_chunk_load(const float* mlane, int chunk, typename VecN<NB>::type (&dst)[16]) {
+template <int NB, int AQ = 16>   // AQ: the chunk's first AQ rows (8: its first half, gemm_dim_half)
+__device__ __forceinline__ void a_chunk_load(const float* mlane, int chunk, typename VecN<NB>::type (&dst)[AQ]) {
   using V = typename VecN<NB>::type;
   constexpr int DIM = 128 * NB;
   const float* base = mlane + (size_t)(32 * NB * (chunk / NB) + (chunk % NB)) * DIM;
 #pragma unroll
-  for (int q = 0; q < 16; ++q) dst[q] = *reinterpret_cast<const V*>(base + (size_t)(NB * ((q & 3) + 8 * (q >> 2))) * DIM);
+  for (int q = 0; q < AQ; ++q) dst[q] = *reinterpret_cast<const V*>(base + (size_t)(NB * ((q & 3) + 8 * (q >> 2))) * DIM);
 }
 
 // The same through a buffer resource: address = scalar base + the lane's constant 32-bit offset (VGPR) + the row's scalar
@@ -220,22 +220,76 @@ __device__ __forceinline__ void gemm_dim(const float* __restrict__ M, const floa
   }
 }
 
+// The half-depth form of the above (the float64-state kernel at NB = 4, which needs the registers for its position
+// tile): the two register sets hold HALF a chunk each -- eight A rows, 8 NB registers -- and the next half-chunk's rows
+// are requested one per group of NB MFMAs while this half-chunk's are multiplied: the same spread issue pattern, half
+// the prefetch distance (8 NB MFMAs).  Every accumulator element receives its k-terms in the same order as in gemm_dim
+// (chunk by chunk, q = 0..15, r = 0..NB-1): the results are the same bits.
+//   half_mfma_ld: the MFMAs of half HALF of `chunk` from a[8]; aload[j] <- row j of half NHALF of the chunk at cbase
+template <int NB, int HALF, int NHALF>
+__device__ __forceinline__ void half_mfma_ld(const f32x4* bbase, int chunk, int lane, const typename VecN<NB>::type (&a)[8],
+                                             f32x4& bnext, Tile<NB>& acc, __amdgpu_buffer_rsrc_t rs, unsigned lane_bytes,
+                                             unsigned cbase, typename VecN<NB>::type (&aload)[8]) {
+  constexpr int NG = 16 * NB, DIM = 128 * NB;
+#pragma unroll
+  for (int q4 = 2 * HALF; q4 < 2 * HALF + 2; ++q4) {
+    const f32x4 b4 = bnext;
+    const int t = 4 * chunk + q4 + 1;
+    bnext = bbase[(size_t)(t < NG ? t : NG - 1) * 64 + lane];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      const int j = 4 * (q4 - 2 * HALF) + qq, qn = 8 * NHALF + j;   // this half's row j; the row requested meanwhile
+#pragma unroll
+      for (int r = 0; r < NB; ++r)
+        acc.b[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(vget<NB>(a[j], r), b4[qq], acc.b[r], 0, 0, 0);
+      aload[j] = buf_load<NB>(rs, lane_bytes, cbase + (unsigned)(NB * ((qn & 3) + 8 * (qn >> 2)) * DIM * 4));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// a0 enters holding the first half of chunk 0 of M and leaves holding the first half of chunk 0 of Mnext
+template <int NB>
+__device__ __forceinline__ void gemm_dim_half(const float* __restrict__ M, const float* __restrict__ Mnext, const PubWave<NB>* pub,
+                                              int w, int c, int h, int lane, typename VecN<NB>::type (&a0)[8], Tile<NB>& acc) {
+  constexpr int DIM = 128 * NB, NCH = 4 * NB;
+  const size_t lane_off = (size_t)(4 * NB * h) * DIM + 32 * NB * w + NB * c;
+  const unsigned lane_bytes = (unsigned)(lane_off * sizeof(float));
+  const __amdgpu_buffer_rsrc_t rM = a_rsrc<NB>(M), rN = a_rsrc<NB>(Mnext);
+  const f32x4* bbase = &pub[0].v[0][0][0];
+  typename VecN<NB>::type a1[8];
+  f32x4 bnext = bbase[lane];
+  auto cbase_of = [](int ch) { return (unsigned)(32 * NB * (ch / NB) + (ch % NB)) * (unsigned)(DIM * 4); };
+#pragma unroll 1
+  for (int chunk = 0; chunk < NCH; chunk += 2) {
+    // two chunks = four half-chunks per trip, as gemm_dim's (one code path; selects, no branch)
+    const bool more = chunk + 2 < NCH;
+    const int c1 = chunk + 1, c2 = more ? chunk + 2 : 0;
+    half_mfma_ld<NB, 0, 1>(bbase, chunk, lane, a0, bnext, acc, rM, lane_bytes, cbase_of(chunk), a1);
+    half_mfma_ld<NB, 1, 0>(bbase, chunk, lane, a1, bnext, acc, rM, lane_bytes, cbase_of(c1), a0);
+    half_mfma_ld<NB, 0, 1>(bbase, c1, lane, a0, bnext, acc, rM, lane_bytes, cbase_of(c1), a1);
+    half_mfma_ld<NB, 1, 0>(bbase, c1, lane, a1, bnext, acc, more ? rM : rN, lane_bytes, cbase_of(c2), a0);
+  }
+}
+
 // ndims <= 128 (NB = 1): a wave's rows of BOTH pre-scaled matrices are 2 x 64 floats per lane -- they stay in
 // registers for the whole kernel (the workgroup's 4 x 64 lanes x 128 VGPRs hold W1 and W2T completely), so a
 // leapfrog step issues no global load at all.  This is the size of the reference's own ProductOfT experiments
 // (36 dims, <= 1000 particles): a handful of tiles, one per CU, where nothing else could hide the A-row latency.
-template <int NB>
+template <int NB, int AQ = 16>
 struct AReg {  // NB > 1: chunk 0 of the matrix the NEXT GEMM reads (the GEMMs alternate W1, W2T, W1, ...), loaded ahead
-  typename VecN<NB>::type a0[16];
+  typename VecN<NB>::type a0[AQ];   // AQ = 16: the whole chunk (gemm_dim); 8: its first half (gemm_dim_half)
 };
-template <>
-struct AReg<1> {
+template <int AQ>
+struct AReg<1, AQ> {
   float w1[4][16];
   float w2[4][16];
 };
 
-template <int NB>
-__device__ __forceinline__ void areg_load(const PotModel& mdl, int w, int c, int h, AReg<NB>& ar) {
+template <int NB, int AQ>
+__device__ __forceinline__ void areg_load(const PotModel& mdl, int w, int c, int h, AReg<NB, AQ>& ar) {
   if constexpr (NB == 1) {
     const float* m1 = mdl.W1 + (size_t)(4 * h) * 128 + 32 * w + c;
     const float* m2 = mdl.W2T + (size_t)(4 * h) * 128 + 32 * w + c;
@@ -245,12 +299,12 @@ __device__ __forceinline__ void areg_load(const PotModel& mdl, int w, int c, int
       a_chunk_load<1>(m2, chunk, ar.w2[chunk]);
     }
   } else {
-    a_chunk_load<NB>(mdl.W1 + (size_t)(4 * NB * h) * (128 * NB) + 32 * NB * w + NB * c, 0, ar.a0);
+    a_chunk_load<NB, AQ>(mdl.W1 + (size_t)(4 * NB * h) * (128 * NB) + 32 * NB * w + NB * c, 0, ar.a0);
   }
 }
 
-template <int NB, bool SECOND>
-__device__ __forceinline__ void gemm_any(const PotModel& mdl, AReg<NB>& ar, const PubWave<NB>* pub, int w, int c,
+template <int NB, bool SECOND, int AQ>
+__device__ __forceinline__ void gemm_any(const PotModel& mdl, AReg<NB, AQ>& ar, const PubWave<NB>* pub, int w, int c,
                                          int h, int lane, Tile<NB>& acc) {
   if constexpr (NB == 1) {
     // k-rows at or beyond ndims (== nbasis) are padding: X, phi(U) and the matrix rows are exactly zero there, so the
@@ -270,6 +324,8 @@ __device__ __forceinline__ void gemm_any(const PotModel& mdl, AReg<NB>& ar, cons
         }
       }
     }
+  } else if constexpr (AQ == 8) {
+    gemm_dim_half<NB>(SECOND ? mdl.W2T : mdl.W1, SECOND ? mdl.W1 : mdl.W2T, pub, w, c, h, lane, ar.a0, acc);
   } else {
     gemm_dim<NB>(SECOND ? mdl.W2T : mdl.W1, SECOND ? mdl.W1 : mdl.W2T, pub, w, c, h, lane, ar.a0, acc);
   }
@@ -352,8 +408,8 @@ struct PotExperts {
 // follows its last read of it).
 // pot_gradient_published: the same from the barrier on -- the caller has written its part of the X image
 // (sh.pub[0][w], publish()'s layout) already.
-template <int NB, class XP>
-__device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, const XP& xp, AReg<NB>& ar, Shared<NB>& sh, int w, int c, int h,
+template <int NB, class XP, int AQ>
+__device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, const XP& xp, AReg<NB, AQ>& ar, Shared<NB>& sh, int w, int c, int h,
                                                        int lane, Tile<NB>& g, bool want_energy, float* energy_out,
                                                        int stamp_slot = 0) {
   __syncthreads();

@@ -125,7 +125,6 @@ struct mjhmc_sampler {
   float* Hwork = nullptr;              // dense energies: H of the inverse-L proposals an iteration integrates
   int* cold_list = nullptr;            // + the compacted lists of those particles (two of Npad entries, iterations alternate; then
                                        //   kMaxDenseParts x 3 rotating counters)
-  double* pot64_scratch = nullptr;     // ProductOfT, float64 state: working rows, one set per concurrent launch (kMaxDenseParts)
   void* Hspec[2] = {nullptr, nullptr}; // dense energies, MJHMC: H(L proposal) of the particles that then moved by F (NaN elsewhere):
                                        //   next iteration's H of their inverse-L proposal, bit for bit (dense_pot.hip); follows scur
   void* Hspec_dump = nullptr;          // (test build, MJHMC_NO_FSPEC: where the hand-over goes instead, so that nothing is ever handed on)

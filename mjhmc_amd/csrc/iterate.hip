@@ -400,8 +400,6 @@ static A part_args(const A& a, int64_t start, int64_t n, int64_t npad, size_t pi
       h.G_in = a.G_in + (size_t)start * pitch;
       h.G_out = a.G_out + (size_t)start * pitch;
     }
-    if constexpr (A::kScratch)  // the float64 tile kernel's working rows: one set per concurrent launch
-      h.scratch = a.scratch + (size_t)which * pot64_scratch_workgroups() * 2 * 32 * (size_t)pitch;
   }
   h.N = n;
   h.Npad = npad;
@@ -750,7 +748,6 @@ static void launch_dense_iteration(const mjhmc_sampler* s, const Parts& parts, c
   d.Hspec_in = (const H*)s->Hspec[si];
   d.Hspec_out = (H*)(spec_out ? spec_out : s->Hspec[si ^ 1]);
   d.rescan = spec_out ? 1 : 0;
-  if constexpr (A::kScratch) d.scratch = s->pot64_scratch;
   for (int k = 0; k < parts.n; ++k) {
     A h = part_args(d, parts.start(k), parts.count(s, k), parts.npad(s, k), (size_t)s->sh.pitch, k, s->cold_list + 2 * s->Npad);
     h.ntiles = dense_ntiles(s, h.N, h.Npad);

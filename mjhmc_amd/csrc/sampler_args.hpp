@@ -156,7 +156,7 @@ struct JumpDecideArgs {
 // The argument blocks of the dense tile kernels: ProductOfT (POT; dense_pot.hip, float32 rows; dense_pot64.hip, the
 // reference's float64 rows around the float32 force) and SparseImageCode (dense_sic.hip, bfloat16 or float32 rows).  S: the
 // type of the stored state rows (and of `noise`, G_in / G_out); H: the per-particle scalars and the step parameters.
-// A field a family does not have (G_in / G_out and D: ProductOfT only; scratch: float64 ProductOfT only) is a NoField that
+// A field a family does not have (G_in / G_out and D: ProductOfT only) is a NoField that
 // takes no room, so that every family's block keeps its own layout (the kernels' scalar loads and registers follow it).
 struct NoField {};
 template <bool HAS, typename F>
@@ -172,11 +172,11 @@ using FieldIf = typename FieldIfT<HAS, F>::type;
 
 template <typename S, typename H, bool POT>
 struct DenseJumpArgs {
-  static constexpr bool kPot = POT, kScratch = POT && sizeof(S) == 8;
+  static constexpr bool kPot = POT;
   const S* X_in;
   const S* V_in;
   [[no_unique_address]] FieldIf<POT, const S*> G_in;  // dE/dX at X_in (HMCState.dEdX, hmc_state.py:36-39); float64 rows: float32 values widened (:52-53)
-  S* X_out;            // (float64 ProductOfT: also the working rows of the trajectory)
+  S* X_out;
   S* V_out;
   [[no_unique_address]] FieldIf<POT, S*> G_out;
   const H* EX_in;
@@ -200,7 +200,6 @@ struct DenseJumpArgs {
   const S* noise;      // replay normals [N][pitch] or nullptr
   const double* rexp;  // replay unit exponentials [3][N] or nullptr
   const double* runif; // replay uniforms of the discrete-time samplers [2N+1] (accept, flip, R gate) or nullptr
-  [[no_unique_address]] FieldIf<kScratch, double*> scratch;  // [workgroups][2][32][dim] working rows of the inverse-L pass (pot64_scratch_workgroups())
   Control* ctl;
   unsigned long long* stats;
   int64_t N, Npad, ntiles, first_pid;

@@ -13,9 +13,9 @@
 # and, for the ProductOfT tile kernels (dense_pot.hip: float32 state; dense_pot64.hip: the reference's arithmetic), that the
 # two GEMM loop bodies of every kernel (the basic blocks that hold the 128 MFMAs of two chunks) contain no scratch_
 # instruction -- a spill reload inside the loop is a counted load whose wait drains the A-row prefetch; the epilogues may
-# spill -- and, in dense_pot64.hip, that the per-step kick / drift pass (the block that streams the position through
-# registers: >= 16 buffer loads and >= 16 buffer stores of the working copy) contains none either; with the VGPR / spill
-# figures of every instance.
+# spill -- and, in dense_pot64.hip, that the per-step kick / drift pass (the blocks that drift the register-resident
+# position and round it to float32 for GEMM 1: >= 16 v_add_f64 and >= 16 v_cvt_f32_f64, no MFMA) contains none either;
+# with the VGPR / spill figures of every instance.
 # Compile flags: the Makefile's own (make print-flags).
 # usage: tools/check_isa.sh [out.s]        exit status 1 on a violation
 set -u
@@ -104,20 +104,16 @@ for name, body in re.findall(r'^(_ZN5mjhmc\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel'
     gemm = [b for b in blocks if sum('v_mfma' in x for x in b) >= 64]
     n_scr = sum(sum(re.match(r'\s*scratch_', x) is not None for x in b) for b in gemm)
     n_acc = sum(sum('v_accvgpr' in x for x in b) for b in gemm)
-    # the float64-state kernel's per-step kick / drift passes: the blocks that stream the position through registers
-    # (>= 16 buffer loads of the working copy and as many stores)
-    # (the pass that stores the end point's position to the particle rows instead runs once per trajectory: not gated)
-    passes = [b for b in blocks if sum('buffer_load' in x for x in b) >= 16 and sum('buffer_store' in x for x in b) >= 16
+    # the float64-state kernel's kick / drift passes: the blocks that drift the position tile and round it to float32
+    # for the X image (>= 16 v_add_f64 and as many v_cvt_f32_f64; the first pass of a trajectory may share its block with
+    # the end of the row staging)
+    passes = [b for b in blocks if sum('v_add_f64' in x for x in b) >= 16 and sum('v_cvt_f32_f64' in x for x in b) >= 16
               and not any('v_mfma' in x for x in b)]
     p_scr = sum(sum(re.match(r'\s*scratch_', x) is not None for x in b) for b in passes)
     m = meta.get(name, {})
     hot = 'Li4E' in name and 'jump_kernel' in name
     tag = ''
-    # (one or two folded reloads of a lane constant in a pass are tolerated: the allocator moves them around with every
-    # change to the kernel; momentum elements reloaded inside the pass -- a handful of them, each behind a vmcnt(0) -- are not)
-    # scratch reloads tolerated in the streamed per-step pass, per instance (what each one has TODAY: a regression of a
-    # clean instance fails; the allocator's one or two folded lane-constant reloads of the others are pinned at their count)
-    allow = {'pot64_jump_kernelILi4ELb0ELi0EE': 1, 'pot64_jump_kernelILi4ELb1ELi0EE': 1}.get(re.sub(r'^_ZN5mjhmc\d+', '', name).split('Ev')[0], 0)
+    allow = 0    # scratch accesses tolerated in a pass: none
     new_kernels = any(t in name for t in ('pot_fix_kernel', 'pot64_decide_kernel'))
     if (hot and (n_scr or p_scr > allow or len(gemm) < 2 or ('pot64' in name and not passes))) or (new_kernels and m.get('scratch')):
         bad += 1
@@ -125,7 +121,7 @@ for name, body in re.findall(r'^(_ZN5mjhmc\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel'
     if gemm:
         print('%-84s vgpr %3s spilled %3s scratch %4s B sgpr spills %3s | GEMM loop bodies %d: scratch_ %d (v_accvgpr %d)%s%s'
               % (name[9:93], m.get('vgpr'), m.get('vgpr_spill'), m.get('scratch'), m.get('sgpr_spill'), len(gemm), n_scr, n_acc,
-                 (' | streamed passes %d: scratch_ %d' % (len(passes), p_scr)) if 'pot64' in name else '', tag))
+                 (' | kick / drift passes %d: scratch_ %d' % (len(passes), p_scr)) if 'pot64' in name else '', tag))
 print('check_isa %s: %s' % (sys.argv[2], 'FAILED: %d kernel(s)' % bad if bad else 'ok'))
 sys.exit(1 if bad else 0)
 PY
