@@ -208,7 +208,8 @@ struct VTile {
 // Every product is rounded before its sum (the library is built with -ffp-contract=off): NumPy's V += c * g.
 // (A form that streamed the position through a per-workgroup working copy in memory, 128 KB in and out per step at
 // NB = 4, took ~6 000 cycles per pass: DESIGN.md 3.4b.)
-template <int NB, int NKICK>
+// DONE: elements q < DONE (a multiple of four) of blocks 0 .. NB - 2 have had their pass already (StepTail)
+template <int NB, int NKICK, int DONE = 0>
 __device__ __forceinline__ void kick_drift_pass(const Tile<NB>& g, VTile<NB>& v, VTile<NB>& x, double c, double eps,
                                                 PubWave<NB>* pub0, int w, int lane) {
 #pragma unroll
@@ -219,6 +220,7 @@ __device__ __forceinline__ void kick_drift_pass(const Tile<NB>& g, VTile<NB>& v,
       const int q = 4 * q4 + qq;
 #pragma unroll
       for (int r = 0; r < NB; ++r) {
+        if (r < NB - 1 && q < DONE) continue;
         const double t = c * (double)g.b[r][q];
         double vv = v.b[r][q];
         vv = vv + t;
@@ -230,10 +232,49 @@ __device__ __forceinline__ void kick_drift_pass(const Tile<NB>& g, VTile<NB>& v,
       }
     }
 #pragma unroll
-    for (int r = 0; r < NB; ++r) pub0[w].v[r][q4][lane] = px[r];
+    for (int r = 0; r < NB; ++r)
+      if (!(r < NB - 1 && 4 * q4 < DONE)) pub0[w].v[r][q4][lane] = px[r];
     __builtin_amdgcn_sched_barrier(0);   // chunk by chunk: what is live beside the tiles stays one chunk's temporaries
   }
 }
+
+// The middle steps' pass under GEMM 2's last MFMAs (dense_pot_tile.hpp: half_mfma_tail, NoTail): block rb's dE/dX is
+// final while blocks rb + 1 .. NB - 1 still accumulate, so its elements are kicked, drifted, rounded and written to the X
+// image between their MFMAs -- kPass elements per gap, the same operations on the same values as kick_drift_pass<NB, 2>.
+// Block NB - 1 (whose parked momentum is in LDS meanwhile) and what the gaps do not hold stay behind the GEMM:
+// kick_drift_pass<NB, 2, kDone>.  kPhi: the same for phi under GEMM 1.
+template <bool B>
+struct Flag {   // a compile-time switch passed as an argument
+  static constexpr bool value = B;
+};
+
+template <int NB>
+struct StepTail {
+  static constexpr bool kOn = true, kFill = true;
+  static constexpr int kPhi = 1, kPass = 1;
+  static constexpr int kDone = 8 * kPass;
+  VTile<NB>& v;
+  VTile<NB>& x;
+  double c, eps;
+  PubWave<NB>& pubw;  // this wave's X image
+  int lane;
+  f32x4& px;          // the quad being collected
+  __device__ __forceinline__ void pass_slice(const Tile<NB>& g, int rb, int j) const {
+#pragma unroll
+    for (int e = 0; e < kPass; ++e) {
+      const int q = kPass * j + e;
+      const double t = c * (double)g.b[rb][q];
+      double vv = v.b[rb][q];
+      vv = vv + t;
+      vv = vv + t;
+      v.b[rb][q] = vv;
+      const double xx = x.b[rb][q] + eps * vv;
+      x.b[rb][q] = xx;
+      px[q & 3] = (float)xx;
+      if ((q & 3) == 3) pubw.v[rb][q >> 2][lane] = px;
+    }
+  }
+};
 
 // The closing half kick of the trajectory, v += c g, and this lane's part of sum(v^2)
 template <int NB>
@@ -353,7 +394,49 @@ __device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP
                                                    int lane, Tile<NB>& g, VTile<NB>& v, VTile<NB>& x, int L, double eps,
                                                    double chalf, float* ex) {
   PubWave<NB>* pub0 = sh.s.pub[0];   // the X images of the four waves (this wave's: pub0[w])
+  constexpr bool kTail = XP::kProductOfT && NB == 4 && kA64<NB> == 8;   // per-step vector work under the GEMMs' tails
   kick_drift_pass<NB, 1>(g, v, x, chalf, eps, pub0, w, lane);
+  if constexpr (kTail) {
+    // The middle steps and the last one apart: the last gradient has no pass behind it and wants the energy.  (One loop
+    // with the work under the tails behind a branch on the step number per MFMA gap: 140 spilled registers.)
+    // TAIL: a middle step's gradient, phi and the pass of the finished blocks under the GEMMs' last MFMAs (StepTail).
+    // The momentum elements of kPark sit it out in LDS, as below.
+    auto gradient = [&](auto tail, [[maybe_unused]] int stamp_slot) {
+      POT_STAMP(0);
+#pragma unroll
+      for (int k = 0; k < kPark / 2; ++k) {
+        f64x2 two;
+        two[0] = v.b[NB - 1][15 - 2 * k];
+        two[1] = v.b[NB - 1][14 - 2 * k];
+        sh.park[k][threadIdx.x] = __builtin_bit_cast(f32x4, two);
+      }
+      if constexpr (decltype(tail)::value) {
+        f32x4 px;
+        pot_gradient_published<NB>(mdl, xp, ar, sh.s, w, c, h, lane, g, false, ex, stamp_slot,
+                                   StepTail<NB>{v, x, chalf, eps, pub0[w], lane, px});
+      } else {
+        pot_gradient_published<NB>(mdl, xp, ar, sh.s, w, c, h, lane, g, true, ex, stamp_slot, BlockTail());
+      }
+#pragma unroll
+      for (int k = 0; k < kPark / 2; ++k) {
+        const f64x2 two = __builtin_bit_cast(f64x2, sh.park[k][threadIdx.x]);
+        v.b[NB - 1][15 - 2 * k] = two[0];
+        v.b[NB - 1][14 - 2 * k] = two[1];
+      }
+#pragma unroll
+      for (int r = 0; r < NB; ++r)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) use_here(v.b[r][q]);
+      POT_STAMP(6);
+    };
+    for (int s = 0; s < L - 1; ++s) {
+      gradient(Flag<true>{}, s);
+      kick_drift_pass<NB, 2, StepTail<NB>::kDone>(g, v, x, chalf, eps, pub0, w, lane);
+      [[maybe_unused]] const int stamp_slot = s;
+      POT_STAMP(7);
+    }
+    gradient(Flag<false>{}, L - 1);
+  } else {
   for (int s = 0; s < L; ++s) {
     [[maybe_unused]] const int stamp_slot = s;
     POT_STAMP(0);
@@ -388,6 +471,7 @@ __device__ __forceinline__ double pot64_trajectory(const PotModel& mdl, const XP
     POT_STAMP(6);
     if (s < L - 1) kick_drift_pass<NB, 2>(g, v, x, chalf, eps, pub0, w, lane);
     POT_STAMP(7);
+  }
   }
   const double part = closing_kick<NB>(g, v, chalf);
   return column_sum<NB>(sh, w, c, h, part) / 2.0;

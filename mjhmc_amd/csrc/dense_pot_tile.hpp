@@ -274,6 +274,65 @@ __device__ __forceinline__ void gemm_dim_half(const float* __restrict__ M, const
   }
 }
 
+// The GEMM's LAST half-chunk block by block (r outer, the half's eight rows inner: 8 NB MFMAs from one register set and
+// the half's two B quads), so that block r is final 8 (NB - 1 - r) MFMAs before the GEMM ends and the per-step vector
+// work of the finished blocks can issue between the MFMAs of the remaining ones: fill(rb, j) runs behind MFMA j of
+// block rb + 1 and holds block rb's slice j.  With one wave per SIMD nothing else issues in those gaps.  Only the order
+// among blocks changes; every accumulator element still receives chunk 0..4 NB - 1, row 0..15 in that order: the same
+// bits.  The next GEMM's first half-set is requested one row per four MFMAs, as everywhere else.
+template <int NB, class Fill>
+__device__ __forceinline__ void half_mfma_tail(const f32x4* bbase, int chunk, int lane, const typename VecN<NB>::type (&a)[8],
+                                               const f32x4 bfirst, Tile<NB>& acc, __amdgpu_buffer_rsrc_t rs, unsigned lane_bytes,
+                                               unsigned cbase, typename VecN<NB>::type (&aload)[8], Fill&& fill) {
+  constexpr int DIM = 128 * NB;
+  static_assert(NB == 4, "one A request per four MFMAs fills the next half-set in exactly 8 NB MFMAs at NB = 4");
+  const f32x4 bq[2] = {bfirst, bbase[(size_t)(4 * chunk + 3) * 64 + lane]};
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      acc.b[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(vget<NB>(a[j], r), bq[j >> 2][j & 3], acc.b[r], 0, 0, 0);
+      if ((j & 3) == 0) {
+        const int qn = 2 * r + (j >> 2);   // row qn of the next GEMM's first half-set
+        aload[qn] = buf_load<NB>(rs, lane_bytes, cbase + (unsigned)(NB * ((qn & 3) + 8 * (qn >> 2)) * DIM * 4));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (r > 0) {
+        fill(r - 1, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+}
+
+// gemm_dim_half with its last trip written out and that trip's last half-chunk in the block-ordered form
+template <int NB, class Fill>
+__device__ __forceinline__ void gemm_dim_half_tail(const float* __restrict__ M, const float* __restrict__ Mnext, const PubWave<NB>* pub,
+                                                   int w, int c, int h, int lane, typename VecN<NB>::type (&a0)[8], Tile<NB>& acc,
+                                                   Fill&& fill) {
+  constexpr int DIM = 128 * NB, NCH = 4 * NB;
+  const size_t lane_off = (size_t)(4 * NB * h) * DIM + 32 * NB * w + NB * c;
+  const unsigned lane_bytes = (unsigned)(lane_off * sizeof(float));
+  const __amdgpu_buffer_rsrc_t rM = a_rsrc<NB>(M), rN = a_rsrc<NB>(Mnext);
+  const f32x4* bbase = &pub[0].v[0][0][0];
+  typename VecN<NB>::type a1[8];
+  f32x4 bnext = bbase[lane];
+  auto cbase_of = [](int ch) { return (unsigned)(32 * NB * (ch / NB) + (ch % NB)) * (unsigned)(DIM * 4); };
+#pragma unroll 1
+  for (int chunk = 0; chunk < NCH - 2; chunk += 2) {
+    const int c1 = chunk + 1, c2 = chunk + 2;
+    half_mfma_ld<NB, 0, 1>(bbase, chunk, lane, a0, bnext, acc, rM, lane_bytes, cbase_of(chunk), a1);
+    half_mfma_ld<NB, 1, 0>(bbase, chunk, lane, a1, bnext, acc, rM, lane_bytes, cbase_of(c1), a0);
+    half_mfma_ld<NB, 0, 1>(bbase, c1, lane, a0, bnext, acc, rM, lane_bytes, cbase_of(c1), a1);
+    half_mfma_ld<NB, 1, 0>(bbase, c1, lane, a1, bnext, acc, rM, lane_bytes, cbase_of(c2), a0);
+  }
+  half_mfma_ld<NB, 0, 1>(bbase, NCH - 2, lane, a0, bnext, acc, rM, lane_bytes, cbase_of(NCH - 2), a1);
+  half_mfma_ld<NB, 1, 0>(bbase, NCH - 2, lane, a1, bnext, acc, rM, lane_bytes, cbase_of(NCH - 1), a0);
+  half_mfma_ld<NB, 0, 1>(bbase, NCH - 1, lane, a0, bnext, acc, rM, lane_bytes, cbase_of(NCH - 1), a1);
+  half_mfma_tail<NB>(bbase, NCH - 1, lane, a1, bnext, acc, rN, lane_bytes, cbase_of(0), a0, fill);
+}
+
 // ndims <= 128 (NB = 1): a wave's rows of BOTH pre-scaled matrices are 2 x 64 floats per lane -- they stay in
 // registers for the whole kernel (the workgroup's 4 x 64 lanes x 128 VGPRs hold W1 and W2T completely), so a
 // leapfrog step issues no global load at all.  This is the size of the reference's own ProductOfT experiments
@@ -408,47 +467,103 @@ struct PotExperts {
 // follows its last read of it).
 // pot_gradient_published: the same from the barrier on -- the caller has written its part of the X image
 // (sh.pub[0][w], publish()'s layout) already.
-template <int NB, class XP, int AQ>
+// The GEMMs' form and a caller's per-step vector work under their last MFMAs (half_mfma_tail): a type TL, the form
+// chosen at compile time.  TL::kOn: both GEMMs end block by block (ProductOfT's own experts with half-chunk A sets at
+// NB = 4 only; everything else ignores TL).  TL::kFill: this is one of a trajectory's MIDDLE gradients -- a pass follows
+// it and the energy is not wanted -- and the finished blocks' work runs between the remaining blocks' MFMAs:
+//   kPhi                  elements of a finished block whose phi is taken per MFMA gap of GEMM 1 (1 or 2)
+//   pass_slice(g, rb, j)  block rb's slice j of the caller's pass, run behind MFMA j of block rb + 1 of GEMM 2
+// The gradient that wants the energy keeps the whole-tile stage behind GEMM 1: its float32 sum runs q outer, r inner.
+struct NoTail {
+  static constexpr bool kOn = false, kFill = false;
+};
+struct BlockTail {   // the block-ordered GEMM tails with nothing under them
+  static constexpr bool kOn = true, kFill = false;
+};
+
+template <int NB, class XP, int AQ, class TL = NoTail>
 __device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, const XP& xp, AReg<NB, AQ>& ar, Shared<NB>& sh, int w, int c, int h,
                                                        int lane, Tile<NB>& g, bool want_energy, float* energy_out,
-                                                       int stamp_slot = 0) {
+                                                       int stamp_slot = 0, TL tl = TL()) {
+  constexpr bool kTail = TL::kOn && XP::kProductOfT && NB == 4 && AQ == 8;
+  constexpr bool kFill = kTail && TL::kFill;
   __syncthreads();
   POT_STAMP(1);
   Tile<NB> u;
   rowvec_load<NB>(sh.cb, w, h, u);                     // u starts at b_j / nu_j (LDS copy, stage_bias)
-  gemm_any<NB, false>(mdl, ar, sh.pub[0], w, c, h, lane, u);   // + sum_d W[d][j]/nu_j * x_d
-  POT_STAMP(2);
-  if constexpr (XP::kProductOfT) {
-    // ProductOfT's experts written out in place: with the stage behind the expert type's member functions hipcc scheduled
-    // the built-in kernels differently; this is their original text
-    if (want_energy) {                                   // E = sum_j alpha_j log(1 + u_j^2)  (distributions.py:430-432)
-      using V = typename VecN<NB>::type;
-      const float* al = mdl.alpha + 32 * NB * w;
-      float s = 0.f;
+  if constexpr (kTail) {                               // + sum_d W[d][j]/nu_j * x_d
+    [[maybe_unused]] f32x4 hq;                         // the quad of phi values being collected
+    gemm_dim_half_tail<NB>(mdl.W1, mdl.W2T, sh.pub[0], w, c, h, lane, ar.a0, u, [&]([[maybe_unused]] int rb, [[maybe_unused]] int j) {
+      if constexpr (kFill) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const V a4 = *reinterpret_cast<const V*>(al + NB * acc_row(q, h));
-#pragma unroll
-        for (int r = 0; r < NB; ++r) s += vget<NB>(a4, r) * logf(1.0f + u.b[r][q] * u.b[r][q]);
+        for (int e = 0; e < TL::kPhi; ++e) {
+          const int q = TL::kPhi * j + e;
+          float uu = u.b[rb][q];
+          asm volatile("" : "+v"(uu));                 // one element at a time: not packed beside the MFMAs
+          hq[q & 3] = uu * __builtin_amdgcn_rcpf(1.0f + uu * uu);
+          if ((q & 3) == 3) sh.pub[1][w].v[rb][q >> 2][lane] = hq;
+        }
       }
-      const float part = half_sum(s);
-      if (h == 0) sh.red[0][w][c] = part;
-    }
+    });
+  } else {
+    gemm_any<NB, false>(mdl, ar, sh.pub[0], w, c, h, lane, u);
+  }
+  POT_STAMP(2);
+  if constexpr (kFill) {
+    // what the gaps did not hold: block NB - 1, and the other blocks' elements from DONE on.  The same phi, element by element
+    static_assert(TL::kPhi == 1 || TL::kPhi == 2, "whole quads of a block per eight gaps");
+    constexpr int DONE = 8 * TL::kPhi;
 #pragma unroll
     for (int r = 0; r < NB; ++r)
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float uu = u.b[r][q];
-        u.b[r][q] = uu * __builtin_amdgcn_rcpf(1.0f + uu * uu);   // phi(u) (v_rcp_f32: 1 ulp); the factor (nu+1)/nu lives in W2T
+      for (int q4 = (r < NB - 1 ? DONE / 4 : 0); q4 < 4; ++q4) {
+        f32x4 v4;
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+          const float uu = u.b[r][4 * q4 + qq];
+          v4[qq] = uu * __builtin_amdgcn_rcpf(1.0f + uu * uu);
+        }
+        sh.pub[1][w].v[r][q4][lane] = v4;
       }
   } else {
-    if (want_energy) {                                 // E = sum_j f(u_j, j)
-      const float part = half_sum(xp.template energy_sum<NB>(u, w, h));
-      if (h == 0) sh.red[0][w][c] = part;
+    if constexpr (XP::kProductOfT) {
+      // ProductOfT's experts written out in place: with the stage behind the expert type's member functions hipcc scheduled
+      // the built-in kernels differently; this is their original text
+      if (want_energy) {                                   // E = sum_j alpha_j log(1 + u_j^2)  (distributions.py:430-432)
+        using V = typename VecN<NB>::type;
+        int we = w, he = h, ce = c;
+        if constexpr (kTail) {   // the lane's addresses formed HERE: hoisted, they are held (or spilled) across every step
+          asm volatile("" : "+v"(we));
+          asm volatile("" : "+v"(he));
+          asm volatile("" : "+v"(ce));
+        }
+        const float* al = mdl.alpha + 32 * NB * we;
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const V a4 = *reinterpret_cast<const V*>(al + NB * acc_row(q, he));
+#pragma unroll
+          for (int r = 0; r < NB; ++r) s += vget<NB>(a4, r) * logf(1.0f + u.b[r][q] * u.b[r][q]);
+        }
+        const float part = half_sum(s);
+        if (he == 0) sh.red[0][we][ce] = part;
+      }
+#pragma unroll
+      for (int r = 0; r < NB; ++r)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float uu = u.b[r][q];
+          u.b[r][q] = uu * __builtin_amdgcn_rcpf(1.0f + uu * uu);   // phi(u) (v_rcp_f32: 1 ulp); the factor (nu+1)/nu lives in W2T
+        }
+    } else {
+      if (want_energy) {                                 // E = sum_j f(u_j, j)
+        const float part = half_sum(xp.template energy_sum<NB>(u, w, h));
+        if (h == 0) sh.red[0][w][c] = part;
+      }
+      xp.template phi<NB>(u, w, h);
     }
-    xp.template phi<NB>(u, w, h);
+    publish<NB>(sh.pub[1][w], lane, u);
   }
-  publish<NB>(sh.pub[1][w], lane, u);
   POT_STAMP(3);
   __syncthreads();
   POT_STAMP(4);
@@ -456,7 +571,13 @@ __device__ __forceinline__ void pot_gradient_published(const PotModel& mdl, cons
   for (int r = 0; r < NB; ++r)
 #pragma unroll
     for (int q = 0; q < 16; ++q) g.b[r][q] = 0.f;
-  gemm_any<NB, true>(mdl, ar, sh.pub[1], w, c, h, lane, g);
+  if constexpr (kTail) {
+    gemm_dim_half_tail<NB>(mdl.W2T, mdl.W1, sh.pub[1], w, c, h, lane, ar.a0, g, [&]([[maybe_unused]] int rb, [[maybe_unused]] int j) {
+      if constexpr (kFill) tl.pass_slice(g, rb, j);
+    });
+  } else {
+    gemm_any<NB, true>(mdl, ar, sh.pub[1], w, c, h, lane, g);
+  }
   POT_STAMP(5);
   if (want_energy && energy_out) {
     *energy_out = sh.red[0][0][c] + sh.red[0][1][c] + sh.red[0][2][c] + sh.red[0][3][c];
