@@ -49,7 +49,7 @@ int pick_shape(int D, int dtype, Shape* out) {
     }
     if (G > 64) {
       // more dims than 64 lanes x 16 elements hold: float64 samplers of the built-in elementwise energies take the
-      // multi-pass path (host_energy.hip: state in HBM between the substeps); others have no such form
+      // multi-pass path (multipass.hip: state in HBM between the substeps); others have no such form
       // (float32 state: the same path on float64 storage, the state rounded to float32 wherever it is written)
       s.esize = 8;
       s.pitch = (D + 1) / 2 * 2;
@@ -562,7 +562,7 @@ int mjhmc_sampler_destroy(mjhmc_sampler* s) {
     if (s->pipe_pin[i]) (void)hipHostFree(s->pipe_pin[i]);
     if (s->pipe_ev[i]) (void)hipEventDestroy(s->pipe_ev[i]);
   }
-  host_traj_free(s);
+  proposal_rows_free(s);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
   return 0;

@@ -16,7 +16,7 @@
 // memory.  A particle that takes the L move is finished when the trajectory is; one that does not gets its pre-move rows
 // copied over at the end.
 //
-// Same operations in the same order as the multi-pass path this replaces on the sampling path (host_energy.hip:
+// Same operations in the same order as the multi-pass path this replaces on the sampling path (pot_rows64.hip:
 // hk_pot_kick_drift / pot_eval_kernel) and the same GEMM code: results are bit-identical to it
 // (tests/test_gpu_dense_parity.py::test_pot64_fused_equals_multipass).
 #include <hip/hip_runtime.h>

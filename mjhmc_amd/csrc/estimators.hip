@@ -10,7 +10,7 @@
 // slot s to dwell-ring slot s: iterate.hip jump_args() sets a.dwell_ring = s->dwell_ring + (ring_slot0 + iter) * Npad, the
 // fused kernels add `it * Npad` to the pointer of their first iteration (jump_kernel.hpp, row_form.hpp: a.dwell_ring[it * Npad + p]),
 // the dense kernels store `best` through it, and the host-energy / multi-pass path does the same
-// (host_energy.hip: c.dwell_ring = s->dwell_ring + ring_slot * Npad).  The draw uses the rates OUT of the state the
+// (multipass.hip: c.dwell_ring = s->dwell_ring + ring_slot * Npad).  The draw uses the rates OUT of the state the
 // iteration starts from, so it is the time the particle spent in the state of slot s - 1: the holding time of the state
 // in slot s sits in dwell slot s + 1.  The kernels here take the two slot offsets separately and the sampler-level driver
 // passes w_slot0 = x_slot0 + 1.  (Read from the sources named above, all five writers; the definition test then checks

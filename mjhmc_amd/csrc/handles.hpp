@@ -87,7 +87,7 @@ inline const char* energy_kind_name(int kind) {
 struct Shape {
   int E, logG, pitch, CH, esize;
   // ndims beyond the register-resident elementwise kernels (> 64 lanes x 16 elements): the sampler runs the multi-pass
-  // path of host_energy.hip, state in HBM between the substeps (float64, built-in elementwise energies)
+  // path of multipass.hip, state in HBM between the substeps (float64, built-in elementwise energies: wide_energy.hip)
   bool wide = false;
   // float32 state was asked for, for rows only the multi-pass path handles: the sampler runs as a float64 one whose state
   // is rounded to float32 at the end of every operation that writes it (the caller sees float32 values throughout)
@@ -102,7 +102,7 @@ struct mjhmc_functionals;  // caller expressions g(x) evaluated into a derived r
 struct mjhmc_timegrid;   // the jump process sampled on a uniform time grid, in a grid ring of its own (timegrid.hip)
 struct mjhmc_stein;      // kernel Stein discrepancy of one recorded ensemble (stein.hip)
 struct DlSession;  // overlapped sample download of one mjhmc_iterate_download call (iterate.hip)
-struct HostTraj;  // proposal workspace of a host-energy sampler (host_energy.hip)
+struct ProposalRows;  // proposal workspace of a multi-pass sampler (multipass.hpp)
 
 struct mjhmc_sampler {
   mjhmc_ctx* ctx;
@@ -150,7 +150,7 @@ struct mjhmc_sampler {
   bool ck_valid = false;
   void* undo_X = nullptr;   // pre-move X of the last single-iteration call (its ping-pong input, still intact)
   bool undo_valid = false;
-  bool undo_multipass = false;   // the last committed iteration ran on the multi-pass path: its undo is a copy back (host_energy.hip)
+  bool undo_multipass = false;   // the last committed iteration ran on the multi-pass path: its undo is a copy back (multipass.hip)
   uint8_t* trans = nullptr;
   // What a call zeroes at its start and reads back at its end lives in ONE device block -- [Control, 64 bytes][flf_counts:
   // stats_cap + 1 counters, padded to 64 bytes][stats: stats_cap x 4] -- so that a call is one fill and one copy
@@ -192,7 +192,7 @@ struct mjhmc_sampler {
   size_t dl_stage_elems = 0;
   void* dl_pin[2] = {nullptr, nullptr};
   hipEvent_t dl_ev[2] = {nullptr, nullptr};
-  HostTraj* ht = nullptr;         // MJHMC_E_HOST: trajectory workspace (mjhmc_traj_*)
+  ProposalRows* prop = nullptr;   // multi-pass samplers (host energies, wide rows, float64 ProductOfT): proposal workspace
   bool host_energy_set = false;   // MJHMC_E_HOST: EX and dE/dX of the current state are the caller's (mjhmc_host_set_energy)
 };
 
@@ -211,19 +211,23 @@ void timegrid_free_all(mjhmc_sampler* s);
 // stein.hip
 void stein_free_all(mjhmc_sampler* s);
 
-// host_energy.hip
-void host_traj_free(mjhmc_sampler* s);
-int host_run_eval(mjhmc_sampler* s, const void* V, void* Vgen, void* EVout);
-int wide_run_eval(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen, void* EVout);
+// multipass.hip
+void proposal_rows_free(mjhmc_sampler* s);
 int multipass_iterate(mjhmc_sampler* s, int n_iter, const double* replay_normal, const double* replay_exp,
                       const double* replay_unif, int ring_slot0, mjhmc_iter_stats* per_iter, int* n_done);
 int multipass_rollback(mjhmc_sampler* s);
-int round_rows32(mjhmc_sampler* s, void* rows);   // float64 rows -> float32 values (Shape::round32), state_io.hip
-void pot_narrow_rows32(const double* src, float* dst, int64_t n, hipStream_t st);   // dst[i] = (float)src[i], i < n
+
+// wide_energy.hip
+int wide_run_eval(mjhmc_sampler* s, const void* X, void* Gout, void* Eout, const void* V, void* Vgen, void* EVout);
 int wide_leapfrog(mjhmc_sampler* w, const double* X, const double* V, double* Xo, double* Vo, double* G, double* EX,
                   double* EV, double eps, int n_steps);
 
-// state_io.hip: E and dE/dX of a state matrix through the sampler's own evaluation kernels (no momentum, no counters)
+// pot_rows64.hip
+void pot_narrow_rows32(const double* src, float* dst, int64_t n, hipStream_t st);   // dst[i] = (float)src[i], i < n
+
+// state_io.hip
+int round_rows32(mjhmc_sampler* s, void* rows);   // float64 rows -> float32 values (Shape::round32)
+// E and dE/dX of a state matrix through the sampler's own evaluation kernels (no momentum, no counters)
 int sampler_eval_rows(mjhmc_sampler* s, const void* X, void* Gout, void* Eout);
 
 // lanes-per-particle / elements-per-lane selection of the elementwise kernels for ndims = D

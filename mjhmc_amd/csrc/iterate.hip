@@ -85,13 +85,8 @@ static void fill_iter_stats(const mjhmc_sampler* s, const std::vector<long long>
   for (int i = 0; i < attempts; ++i) {
     mjhmc_iter_stats& st = per_iter[i];
     std::memset(&st, 0, sizeof(st));
-    // the clocks L, F, R of MarkovJumpHMC; FL, F, R of ContinuousTimeHMC (markov_jump_hmc.py:288-290); L, F, R, FL of the
-    // discrete-time samplers (markov_jump_hmc.py:138-148)
-    (s->mode == MJHMC_MODE_CTHMC ? st.fl : st.l) = hs[4 * i + 0];
-    st.f = hs[4 * i + 1];
-    st.r = hs[4 * i + 2];
+    clocks_to_stats(s->mode, &hs[4 * i], &st);
     if (s->mode == MJHMC_MODE_MJHMC) st.n_cold = hs[4 * i + 3] & 0xFFFFFFFFLL;   // (the dense kernels: integrated inverse-L trajectories in the high half)
-    else if (s->mode != MJHMC_MODE_CTHMC) st.fl = hs[4 * i + 3];
     st.E_evals = s->N + st.n_cold;  // L on all (+ FLF on the cold ones)
     st.dEdX_evals = (int64_t)s->L * (s->N + st.n_cold);
     st.nonfinite = (failed && i == done) ? 1 : 0;

@@ -2,7 +2,7 @@
 // the kernel and the order of its sums in dense_lin_pointwise.hpp).
 //
 // Per recorded slot, in stream order on the sampler's stream:
-//   1. a float64 slot is narrowed to the handle's float32 rows (the multi-pass path's own narrowing, host_energy.hip); a
+//   1. a float64 slot is narrowed to the handle's float32 rows (the multi-pass path's own narrowing, pot_rows64.hip); a
 //      float32 slot is read in place -- either way [Npad][P] float32 with the rows beyond the batch zero, what the float32
 //      force is given;
 //   2. the generated kernel over the items (strip, block of experts): one partial (S1, S2, mx, se) per strip, value and

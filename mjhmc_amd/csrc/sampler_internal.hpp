@@ -66,6 +66,16 @@ static inline RngKey rng_key(const mjhmc_sampler* s, uint64_t tick) {
                 (uint32_t)(tick >> 32)};
 }
 
+// the clocks of one attempt from its four device tallies: L, F, R of MarkovJumpHMC; FL, F, R of ContinuousTimeHMC
+// (markov_jump_hmc.py:288-290); L, F, R, FL of the discrete-time samplers (markov_jump_hmc.py:138-148).  What MarkovJumpHMC
+// keeps in the fourth tally is its caller's (iterate.hip: fill_iter_stats)
+static inline void clocks_to_stats(int mode, const long long hs[4], mjhmc_iter_stats* st) {
+  (mode == MJHMC_MODE_CTHMC ? st->fl : st->l) = hs[0];
+  st->f = hs[1];
+  st->r = hs[2];
+  if (mode != MJHMC_MODE_MJHMC && mode != MJHMC_MODE_CTHMC) st->fl = hs[3];
+}
+
 // ---------------------------------------------------------------------------------------------
 // api.hip
 // ---------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 namespace mjhmc {
 
 enum class Schedule {
-  Multipass,    // host_energy.hip: state in HBM between the substeps (wide rows; float64 ProductOfT at L = 0)
+  Multipass,    // multipass.hip: state in HBM between the substeps (wide rows; float64 ProductOfT at L = 0)
   Fused,        // iterate_fused_t: launches of up to kMaxFuse iterations of the elementwise energies
   DenseParts,   // iterate_dense_parts: the tile kernels of ProductOfT / SparseImageCode, as free-running parts where that pays
   Compact,      // iterate_compact_t: trajectory launch + jump-process launch, the cold list carried from call to call

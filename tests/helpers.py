@@ -295,3 +295,41 @@ def hooks_context(device=0):
     if device not in _HOOKS_CTX:
         _HOOKS_CTX[device] = engine.Context(device, lib=_lib.load_test_hooks())
     return _HOOKS_CTX[device]
+
+
+# ---------------------------------------------------------------------------------------------
+# the float64 tile kernels against their multi-pass twin (csrc/multipass.hip: multipass_iterate around
+# csrc/pot_rows64.hip), which the test build's MJHMC_POT64_MULTIPASS=1 selects
+# ---------------------------------------------------------------------------------------------
+MULTIPASS_PAIR_FIELDS = ('X', 'V', 'DEDX', 'EX', 'EV', 'HFLF', 'DWELL', 'TRANS')
+
+
+def iterate_multipass_pair(pair, n_it, hparams, monkeypatch, **iterate_kw):
+    """n_it iterations of the product library's sampler (pair[0], the variable unset) and of the test build's in the
+    multi-pass form (pair[1], MJHMC_POT64_MULTIPASS=1), both with set_hparams(*hparams).  Returns their two lists of
+    (l, f, r, fl, n_cold, E_evals, dEdX_evals, n_flf_run), one tuple per iteration."""
+    out = []
+    for k, s in enumerate(pair):
+        s.set_hparams(*hparams)
+        if k == 1:
+            monkeypatch.setenv('MJHMC_POT64_MULTIPASS', '1')
+        else:
+            monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
+        st, done = s.iterate(n_it, **iterate_kw)
+        assert done == n_it
+        out.append([(t.l, t.f, t.r, t.fl, t.n_cold, t.E_evals, t.dEdX_evals, t.n_flf_run) for t in st])
+    monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
+    return out
+
+
+def assert_multipass_pair_equal(pair, tag, fields=MULTIPASS_PAIR_FIELDS):
+    """The live state of the two samplers: X, V, dE/dX, E(X) and the transitions bit for bit.  The kinetic energy's
+    squares are added up in another order in the two forms (tile reduction / one wavefront per row) -- EV, HFLF: 1e-12;
+    DWELL, where an F clock's rate is a difference of two near-equal rates: 1e-7."""
+    from mjhmc_amd import _lib
+    for f in fields:
+        fa, fb = pair[0].read(getattr(_lib, 'F_' + f)), pair[1].read(getattr(_lib, 'F_' + f))
+        if f in ('EV', 'HFLF', 'DWELL'):
+            assert np.allclose(fa, fb, rtol=1e-7 if f == 'DWELL' else 1e-12, atol=0, equal_nan=True), (tag, f)
+        else:
+            assert np.array_equal(fa, fb, equal_nan=True), (tag, f, np.abs(fa - fb).max())

@@ -87,7 +87,8 @@ import numpy as np
 import pytest
 
 from oracle import mjhmc_oracle as orc
-from tests.helpers import check_control_iteration, check_iteration, hooks_context, pot_padded_dim, resync
+from tests.helpers import (assert_multipass_pair_equal, check_control_iteration, check_iteration, hooks_context,
+                           iterate_multipass_pair, pot_padded_dim, resync)
 from tests.test_gpu_pot_widths import (BARS, BETA, EPS_GRID, LIVE_DH, N_ITER, SEEDS, STATES, _decision,
                                        _other_decision, _proposals, f32, rel, shares_ok)
 
@@ -628,36 +629,18 @@ def _pair(D, K, N, mode, exprs, seed=11):
     return [engine.DeviceSampler(en, _x0(D, N), seed=seed, dtype='float64', mode=getattr(_lib, 'MODE_' + mode)) for en in ens]
 
 
-def _iterate_both(pair, n_it, hparams, monkeypatch):
-    out = []
-    for k, s in enumerate(pair):
-        s.set_hparams(*hparams)
-        if k == 1:
-            monkeypatch.setenv('MJHMC_POT64_MULTIPASS', '1')
-        else:
-            monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
-        st, done = s.iterate(n_it)
-        assert done == n_it
-        out.append([(t.l, t.f, t.r, t.fl, t.n_cold, t.E_evals, t.dEdX_evals, t.n_flf_run) for t in st])
-    monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
-    return out
-
-
 def _compare(pair, tag, finite, mode):
     from mjhmc_amd import _lib
-    for f in _FIELDS:
+    assert_multipass_pair_equal(pair, tag, fields=_FIELDS)
+    for f in _FIELDS if finite else ():
         fa, fb = pair[0].read(getattr(_lib, 'F_' + f)), pair[1].read(getattr(_lib, 'F_' + f))
-        if f in ('EV', 'HFLF', 'DWELL'):
-            assert np.allclose(fa, fb, rtol=1e-7 if f == 'DWELL' else 1e-12, atol=0, equal_nan=True), (tag, f)
-        else:
-            assert np.array_equal(fa, fb, equal_nan=True), (tag, f, np.abs(fa - fb).max())
-        if finite and f in ('X', 'V', 'DEDX', 'EX', 'EV'):
+        if f in ('X', 'V', 'DEDX', 'EX', 'EV'):
             assert np.isfinite(fa).all() and np.isfinite(fb).all(), (tag, f, 'not finite')
-        if finite and f == 'HFLF':       # NaN is the empty cache's mark: the cached energies must be finite
+        if f == 'HFLF':       # NaN is the empty cache's mark: the cached energies must be finite
             cached = [s.read(_lib.F_CACHE).astype(bool) for s in pair]
             assert np.array_equal(cached[0], cached[1]) and np.array_equal(~np.isnan(fa), cached[0]), (tag, 'cache flags')
             assert np.isfinite(fa[cached[0]]).all(), (tag, f, 'not finite')
-        if finite and f == 'DWELL' and mode != 'CONTROL':
+        if f == 'DWELL' and mode != 'CONTROL':
             assert np.isfinite(fa).all() and (fa > 0).all(), (tag, f, 'not finite')
 
 
@@ -675,7 +658,7 @@ def test_float64_kernel_equals_its_multipass_twin(D, K, N, L, mode, pair_name, m
     hparams = (0.1, L, 0.4, 0.3) if mode == 'CONTROL' else (0.1, L, 0.4, 1.0)
     stats = [[], []]
     for n_it in (1, 3):
-        a, b = _iterate_both(pair, n_it, hparams, monkeypatch)
+        a, b = iterate_multipass_pair(pair, n_it, hparams, monkeypatch)
         stats[0] += a
         stats[1] += b
         _compare(pair, (D, K, N, L, mode, pair_name, n_it), pair_name == 'l1', mode)

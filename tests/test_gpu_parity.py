@@ -959,7 +959,7 @@ def test_float32_state_beyond_the_register_kernels(kind, D, N):
 def test_more_dims_than_the_register_kernels_hold(cls_name, kind, D, N):
     """hmc_state.py:86-100 are plain array operations: the reference takes any ndims.  Beyond 1024 float64 dims (64 lanes x
     16 elements) the engine switches to its multi-pass path -- state in HBM between the substeps, one wavefront per row
-    (csrc/host_energy.hip: multipass_iterate) -- and must follow the oracle exactly as the register kernels do."""
+    (csrc/multipass.hip: multipass_iterate) -- and must follow the oracle exactly as the register kernels do."""
     from mjhmc_amd.samplers import markov_jump_hmc as M
     from mjhmc_amd.misc import distributions as Dm
     rs = np.random.RandomState(D + N)

@@ -12,12 +12,9 @@ several.  Every pair of (N, L), (N, mode) and (L, mode) occurs at every D."""
 import numpy as np
 import pytest
 
-from tests.helpers import ref_init_weights, hooks_context
+from tests.helpers import ref_init_weights, hooks_context, iterate_multipass_pair, assert_multipass_pair_equal
 
 pytestmark = pytest.mark.gpu
-
-_FIELDS = ('X', 'V', 'DEDX', 'EX', 'EV', 'HFLF', 'DWELL', 'TRANS')
-
 
 def _pair(D, N, mode, bias_seed, x_seed, seed):
     from mjhmc_amd import engine, _lib
@@ -28,32 +25,6 @@ def _pair(D, N, mode, bias_seed, x_seed, seed):
     ens = [engine.DeviceEnergy(c, _lib.E_PRODUCT_OF_T, D, params) for c in ctxs]
     X0 = np.random.RandomState(x_seed).randn(D, N)
     return [engine.DeviceSampler(en, X0, seed=seed, dtype='float64', mode=getattr(_lib, 'MODE_' + mode)) for en in ens]
-
-
-def _iterate_both(pair, n_it, hparams, monkeypatch):
-    """n_it iterations of the product library (pair[0]) and of the multi-pass form (pair[1]); their stats"""
-    out = []
-    for k, s in enumerate(pair):
-        s.set_hparams(*hparams)
-        if k == 1:
-            monkeypatch.setenv('MJHMC_POT64_MULTIPASS', '1')
-        else:
-            monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
-        st, done = s.iterate(n_it)
-        assert done == n_it
-        out.append([(t.l, t.f, t.r, t.fl, t.n_cold, t.E_evals, t.dEdX_evals, t.n_flf_run) for t in st])
-    monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
-    return out
-
-
-def _compare(pair, tag):
-    from mjhmc_amd import _lib
-    for f in _FIELDS:
-        fa, fb = pair[0].read(getattr(_lib, 'F_' + f)), pair[1].read(getattr(_lib, 'F_' + f))
-        if f in ('EV', 'HFLF', 'DWELL'):
-            assert np.allclose(fa, fb, rtol=1e-7 if f == 'DWELL' else 1e-12, atol=0, equal_nan=True), (tag, f)
-        else:
-            assert np.array_equal(fa, fb, equal_nan=True), (tag, f, np.abs(fa - fb).max())
 
 
 _CASES = [(N, L, mode) for N, L, mode in ((33, 1, 'MJHMC'), (64, 1, 'CONTROL'), (33, 2, 'MJHMC'), (64, 2, 'CONTROL'),
@@ -69,10 +40,10 @@ def test_pot64_register_position_equals_multipass(D, N, L, mode, monkeypatch):
     hparams = (0.1, L, 0.4, 0.3) if mode == 'CONTROL' else (0.1, L, 0.4, 1.0)
     stats = [[], []]
     for n_it in (1, 3):
-        a, b = _iterate_both(pair, n_it, hparams, monkeypatch)
+        a, b = iterate_multipass_pair(pair, n_it, hparams, monkeypatch)
         stats[0] += a
         stats[1] += b
-        _compare(pair, (D, N, L, mode, n_it))
+        assert_multipass_pair_equal(pair, (D, N, L, mode, n_it))
     assert [t[:7] for t in stats[0]] == [t[:7] for t in stats[1]]
     if mode == 'MJHMC':
         n_flf_run = [t[7] for t in stats[0]]
@@ -88,8 +59,8 @@ def test_pot64_half_depth_gemm_one_step(monkeypatch):
     changes it."""
     from mjhmc_amd import _lib
     pair = _pair(512, 32, 'MJHMC', bias_seed=1, x_seed=3, seed=8)
-    a, b = _iterate_both(pair, 1, (0.1, 1, 0.2, 1.0), monkeypatch)
-    _compare(pair, 'half-depth')
+    a, b = iterate_multipass_pair(pair, 1, (0.1, 1, 0.2, 1.0), monkeypatch)
+    assert_multipass_pair_equal(pair, 'half-depth')
     assert [t[:7] for t in a] == [t[:7] for t in b]
     G =pair[0].read(_lib.F_DEDX)
     assert np.isfinite(G).all() and np.abs(G).max() > 0

@@ -7,7 +7,7 @@ where the first kick / drift pass is also the last drift."""
 import numpy as np
 import pytest
 
-from tests.helpers import ref_init_weights, hooks_context
+from tests.helpers import ref_init_weights, hooks_context, iterate_multipass_pair, assert_multipass_pair_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -26,24 +26,12 @@ def test_pot64_staged_rows_equal_multipass(D, N, mode, L, monkeypatch):
     X0 = np.random.RandomState(4).randn(D, N)
     pair = [engine.DeviceSampler(en, X0, seed=11, dtype='float64', mode=getattr(_lib, 'MODE_' + mode)) for en in ens]
     stats = [[], []]
+    # p_r = 0.4: many R-movers, so every MJHMC iteration has inverse-L items
+    hparams = (0.1, L, 0.4, 0.3) if mode == 'CONTROL' else (0.1, L, 0.4, 1.0)
     for n_it in (1, 3, 2):
-        for k, s in enumerate(pair):
-            # p_r = 0.4: many R-movers, so every MJHMC iteration has inverse-L items
-            s.set_hparams(0.1, L, 0.4, 0.3) if mode == 'CONTROL' else s.set_hparams(0.1, L, 0.4, 1.0)
-            if k == 1:
-                monkeypatch.setenv('MJHMC_POT64_MULTIPASS', '1')
-            else:
-                monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
-            st, done = s.iterate(n_it)
-            assert done == n_it
-            stats[k] += [(t.l, t.f, t.r, t.fl, t.n_cold, t.E_evals, t.dEdX_evals) for t in st]
-        monkeypatch.delenv('MJHMC_POT64_MULTIPASS', raising=False)
-        for f in ('X', 'V', 'DEDX', 'EX', 'EV', 'HFLF', 'DWELL', 'TRANS'):
-            fa, fb = pair[0].read(getattr(_lib, 'F_' + f)), pair[1].read(getattr(_lib, 'F_' + f))
-            if f in ('EV', 'HFLF', 'DWELL'):   # sum(V^2) is added up in a different order in the two forms
-                assert np.allclose(fa, fb, rtol=1e-7 if f == 'DWELL' else 1e-12, atol=0, equal_nan=True), (n_it, f)
-            else:
-                assert np.array_equal(fa, fb, equal_nan=True), (n_it, f, np.abs(fa - fb).max())
+        for k, st in enumerate(iterate_multipass_pair(pair, n_it, hparams, monkeypatch)):
+            stats[k] += [t[:7] for t in st]
+        assert_multipass_pair_equal(pair, n_it)
     assert stats[0] == stats[1]
     if mode == 'MJHMC':
         cold = [t[4] for t in stats[0]]
