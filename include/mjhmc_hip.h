@@ -586,6 +586,64 @@ int mjhmc_histogram_create_on(mjhmc_functionals* f, int n_bins, const double* lo
 int mjhmc_pairhist_create_on(mjhmc_functionals* f, int n_pairs, const int32_t* pairs, int n_bins, const double* lo,
                              const double* hi, double quantum, mjhmc_pairhist** out);
 
+/* Cell occupancy and transition counts of the recorded chains, kept on the device (csrc/occupancy.hip, csrc/occupancy.hpp):
+ * how much time the ensemble spends in each region of the state space and how often a chain moves from one region to
+ * another -- the empirical transition matrices the reference builds for its toy ladders only (mjhmc/misc/mixing.py,
+ * mjhmc/experiments/spectral.py), for the continuous samplers.  The accumulators above say where the ensemble is; this
+ * one keeps a per-chain memory from one recorded state to the next.
+ * n_centres = M centres (1 .. 64) of n_dims = K coordinates each (centres: double [M][K], finite; K must be the ring's
+ * ndims), r2: M squared radii (>= 0, +inf for none) or NULL for none, `quantum` q a positive power of two.  The cells are the
+ * Voronoi cells of the centres -- with radii, cut to the balls -- and one more, index M, "outside".  For a state row x (its
+ * elements widened exactly to float64), m ascending:
+ *     d2_m = 0.0;  for d ascending below K:  t = x_d - c[m][d];  d2_m = d2_m + t * t     every operation rounded, not fused
+ *     best = +inf, label = M;  m replaces the label only when d2_m < best (strictly: the lowest index wins ties; a NaN or
+ *     infinite distance is never chosen, so a state that is not finite lands outside)
+ *     with r2: label = M unless best <= r2[label]
+ * Tables, uint64, indexed by cell in [0, M], with u = rint(w / q) (nearest-even; the division is exact):
+ *     count[a], mass[a]             states in cell a and their units
+ *     trans[a][b]                   pairs (state s, state s + 1) of one chain with labels a, b
+ *     from_count[a], from_mass[a]   count / mass of the states that have a successor; from_count[a] = sum_b trans[a][b]
+ *     W_units                       the sum of units
+ * and per chain p switches[p] (transitions with a != b; the outside cell is a cell) and visited[p] (bit m: cell m < M was
+ * seen).  Every sum is an integer: the tables are bit-identical from run to run and do not depend on how a run is cut into
+ * linked blocks; there is no floating-point atomic in the pass.
+ * Ownership as for mjhmc_histogram: the handle belongs to the sampler it was created on (and to its ring: a re-allocated
+ * ring invalidates it), mjhmc_sampler_destroy frees every one still alive and the handle is INVALID from then on.
+ * MJHMC_ERR_INVALID, before anything is allocated: M outside [1, 64], a centre that is not finite, an r2 that is negative
+ * or NaN, K that is not the ring's ndims, a quantum that is no power of two, no ring. */
+typedef struct mjhmc_occupancy mjhmc_occupancy;
+int mjhmc_occupancy_create(mjhmc_sampler* s, int n_centres, int n_dims, const double* centres, const double* r2, double quantum,
+                           mjhmc_occupancy** out);
+/* on the derived ring (which must exist): the cells live in the space of the K functional values */
+int mjhmc_occupancy_create_on(mjhmc_functionals* f, int n_centres, int n_dims, const double* centres, const double* r2,
+                              double quantum, mjhmc_occupancy** out);
+int mjhmc_occupancy_destroy(mjhmc_occupancy* h);
+/* Adds the n states of ring slots [x_slot0, x_slot0 + n) of every chain, in slot order, with the weights of dwell-ring
+ * slots [w_slot0, w_slot0 + n) or unit weights for w_slot0 == -1: the pairing of mjhmc_histogram_accumulate.  linked = 0
+ * starts new chains at x_slot0 (no transition into its state is counted; switches and visited go on); linked = 1 says
+ * that slot x_slot0 follows the last state of the previous block, whose label and units every chain carries, and counts
+ * that pair too.  The weights are checked on the device ahead of the pass by mjhmc_histogram_accumulate's own check; a
+ * refused block adds nothing and leaves the carry as it was, with that pass's codes and messages: MJHMC_ERR_NONFINITE: a
+ * weight that is not finite, or negative.  MJHMC_ERR_INVALID: a weight with w / q >= 2^53, a block that would take
+ * W_units to 2^63 or beyond, slots outside the ring, n < 1, linked = 1 on a handle that holds no block, or a ring
+ * re-allocated since create. */
+int mjhmc_occupancy_accumulate(mjhmc_occupancy* h, int x_slot0, int w_slot0, int n, int linked);
+/* count, mass, from_count, from_mass: M + 1 values each; trans: (M + 1) * (M + 1), row a = the departures from cell a;
+ * chains_by_switches: 17 values, the chains with 0 .. 15 and with 16 or more switches; chains_by_cells: M + 1 values, the
+ * chains that saw exactly c distinct cells < M (both tallied on the device with integer atomics); switches (uint32 [N])
+ * and visited (uint64 [N]): the per-chain values themselves, either may be NULL; the number of (slot, particle) states
+ * added so far. */
+int mjhmc_occupancy_read(mjhmc_occupancy* h, uint64_t* count, uint64_t* mass, uint64_t* from_count, uint64_t* from_mass,
+                         uint64_t* trans, uint64_t* W_units, uint64_t* chains_by_switches, uint64_t* chains_by_cells,
+                         uint32_t* switches, uint64_t* visited, int64_t* n_states);
+/* labels: uint8 [n][N], the labels of the first n slots of the last block given to mjhmc_occupancy_accumulate (refused or
+ * not), as the pass computed them (tests and inspection) */
+int mjhmc_occupancy_read_labels(mjhmc_occupancy* h, int n, uint8_t* labels);
+/* zero tables, totals, switches, visited and the carry; centres, radii and quantum stay */
+int mjhmc_occupancy_reset(mjhmc_occupancy* h);
+/* M, K and the slots the label scratch holds (the ring's at create: n of an accumulate call is at most this) */
+int mjhmc_occupancy_info(mjhmc_occupancy* h, int* n_centres, int* n_dims, int* label_slots);
+
 /* Kernel Stein discrepancy of one recorded ensemble against exp(-E), on the device (csrc/stein.hip, csrc/stein.hpp):
  * the one question the accumulators above leave open -- is the ensemble a sample of the target? -- answered from the
  * states and dE/dX at the states alone, with no normaliser and no reference sample (Gorham & Mackey 2017).  The base

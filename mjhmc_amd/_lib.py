@@ -143,6 +143,16 @@ PROTOTYPES = {
     'mjhmc_estimator_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
     'mjhmc_chainstats_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(_P)]),
     'mjhmc_histogram_create_on': (ctypes.c_int, [_P, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_occupancy_create': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_occupancy_create_on': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_double, ctypes.POINTER(_P)]),
+    'mjhmc_occupancy_destroy': (ctypes.c_int, [_P]),
+    'mjhmc_occupancy_accumulate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_occupancy_read': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_uint64), _P, _P, _P, _P,
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    'mjhmc_occupancy_read_labels': (ctypes.c_int, [_P, ctypes.c_int, _P]),
+    'mjhmc_occupancy_reset': (ctypes.c_int, [_P]),
+    'mjhmc_occupancy_info': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int)]),
     'mjhmc_stein_create': (ctypes.c_int, [_P, ctypes.c_double, ctypes.POINTER(_P)]),
     'mjhmc_stein_evaluate': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
     'mjhmc_stein_destroy': (ctypes.c_int, [_P]),
@@ -219,6 +229,8 @@ TEST_HOOK_PROTOTYPES = {
     'mjhmc_test_ring_write_dwell': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, ctypes.c_double]),
     'mjhmc_test_ring_write': (ctypes.c_int, [_P, ctypes.c_int, _P]),
     'mjhmc_test_ring_fill_padding': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_test_ring_fill_element_padding': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    'mjhmc_test_occupancy_part': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'mjhmc_test_timegrid_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
     'mjhmc_test_functionals_read_raw': (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_size_t]),
     'mjhmc_test_energy_observables_part': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

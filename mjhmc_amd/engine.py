@@ -500,6 +500,13 @@ class DeviceSampler(object):
         power of two).  The ring must exist (ring_alloc)."""
         return DevicePairHistogram(self, pairs, bins, lo, hi, quantum)
 
+    def occupancy(self, centres, r2=None, q=1.0):
+        """Cell occupancy and transition counts of the chains over linked blocks of this sampler's ring (mjhmc_occupancy_*):
+        the Voronoi cells of ``centres`` (M, ndims), 1 <= M <= 64, cut to balls of squared radius ``r2`` (an M-vector, +inf
+        for none, or None), plus the cell "outside"; integer counts and integer masses in units of ``q`` (a power of
+        two).  The ring must exist (ring_alloc)."""
+        return DeviceOccupancy(self, centres, r2, q)
+
     def functionals(self, values, stats=(), params=()):
         """K values g[k] = value_k(S; p) of every recorded state, S[j] = sum_d stat_j(x_d, d; p): C expressions evaluated on
         the device into a derived ring that the estimators read (mjhmc_functionals_*).  The ring must exist (ring_alloc)."""
@@ -987,6 +994,62 @@ class DevicePairHistogram(_RingAccumulator):
         return count, mass, int(W.value), int(n.value)
 
 
+class DeviceOccupancy(_RingAccumulator):
+    """Per cell a of the M + 1 cells (the Voronoi cells of the M centres, cut to the balls of squared radius ``r2`` where
+    one is given, and cell M, "outside"): count[a] states, mass[a] = sum of rint(w / q), and per pair of cells trans[a][b]
+    consecutive states of one chain, over the ring blocks given to ``accumulate`` in chain order; per chain the number of
+    switches and the cells seen (include/mjhmc_hip.h: mjhmc_occupancy_create).  Integer sums: bit-identical from run to
+    run, whatever the blocks.  ``accumulate`` refuses what DeviceHistogram's refuses, and a refused block leaves the
+    chains where they were."""
+    _kind = 'occupancy'
+
+    def __init__(self, dev, centres, r2=None, q=1.0, on=None):
+        """``on``: a DeviceFunctionals of ``dev`` whose derived ring the states are read from (see DeviceEstimator)"""
+        self.centres = np.ascontiguousarray(np.asarray(centres, dtype=np.float64))
+        if self.centres.ndim != 2:
+            raise ValueError('centres must be (M, K), got an array of shape %r' % (self.centres.shape,))
+        self.n_centres, self.ndims = self.centres.shape
+        self.r2 = None if r2 is None else as_f64(np.broadcast_to(np.asarray(r2, dtype=np.float64), (self.n_centres,)))
+        self.quantum = float(q)
+        self.nparticles = dev.nparticles
+        self._create(dev, on, self.n_centres, self.ndims, ptr(self.centres), ptr(self.r2), self.quantum, checker=check_args)
+
+    def accumulate(self, x_slot0, n, w_slot0=-1, linked=False):
+        """``linked``: slot ``x_slot0`` follows the last state of the previous block (its pair is counted); False starts
+        new chains there"""
+        self._call('accumulate', int(x_slot0), int(w_slot0), int(n), 1 if linked else 0)
+
+    def read(self, chains=False):
+        """dict of uint64 arrays: count, mass, from_count, from_mass (M + 1,), trans (M + 1, M + 1), chains_by_switches
+        (17,), chains_by_cells (M + 1,), and the ints W_units, n_states; ``chains=True`` adds switches (N,) uint32 and
+        visited (N,) uint64, an O(N) download"""
+        C, N = self.n_centres + 1, self.nparticles
+        out = dict((k, np.zeros(C, dtype=np.uint64)) for k in ('count', 'mass', 'from_count', 'from_mass', 'chains_by_cells'))
+        out['trans'] = np.zeros((C, C), dtype=np.uint64)
+        out['chains_by_switches'] = np.zeros(17, dtype=np.uint64)
+        sw = np.zeros(N, dtype=np.uint32) if chains else None
+        vis = np.zeros(N, dtype=np.uint64) if chains else None
+        W, n = ctypes.c_uint64(), ctypes.c_int64()
+        self._call('read', ptr(out['count']), ptr(out['mass']), ptr(out['from_count']), ptr(out['from_mass']), ptr(out['trans']),
+                   ctypes.byref(W), ptr(out['chains_by_switches']), ptr(out['chains_by_cells']), ptr(sw), ptr(vis), ctypes.byref(n))
+        out['W_units'], out['n_states'] = int(W.value), int(n.value)
+        if chains:
+            out['switches'], out['visited'] = sw, vis
+        return out
+
+    def read_labels(self, n):
+        """(n, N) uint8: the labels of the first ``n`` slots of the last block given to ``accumulate``"""
+        out = np.zeros((int(n), self.nparticles), dtype=np.uint8)
+        self._call('read_labels', int(n), ptr(out))
+        return out
+
+    def info(self):
+        """(M, K, the slots the label scratch holds)"""
+        m, k, sl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._call('info', ctypes.byref(m), ctypes.byref(k), ctypes.byref(sl))
+        return int(m.value), int(k.value), int(sl.value)
+
+
 def join_exprs(exprs):
     """one expression or a sequence of them -> the ';'-separated bytes the C ABI takes (None for none)"""
     exprs = [exprs] if isinstance(exprs, str) else list(exprs)
@@ -1072,6 +1135,10 @@ class DeviceFunctionals(_RingHandle):
 
     def pair_histogram(self, pairs, bins, lo, hi, quantum=1.0):
         return DevicePairHistogram(self.dev, pairs, bins, lo, hi, quantum, on=self)
+
+    def occupancy(self, centres, r2=None, q=1.0):
+        """the sampler's DeviceOccupancy with the cells in the space of the K values of this derived ring"""
+        return DeviceOccupancy(self.dev, centres, r2, q, on=self)
 
     def cross_moments(self):
         """the sampler's DeviceCrossMoments with b the K values of this derived ring (K <= 512)"""

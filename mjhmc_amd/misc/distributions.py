@@ -349,6 +349,13 @@ class MultimodalGaussian(Distribution):
     def device_energy(self):
         return (_lib.E_MM_GAUSS, np.array([self.separation], dtype=np.float64))
 
+    def modes(self):
+        """(2, ndims): the centres of the two modes as the energy codes them (csrc/energy_mm.hip), -/+ 2 * separation on
+        the first axis -- ``sampler.occupancy(n_iter, distribution.modes())`` counts the hops between them"""
+        c = np.zeros((2, self.ndims))
+        c[0, 0], c[1, 0] = -2.0 * self.separation, 2.0 * self.separation
+        return c
+
     def init_X(self):
         self.Xinit = ((np.random.randn(self.ndims, self.nbatch) + self.sep_vec) +
                       (np.random.randn(self.ndims, self.nbatch) - self.sep_vec))

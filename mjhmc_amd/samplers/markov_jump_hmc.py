@@ -289,6 +289,109 @@ class JointMarginals(object):
         return threshold, mask.reshape(self.n_pairs, B, B)
 
 
+class Occupancy(object):
+    """What ``occupancy()`` returns: how the chains spend their time in, and move between, the cells of ``centres`` -- cell
+    m < M the Voronoi cell of centre m (cut to its ball where a radius was given), cell M "outside".
+
+    Built from the integer tables of ``DeviceOccupancy.read()`` (``tables``: count, mass, from_count, from_mass (M + 1,),
+    trans (M + 1, M + 1), W_units, chains_by_switches (17,), chains_by_cells (M + 1,)), the quantum ``q`` of the masses, the
+    ``centres``, ``n_states`` and ``grad_evals`` (the increase of ``distribution.dEdX_count`` over the call).  Everything
+    below is float64 NumPy on (M + 1)^2 numbers:
+
+      weight               mass / W_units: the (dwell-weighted) share of the time spent in each cell
+      transition_matrix()  trans row-normalised; a cell with no departure keeps the identity row
+      rate_matrix()        Q[a][b] = trans[a][b] / (q from_mass[a]) off the diagonal, Q[a][a] = -sum of its row: the
+                           maximum-likelihood generator of the cell process in process time (a row without departures is
+                           zero); for the discrete-time samplers (unit weights) it is transition_matrix() - I
+      stationary()         the left null vector of Q on the cells that were visited (0 elsewhere), summing to 1
+      spectral_gap()       1 - |lambda_2| of the transition matrix on the visited cells (the reference's sg(); NaN with
+                           fewer than two visited cells)
+      relaxation_time()    -1 / Re lambda_2(Q) on the visited cells, in process time (inf when a second eigenvalue is 0)
+      relaxation_grads()   the same in gradient evaluations: relaxation_time() * grad_evals / (q W_units)
+      mean_residence       q from_mass[a] / (departures from a to another cell): the mean time of a stay (inf: none left)
+      crossings            transitions between different cells (the outside cell is a cell); crossings_per_grad
+      chains_by_switches   chains with 0 .. 15 and with >= 16 switches;  never_left: the fraction with none
+      chains_by_cells      chains that saw exactly c distinct cells < M"""
+
+    def __init__(self, tables, q, centres, n_states, grad_evals=0):
+        self.tables = tables
+        self.quantum = q = float(q)
+        self.centres = np.asarray(centres, dtype=np.float64)
+        self.n_cells = self.centres.shape[0] + 1
+        self.n_states, self.grad_evals = int(n_states), int(grad_evals)
+        self.counts = np.asarray(tables['count'], dtype=np.uint64)
+        self.units = np.asarray(tables['mass'], dtype=np.uint64)
+        self.trans = np.asarray(tables['trans'], dtype=np.uint64)
+        self.from_counts = np.asarray(tables['from_count'], dtype=np.uint64)
+        self.from_units = np.asarray(tables['from_mass'], dtype=np.uint64)
+        self.W_units = int(tables['W_units'])
+        self.total_weight = q * self.W_units
+        self.chains_by_switches = np.asarray(tables['chains_by_switches'], dtype=np.uint64)
+        self.chains_by_cells = np.asarray(tables['chains_by_cells'], dtype=np.uint64)
+        self.n_chains = int(self.chains_by_switches.sum())
+        self.weight = self.units.astype(np.float64) / self.W_units if self.W_units else np.full(self.n_cells, np.nan)
+        self.visited = self.counts > 0
+        T = self.trans.astype(np.float64)
+        self.crossings = int(self.trans.sum() - np.trace(self.trans))
+        self.crossings_per_grad = self.crossings / float(self.grad_evals) if self.grad_evals else np.nan
+        self.never_left = float(self.chains_by_switches[0]) / self.n_chains if self.n_chains else np.nan
+        exits = T.sum(axis=1) - np.diag(T)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.mean_residence = np.where(exits > 0, q * self.from_units.astype(np.float64) / exits, np.inf)
+
+    def transition_matrix(self):
+        T = self.trans.astype(np.float64)
+        n = self.from_counts.astype(np.float64)
+        P = np.eye(self.n_cells)
+        rows = n > 0
+        P[rows] = T[rows] / n[rows, None]
+        return P
+
+    def rate_matrix(self):
+        T = self.trans.astype(np.float64)
+        t = self.quantum * self.from_units.astype(np.float64)
+        Q = np.zeros((self.n_cells, self.n_cells))
+        rows = t > 0
+        Q[rows] = T[rows] / t[rows, None]
+        np.fill_diagonal(Q, 0.0)
+        np.fill_diagonal(Q, -Q.sum(axis=1))
+        return Q
+
+    def _on_visited(self, A):
+        v = np.flatnonzero(self.visited)
+        return A[np.ix_(v, v)], v
+
+    def stationary(self):
+        Q, v = self._on_visited(self.rate_matrix())
+        pi = np.zeros(self.n_cells)
+        if v.size:
+            # pi Q = 0 with sum pi = 1, in the least-squares sense (one solution when the visited cells communicate)
+            A = np.vstack([Q.T, np.ones((1, v.size))])
+            rhs = np.zeros(v.size + 1)
+            rhs[-1] = 1.0
+            pi[v] = np.linalg.lstsq(A, rhs, rcond=None)[0]
+        return pi
+
+    def spectral_gap(self):
+        P, v = self._on_visited(self.transition_matrix())
+        if v.size < 2:
+            return np.nan
+        lam = np.sort(np.abs(np.linalg.eigvals(P)))[::-1]
+        return float(1.0 - lam[1])
+
+    def relaxation_time(self):
+        Q, v = self._on_visited(self.rate_matrix())
+        if v.size < 2:
+            return np.nan
+        re = np.sort(np.linalg.eigvals(Q).real)[::-1]      # 0 first, then the slowest decay
+        return float(-1.0 / re[1]) if re[1] < 0 else np.inf
+
+    def relaxation_grads(self):
+        if not (self.grad_evals and self.W_units):
+            return np.nan
+        return self.relaxation_time() * self.grad_evals / self.total_weight
+
+
 class AutocorrelationTimes(object):
     """What ``Paths.iat()`` returns, per dimension: ``rho`` (max_lag + 1, ndims), ``tau`` (grid steps), ``tau_time``
     (process time), ``tau_grad_evals`` (gradient evaluations per chain), ``window`` (lags that entered tau), ``converged``;
@@ -1877,6 +1980,69 @@ class HMCBase(object):
         lo, hi, q, sums = self._histograms(n_iter, range, block, span, of,
                                            lambda src, lo, hi, q: src.pair_histogram(pairs, bins, lo[pairs], hi[pairs], q))
         return JointMarginals(pairs, lo[pairs], hi[pairs], bins, q, *sums)
+
+    def occupancy(self, n_iter, centres, radius=None, of=None, block=None):
+        """Cell occupancy and transition counts of ``n_iter`` consecutive states of every particle, every particle being
+        one chain, accumulated on the device (csrc/occupancy.hip): how much time the chains spend in each region, how often
+        they cross, how many never did, and the relaxation time the crossings imply.  The host receives (M + 1)^2 integers
+        whatever the length of the run.  Returns an ``Occupancy``.
+
+        The cells are the Voronoi cells of ``centres`` (M, ndims), 1 <= M <= 64: a state belongs to the nearest centre (the
+        lowest index at equal distances).  ``radius``, a scalar or an M-vector, cuts every cell to the ball around its
+        centre (core sets).  One more cell, index M, is "outside": every state that belongs to no centre, a state that is
+        not finite included.
+
+        The run itself is that of ``expectations(n_iter)``: the same iterations, the same weights (holding times for the
+        jump samplers, which run ``n_iter + 1`` iterations; one per state otherwise), the same counters,
+        ``dwelling_times`` and final state, bit for bit, in blocks of ``block`` states; nothing is added to ``E_count`` /
+        ``dEdX_count``.  Every chain carries its last label from one block to the next, so the tables do not depend on
+        ``block``, bit for bit.  The jump samplers count weights in units of q = 2^(floor(log2(mean weight of the first
+        block)) - 24); the others in units of 1.
+
+        ``of``: a ``Functionals`` (``functionals()``), ``Projections`` (``projections()``) or ``EnergyObservables``
+        (``energy_observables()``): the same run, the cells live in the space of the K functional values (``centres`` is
+        (M, K); every block is evaluated into a derived ring first).
+
+        ValueError, before anything runs: n_iter < 2, centres that are not (M, K) with 1 <= M <= 64 or not finite, a radius
+        that is negative, NaN or of another size, a sharded sampler (the tables are additive over ranks, but summing them is
+        out of scope here)."""
+        n_iter = int(n_iter)
+        K = self.ndims if of is None else of.n_values
+        if self._comm is not None:
+            raise ValueError('occupancy: a sharded sampler (comm set) is not supported -- the tables are additive over ranks, '
+                             'but summing them is out of scope here')
+        if n_iter < 2:
+            raise ValueError('n_iter must be >= 2 (a transition takes two states), got %d' % n_iter)
+        centres = np.ascontiguousarray(np.asarray(centres, dtype=np.float64))
+        if centres.ndim != 2 or centres.shape[1] != K or not 1 <= centres.shape[0] <= 64:
+            raise ValueError('centres must be (M, %s = %d) with 1 <= M <= 64, got an array of shape %r'
+                             % ('ndims' if of is None else 'n_values', K, centres.shape))
+        if not np.all(np.isfinite(centres)):
+            raise ValueError('centres must be finite')
+        M, r2 = centres.shape[0], None
+        if radius is not None:
+            radius = np.asarray(radius, dtype=np.float64)
+            if radius.size not in (1, M):
+                raise ValueError('radius must be a scalar or have M = %d entries' % M)
+            radius = np.array(np.broadcast_to(radius.reshape(-1), (M,)))
+            if not np.all(radius >= 0):                   # (NaN fails it too)
+                raise ValueError('radius must not be negative or NaN')
+            r2 = radius * radius
+        self._check_of(of)
+        grad0 = self.distribution.dEdX_count
+        occ, q, done = None, 1.0, 0
+        with self._RecordedRun(self, [n_iter], block, of) as run:
+            for _, k in run.blocks():
+                if occ is None:
+                    if run.lead:
+                        W, _, _, _, n_first = run.first_block_sums(k)
+                        q = 2.0 ** (np.floor(np.log2(W / n_first)) - 24)
+                    occ = run.own(run.src.occupancy(centres, r2, q))
+                occ.accumulate(0, k, w_slot0=run.w_slot0, linked=done > 0)
+                done += k
+            run.finish()
+            tables = occ.read()
+        return Occupancy(tables, q, centres, tables['n_states'], self.distribution.dEdX_count - grad0)
 
     def paths(self, n_iter, n_grid=None, dt=None, block=None):
         """A fair sample of every chain with its time order kept: the process "chain p sits in state k for its holding
