@@ -195,6 +195,24 @@ int mjhmc_energy_create_linear_tall(mjhmc_ctx* ctx, int ndims, int64_t nexperts,
                                     const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out);
 /* compile-only check of a tall linear-model energy (needs no device): 0, MJHMC_ERR_INVALID, MJHMC_ERR_UNSUPPORTED as above */
 int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
+/* Wide linear-model energies: the same form and the same expressions with MORE dims than 512 -- 1 <= ndims <= 4096,
+ * 1 <= nexperts <= 2^20 (a regression with a thousand coefficients).  Always blocks of 512: the experts in
+ * nblk = ceil(nexperts / 512) blocks, the dims in ND = ceil(ndims / 512) chunks, every (block, chunk) a zero-padded
+ * 512 x 512 matrix, and one fused matrix-core kernel (compiled with hipRTC at creation, cached per process) walks them per
+ * tile of 32 particles: per block u = b + sum over the chunks, ascending, of W x; then dE/dx chunk by chunk, kept in the
+ * caller's dE/dX rows between blocks.  u = W x + b and f'(u) never reach memory; one launch per evaluation; the result
+ * depends on the model and the row alone, bit for bit.  j is the GLOBAL expert index.  The kind is MJHMC_E_LINEAR_EXPR;
+ * samplers run the engine's multi-pass path with either state dtype on rows of pitch 512 ND, so everything built on the ring
+ * works, except the passes that take at most 512 dims: mjhmc_pointwise_create and mjhmc_influence_create refuse a wide
+ * energy (MJHMC_ERR_UNSUPPORTED).  ndims <= 512 is legal: one chunk, the operations of the tall form at P = 512 in the same
+ * order.  ndims > 4096 or nexperts > 2^20: MJHMC_ERR_UNSUPPORTED, naming the limit; sizes < 1, NULLs, more than 4 expert rows,
+ * non-finite W / b, compile errors (with the log): MJHMC_ERR_INVALID, sizes before the context is looked at.  Device memory of
+ * the matrices: 2 * nblk * ND * 512 * 512 * 4 bytes (reported when the allocation fails). */
+int mjhmc_energy_create_linear_wide(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
+                                    const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                                    const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out);
+/* compile-only check of a wide linear-model energy (needs no device): 0, MJHMC_ERR_INVALID, MJHMC_ERR_UNSUPPORTED as above */
+int mjhmc_linear_wide_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
 /* Grouped linear-model energies: the tall form with a log-sum-exp over groups of experts,
  *     E(x) = sum_{j<K} f(u_j, j) + sum_{g<G} LSE_{c<C} u_{gC+c},   dE/dx = W^T phi,   phi_j = f'(u_j, j) + [j < G C] softmax_g(u)_c
  * -- multinomial logistic (softmax) regression: G = n_groups data rows of C = group_size classes as the FIRST G C experts

@@ -64,6 +64,9 @@ PROTOTYPES = {
     'mjhmc_energy_create_linear_tall': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, _P, _P, ctypes.c_char_p, ctypes.c_char_p,
                                                        _P, ctypes.c_size_t, _P, ctypes.c_int, ctypes.c_char_p, _P]),
     'mjhmc_linear_tall_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
+    'mjhmc_energy_create_linear_wide': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, _P, _P, ctypes.c_char_p, ctypes.c_char_p,
+                                                       _P, ctypes.c_size_t, _P, ctypes.c_int, ctypes.c_char_p, _P]),
+    'mjhmc_linear_wide_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
     'mjhmc_energy_create_linear_grouped': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64, _P, _P, ctypes.c_int, ctypes.c_int64,
                                                           ctypes.c_char_p, ctypes.c_char_p, _P, ctypes.c_size_t, _P, ctypes.c_int,
                                                           ctypes.c_char_p, _P]),

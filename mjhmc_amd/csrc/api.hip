@@ -82,9 +82,9 @@ int check_state_dtype(const mjhmc_energy* e, int dtype) {
 int shape_for(const mjhmc_energy* e, int* dtype, Shape* sh) {
   if (e->is_pot()) {
     if (*dtype != MJHMC_F64 && *dtype != MJHMC_F32) return fail(MJHMC_ERR_UNSUPPORTED, "PRODUCT_OF_T and LINEAR_EXPR run with float32 or float64 state");
-    if (*dtype == MJHMC_F64 || e->pot_big() || e->lin_tall()) {
+    if (*dtype == MJHMC_F64 || e->pot_big() || e->lin_tall() || e->lin_wide()) {
       // the reference's own arithmetic: float64 HMCState arrays around the float32 force (distributions.py:408-415,
-      // hmc_state.py:29-38); ndims > 512 and tall linear models: their force evaluation exists on the multi-pass path only
+      // hmc_state.py:29-38); ndims > 512, tall and wide linear models: their force evaluation exists on the multi-pass path only
       *sh = Shape{0, 0, e->pot_dim, e->pot_dim / 2, 8, true};
       sh->round32 = *dtype != MJHMC_F64;
     } else {
@@ -405,8 +405,8 @@ int mjhmc_expr_check(int ndims, const char* energy_expr, const char* grad_expr, 
   return mjhmc_expr_check_coupled(ndims, nullptr, energy_expr, nullptr, grad_expr, include_dir);
 }
 
-// What the three mjhmc_energy_create_linear* share; each entry point keeps its own order of checks (sizes before ctx for
-// the tall and the grouped form, after it for the square one).
+// What the mjhmc_energy_create_linear* entry points share; each entry point keeps its own order of checks (sizes before ctx for
+// the tall, grouped and wide forms, after it for the square one).
 static int linear_check_model(const double* W, const double* b, const double* params, size_t nparams, const double* expert_params,
                               int n_expert_rows) {
   if (!W || !b) return fail(MJHMC_ERR_INVALID, "W or b is NULL");
@@ -475,6 +475,27 @@ int mjhmc_linear_tall_check(int ndims, int64_t nexperts, const char* energy_expr
   std::string err;
   const RtcCode* c = nullptr;
   const int rc = linear_tall_compile(energy_expr, grad_expr, tall_pad(ndims), include_dir, &err, &c);
+  return rc ? fail(rc, err) : 0;
+}
+
+int mjhmc_energy_create_linear_wide(mjhmc_ctx* ctx, int ndims, int64_t nexperts, const double* W, const double* b,
+                                    const char* energy_expr, const char* grad_expr, const double* params, size_t nparams,
+                                    const double* expert_params, int n_expert_rows, const char* include_dir, mjhmc_energy** out) {
+  TRY(linear_wide_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  if (!ctx || !out) return fail(MJHMC_ERR_INVALID, "NULL argument");
+  TRY(linear_check_model(W, b, params, nparams, expert_params, n_expert_rows));
+  TRY(linear_check_finite(ndims, nexperts, W, b));
+  return linear_energy_shell(ctx, ndims, out, [&](mjhmc_energy* e) {
+    return linear_wide_energy_build(e, nexperts, W, b, energy_expr, grad_expr, params, nparams, expert_params, n_expert_rows,
+                                    include_dir);
+  });
+}
+
+int mjhmc_linear_wide_check(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
+  TRY(linear_wide_check_args(ndims, nexperts, energy_expr, grad_expr, include_dir));
+  std::string err;
+  const RtcCode* c = nullptr;
+  const int rc = linear_wide_compile(energy_expr, grad_expr, include_dir, &err, &c);
   return rc ? fail(rc, err) : 0;
 }
 

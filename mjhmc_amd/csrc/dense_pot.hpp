@@ -51,6 +51,16 @@ struct LinTallModel {
   int nblk, D, K;
 };
 
+// A wide linear-model energy (more dims than the tile kernels hold; dense_lin_wide.hpp): the tall layout's
+// blocks of 512 experts with a dim chunk index added -- ND = Dpad / 512 chunks of 512 dims, every (block, chunk) a
+// 512 x 512 matrix laid out like a <= 512 model's, zero padded (compare PotBigModel)
+struct LinWideModel {
+  const float* W1w;    // [jb][dc][d][j] = W[512 jb + j][512 dc + d]   (u += W1w[jb][dc]^T x_dc, from cb[jb])
+  const float* W2Tw;   // [jb][dc][j][d] = W[512 jb + j][512 dc + d]   (dE/dx_dc += W2Tw[jb][dc]^T phi(u))
+  const float* cb;     // [512 nblk]     = b
+  int nblk, ND, D, K;
+};
+
 // Rates, waiting times and first minimum of ONE particle, evaluated serially by one lane (the dense
 // kernels run it on 32 lanes of one wave, one particle each; ~1e3 instructions against ~1e6 cycles of
 // trajectory).  markov_jump_hmc.py:366-396, utils.py:15-49.  Returns k (0 L, 1 F, 2 R).

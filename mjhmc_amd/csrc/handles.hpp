@@ -49,7 +49,8 @@ struct mjhmc_energy {
   int pot_dim = kPotDim;  // rows padded to 128, 256 or 512 -- or, beyond the tile kernels, to a multiple of 512 (pot_big())
   int pot_rows = 0;       // LINEAR_EXPR: max(ndims, nexperts), the rows the matrices may hold (0: ndims)
   PotModel pot_model() const { return PotModel{pot[0], pot[1], pot[2], pot[3], pot_dim, pot_rows ? pot_rows : ep.ndims}; }
-  bool pot_big() const { return is_pot() && pot_dim > kPotDim; }   // matrices stored as 512 x 512 blocks, multi-pass path only
+  // ProductOfT beyond the tile kernels: matrices stored as 512 x 512 blocks, multi-pass path only (never a linear model)
+  bool pot_big() const { return is_pot() && !lin && pot_dim > kPotDim; }
   PotBigModel pot_big_model() const { return PotBigModel{pot[0], pot[1], pot[2], pot[3], pot_dim, ep.ndims}; }
   // the ProductOfT tile kernels' energies: ProductOfT itself and the linear-model energies, which run its kernels (and every
   // path of it) with their own experts (linear_energy.hip; never pot_big())
@@ -59,6 +60,9 @@ struct mjhmc_energy {
   // a tall linear model (more than 512 experts allowed; pot_dim: the pad of ndims): one fused force kernel, no tile
   // kernels -- routed like pot_big(), to the multi-pass path (is_pot() stays true, pot_big() false)
   bool lin_tall() const { return lin && lin->tall; }
+  // a wide linear model (up to 4096 dims; pot_dim: ndims rounded up to a multiple of 512, the pitch of its rows): one fused
+  // force kernel over expert blocks x dim chunks, no tile kernels -- routed like pot_big() and lin_tall()
+  bool lin_wide() const { return lin && lin->wide; }
   void* sic[3] = {nullptr, nullptr, nullptr};  // SparseImageCode: A1, A2 (bf16, fragment order), y (float32 [P][256])
   float sic_lambda = 0.f;
   int sic_cauchy = 1;

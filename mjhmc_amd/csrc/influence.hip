@@ -156,6 +156,10 @@ int mjhmc_influence_create(mjhmc_sampler* s, const char* value, int64_t j0, int6
                                              "are not formed: its experts are stored in a permuted order and the terms of a group "
                                              "are coupled through its log-sum-exp, while this pass reports per expert in the "
                                              "caller's order");
+  if (e->lin_wide())
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the influence of a data row of a wide linear model (mjhmc_energy_create_linear_wide) is not formed: "
+                                             "the per-expert passes take models of at most 512 dims, stored in one chunk of "
+                                             "dims per block of experts");
   if (s->dtype != MJHMC_F64 && s->dtype != MJHMC_F32)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "linear models run with float32 or float64 state");
   if (!s->ring) return acc_no_ring(nullptr);

@@ -942,7 +942,7 @@ static ScheduleInputs schedule_inputs(const mjhmc_sampler* s, int n_iter, const 
               : fused_rows(s) ? EnergyFamily::Rows
                               : EnergyFamily::Other;
   in.wide = s->sh.wide;
-  in.pot64_tile = e->is_pot() && !e->pot_big() && !e->lin_tall() && !s->sh.round32;
+  in.pot64_tile = e->is_pot() && !e->pot_big() && !e->lin_tall() && !e->lin_wide() && !s->sh.round32;
   in.N = s->N;
   in.D = s->D;
   in.logG = s->sh.logG;

@@ -14,7 +14,9 @@
 // Models with more experts than 512 (K <= 2^20, D <= 512) are the second half of this file: one fused kernel over expert
 // blocks (dense_lin_tall.hpp) as the force of the multi-pass path.  Grouped models (a log-sum-exp
 // over groups of experts: softmax regression) are the third part: the tall form with a permuted layout and a kernel of its
-// own (dense_lin_grouped.hpp).
+// own (dense_lin_grouped.hpp).  Models with more dims than 512 (D <= 4096, K <= 2^20) are the fourth:
+// the tall form's blocks with a dim chunk index, one fused kernel over expert blocks x dim chunks (dense_lin_wide.hpp,
+// DESIGN.md section 3.6e).
 // What the forms share stands once: every compile is "source, name expressions, rtc_compile_cached" (user_expr.hpp: one
 // cache for the process), every builder loads its module through linear_module_load and puts its model on the device through
 // linear_model_upload (slots in blocks of P and a slot -> expert map: one block and the identity for the square form, the
@@ -88,6 +90,18 @@ std::string linear_tall_source(const std::string& energy_expr, const std::string
   s += user_functor_source(energy_expr, grad_expr);
   s += "template <int NB>\n__global__ __launch_bounds__(256, 1) void lin_tall_eval_kernel(const PotEvalArgs a, const LinTallModel tm, const PotLinear lin) {\n";
   s += "  __shared__ Shared<NB> sh;\n  lin_tall_eval_tiles<NB, LinUserF>(a, tm, lin, sh);\n}\n";
+  s += "}  // namespace mjhmc\n";
+  return s;
+}
+
+// A wide model's one kernel (dense_lin_wide.hpp; always the NB = 4 tile code): a source and a cache key of its own
+std::string linear_wide_source(const std::string& energy_expr, const std::string& grad_expr) {
+  std::string s;
+  s += "#include \"dense_lin_wide.hpp\"\n";
+  s += "namespace mjhmc {\n";
+  s += user_functor_source(energy_expr, grad_expr);
+  s += "__global__ __launch_bounds__(256, 1) void lin_wide_eval_kernel(const PotEvalArgs a, const LinWideModel wm, const PotLinear lin) {\n";
+  s += "  __shared__ Shared<4> sh;\n  lin_wide_eval_tiles<LinUserF>(a, wm, lin, sh);\n}\n";
   s += "}  // namespace mjhmc\n";
   return s;
 }
@@ -170,19 +184,21 @@ int linear_module_load(LinearEnergy* l, const RtcCode& c, const std::vector<hipF
   return 0;
 }
 
-// The model on the device, float32, in the blocked layout: S slots in blocks of P (the state rows' pitch), slot
-// blk P + local holding the caller's expert j = expert(slot), -1 for padding (zero):
-//     W1b[blk][d][local] = W2Tb[blk][local][d] = W[j][d]     (u = W1b[blk]^T x + cb[blk]; dE/dx += W2Tb[blk]^T phi(u))
-// cb = b and the per-expert rows q[m] (rows of S floats) in slot order, the shared parameters behind them.  One block and
-// the identity map are a <= 512 model in ProductOfT's own layout.  `form` words the allocation failure ("a tall").
+// The model on the device, float32, in the blocked layout: S slots in blocks of P, slot blk P + local holding the caller's
+// expert j = expert(slot), -1 for padding (zero), and the dims in ND chunks of P (the state rows' pitch is P ND; one chunk
+// for every form but the wide one):
+//     W1b[blk][dc][dl][local] = W2Tb[blk][dc][local][dl] = W[j][P dc + dl]
+//     (u = cb[blk] + sum_dc W1b[blk][dc]^T x_dc; dE/dx_dc += W2Tb[blk][dc]^T phi(u))
+// cb = b and the per-expert rows q[m] (rows of S floats) in slot order, the shared parameters behind them.  One block, one
+// chunk and the identity map are a <= 512 model in ProductOfT's own layout.  `form` words the allocation failure ("a tall").
 int linear_model_upload(mjhmc_energy* e, int P, size_t S, int K, const double* W, const double* b, const double* params,
                         size_t nparams, const double* expert_params, int n_expert_rows,
-                        const std::function<int64_t(int64_t)>& expert, const char* form) {
+                        const std::function<int64_t(int64_t)>& expert, const char* form, int ND = 1) {
   const int D = e->ep.ndims;
   LinearEnergy* l = e->lin;
-  e->pot_dim = P;
-  const size_t M = (size_t)P * P, mat_bytes = S * P * sizeof(float), nrows = (size_t)4 * S + (nparams ? nparams : 1);
-  std::vector<float> w1(S * P, 0.f), w2t(S * P, 0.f), cb(S, 0.f), rows(nrows, 0.f);
+  e->pot_dim = P * ND;
+  const size_t M = (size_t)P * P, mat_bytes = S * P * ND * sizeof(float), nrows = (size_t)4 * S + (nparams ? nparams : 1);
+  std::vector<float> w1(S * P * ND, 0.f), w2t(S * P * ND, 0.f), cb(S, 0.f), rows(nrows, 0.f);
   for (size_t slot = 0; slot < S; ++slot) {
     const int64_t j = expert((int64_t)slot);
     if (j < 0) continue;
@@ -190,8 +206,9 @@ int linear_model_upload(mjhmc_energy* e, int P, size_t S, int K, const double* W
     cb[slot] = (float)b[j];
     for (int d = 0; d < D; ++d) {
       const float w = (float)W[(size_t)j * D + d];
-      w1[blk * M + (size_t)d * P + jl] = w;
-      w2t[blk * M + jl * P + d] = w;
+      const size_t m = (blk * ND + (size_t)(d / P)) * M, dl = (size_t)(d % P);
+      w1[m + dl * P + jl] = w;
+      w2t[m + jl * P + dl] = w;
     }
     for (int m = 0; m < n_expert_rows; ++m) rows[(size_t)m * S + slot] = (float)expert_params[(size_t)m * K + j];
   }
@@ -204,7 +221,7 @@ int linear_model_upload(mjhmc_energy* e, int P, size_t S, int K, const double* W
       e->pot[i] = nullptr;
       return mjhmc_fail(MJHMC_ERR_HIP, std::string(form) + " LINEAR_EXPR model of " + std::to_string(D) + " dims x " + std::to_string(K) +
                                        " experts needs " + std::to_string(2 * mat_bytes) + " bytes of device memory for its matrices (" +
-                                       std::to_string(S / P) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
+                                       std::to_string(S / P * ND) + " blocks of " + std::to_string(P) + " x " + std::to_string(P) +
                                        ", twice): the allocation failed");
     }
     HIPCHK(hipMemcpy(e->pot[i], src[i], bytes[i], hipMemcpyHostToDevice));
@@ -312,6 +329,68 @@ void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E
   const LinGroupedModel gm{e->pot[0], e->pot[1], e->pot[2], e->lin->grp_nbg, e->lin->grp_nbp, e->ep.ndims, e->lin->tall_K, e->lin->grp_G};
   void* params[] = {(void*)&a, e->lin->grouped() ? (void*)&gm : (void*)&tm, (void*)&lin};
   (void)hipModuleLaunchKernel(e->lin->tall, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Wide models: 1 <= D <= 4096, 1 <= K <= 2^20.  Always blocks of 512: the experts in
+// nblk = ceil(K / 512) blocks, the dims in ND = ceil(D / 512) chunks, and one generated kernel that walks them
+// (dense_lin_wide.hpp).  The energy keeps the kind MJHMC_E_LINEAR_EXPR and is_pot(); its samplers run the multi-pass path
+// (lin_wide(), handles.hpp) on rows of pitch 512 ND, whose float32 force this kernel is.
+// ---------------------------------------------------------------------------------------------------------------------
+int linear_wide_check_args(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir) {
+  if (!energy_expr || !grad_expr || !include_dir) return mjhmc_fail(MJHMC_ERR_INVALID, "NULL argument");
+  if (ndims < 1 || nexperts < 1) return mjhmc_fail(MJHMC_ERR_INVALID, "LINEAR_EXPR needs ndims >= 1 and nexperts >= 1");
+  if (ndims > kLinWideMaxDims)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a wide LINEAR_EXPR model takes at most 4096 dims (got " + std::to_string(ndims) +
+                                             "): 8 chunks of the tile kernels' 512");
+  if (nexperts > kLinTallMaxExperts)
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "a wide LINEAR_EXPR model takes at most 1048576 (2^20) experts (got " +
+                                             std::to_string(nexperts) + ")");
+  return 0;
+}
+
+int linear_wide_compile(const std::string& energy_expr, const std::string& grad_expr, const std::string& include_dir,
+                        std::string* err, const RtcCode** out) {
+  return rtc_compile_cached(linear_wide_source(energy_expr, grad_expr), "mjhmc_linear_wide.hip", {"mjhmc::lin_wide_eval_kernel"},
+                            include_dir, kEnergyWords, out, err);
+}
+
+int linear_wide_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, const char* energy_expr,
+                             const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
+                             int n_expert_rows, const char* include_dir) {
+  const int D = e->ep.ndims, K = (int)nexperts, P = kPotDim, nblk = (K + P - 1) / P, ND = (D + P - 1) / P;
+  LinearEnergy* l = e->lin = new LinearEnergy();
+  const RtcCode* c = nullptr;
+  std::string err;
+  const int rc = linear_wide_compile(energy_expr, grad_expr, include_dir, &err, &c);
+  if (rc) return mjhmc_fail(rc, err);
+  TRY(linear_module_load(l, *c, {&l->wide}));
+  l->tall_nblk = nblk;
+  l->tall_K = K;
+  l->wide_nd = ND;
+  e->pot_rows = D;
+  return linear_model_upload(e, P, (size_t)nblk * P, K, W, b, params, nparams, expert_params, n_expert_rows,
+                             [K](int64_t slot) { return slot < K ? slot : -1; }, "a wide", ND);
+}
+
+void lin_wide_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st) {
+  PotEvalArgs a;
+  a.X = X32;
+  a.G = G32;
+  a.E = E32;
+  a.EV = nullptr;
+  a.V = nullptr;
+  a.V_gen = nullptr;
+  a.N = nrows;
+  a.ntiles = rows_pad / 32;
+  a.first_pid = 0;
+  a.D = e->ep.ndims;
+  a.key = RngKey{0u, 0u, 0u, 0u};
+  const PotLinear lin = e->lin->gen.lin;
+  const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, resident_cus());
+  const LinWideModel wm{e->pot[0], e->pot[1], e->pot[2], e->lin->tall_nblk, e->lin->wide_nd, e->ep.ndims, e->lin->tall_K};
+  void* params[] = {(void*)&a, (void*)&wm, (void*)&lin};
+  (void)hipModuleLaunchKernel(e->lin->wide, grid, 1, 1, 256, 1, 1, 0, st, params, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

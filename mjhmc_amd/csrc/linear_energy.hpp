@@ -23,6 +23,10 @@ struct LinearEnergy {
   // grp_nbp plain ones (tall_nblk in all), grp_C members per group (0: not grouped), grp_G groups
   int grp_C = 0, grp_G = 0, grp_nbg = 0, grp_nbp = 0;
   bool grouped() const { return grp_C != 0; }
+  // a wide model (more than 512 dims allowed): its one kernel, lin_wide_eval_kernel, over tall_nblk blocks
+  // of 512 experts x wide_nd chunks of 512 dims (tall_K experts); `tall` and the tile kernels of `gen` are then absent
+  hipFunction_t wide = nullptr;
+  int wide_nd = 0;
 };
 
 constexpr int64_t kLinTallMaxExperts = (int64_t)1 << 20;
@@ -50,6 +54,20 @@ int linear_tall_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W,
                              int n_expert_rows, const char* include_dir);
 // E (or none) and dE/dX (or none) of float32 rows X32 [rows_pad][pad of ndims] (rows_pad a multiple of 32) on `st`
 void lin_tall_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st);
+
+// Wide models: 1 <= ndims <= 4096 (kLinWideMaxDims), 1 <= nexperts <= 2^20, experts in blocks of 512, dims
+// in chunks of 512 (ndims <= 512: one chunk)
+constexpr int kLinWideMaxDims = 4096;
+int linear_wide_check_args(int ndims, int64_t nexperts, const char* energy_expr, const char* grad_expr, const char* include_dir);
+// the hipRTC compile of lin_wide_eval_kernel: its own small source, its own cache key
+int linear_wide_compile(const std::string& energy_expr, const std::string& grad_expr, const std::string& include_dir,
+                        std::string* err, const RtcCode** out);
+int linear_wide_energy_build(mjhmc_energy* e, int64_t nexperts, const double* W, const double* b, const char* energy_expr,
+                             const char* grad_expr, const double* params, size_t nparams, const double* expert_params,
+                             int n_expert_rows, const char* include_dir);
+// E (or none) and dE/dX (or none) of float32 rows X32 [rows_pad][e->pot_dim] (rows_pad a multiple of 32) on `st`; G32 needs
+// no zeroing
+void lin_wide_eval(const mjhmc_energy* e, const float* X32, float* G32, float* E32, int64_t rows_pad, int64_t nrows, hipStream_t st);
 
 // Grouped models: the first n_groups * group_size experts are groups under a log-sum-exp, stored so that
 // a group lies in one lane's registers (dense_lin_grouped.hpp); 2 <= group_size <= 16, at most 2^20 slots

@@ -227,6 +227,10 @@ int mjhmc_pointwise_create(mjhmc_sampler* s, const char* values, unsigned lme_ma
                                              "are not formed: its experts are stored in a permuted order and the terms of a group "
                                              "are coupled through its log-sum-exp, while this pass reports per expert in the "
                                              "caller's order (its per-row pass is mjhmc_pointwise_create_grouped)");
+  if (e->lin_wide())
+    return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "the pointwise statistics of a wide linear model (mjhmc_energy_create_linear_wide) are not formed: "
+                                             "the per-expert passes take models of at most 512 dims, stored in one chunk of "
+                                             "dims per block of experts");
   if (s->dtype != MJHMC_F64 && s->dtype != MJHMC_F32)
     return mjhmc_fail(MJHMC_ERR_UNSUPPORTED, "linear models run with float32 or float64 state");
   if (!s->ring) return acc_no_ring(nullptr);

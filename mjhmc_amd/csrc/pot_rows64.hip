@@ -46,7 +46,8 @@ __global__ void hk_pot_close(double* __restrict__ V, const float* __restrict__ G
 }
 
 // the float32 force on rows buf[0] ([rows_pad][pitch] float32) -> dE/dX rows buf[1] (or none) and E buf[2] (or none): the
-// tile kernel's evaluation up to 512 dims, the blocked evaluation (buf[3]: its u rows) beyond
+// tile kernel's evaluation up to 512 dims, the blocked evaluation (buf[3]: its u rows) beyond, the fused kernel of a tall or
+// wide linear model
 void pot_force32(mjhmc_sampler* s, float* const* buf, bool want_G, bool want_E, int64_t rows_pad, int64_t nrows) {
   if (s->en->pot_big()) {
     pot_big_eval(s->en->pot_big_model(), buf[0], want_G ? buf[1] : nullptr, want_E ? buf[2] : nullptr, buf[3], rows_pad, s->stream);
@@ -54,6 +55,10 @@ void pot_force32(mjhmc_sampler* s, float* const* buf, bool want_G, bool want_E, 
   }
   if (s->en->lin_tall()) {   // the fused block-by-block kernel of a tall linear model (no u rows: buf[3] is not used)
     lin_tall_eval(s->en, buf[0], want_G ? buf[1] : nullptr, want_E ? buf[2] : nullptr, rows_pad, nrows, s->stream);
+    return;
+  }
+  if (s->en->lin_wide()) {   // the fused kernel of a wide linear model: rows of pitch 512 ND, dE/dX rows that need no zeroing
+    lin_wide_eval(s->en, buf[0], want_G ? buf[1] : nullptr, want_E ? buf[2] : nullptr, rows_pad, nrows, s->stream);
     return;
   }
   PotEvalArgs a;

@@ -99,16 +99,20 @@ class Context(object):
 
 
 TALL_MAX_EXPERTS = 2 ** 20      # mjhmc_energy_create_linear_tall
+WIDE_MAX_DIMS = 4096            # mjhmc_energy_create_linear_wide
 
 
-def linear_arrays(W, b, params=(), expert_params=None, _tall=False):
+def linear_arrays(W, b, params=(), expert_params=None, _tall=False, _wide=False):
     """The checked float64 arrays of a linear-model energy: W (K, D), b (K,), params (n,), expert_params (M <= 4, K).
     Raises ValueError on a shape the device form does not take (before any device call)."""
     W = np.ascontiguousarray(W, dtype=np.float64)
     if W.ndim != 2 or W.shape[0] < 1 or W.shape[1] < 1:
         raise ValueError('W must be a (K, D) matrix, got shape %r' % (W.shape,))
     K, D = W.shape
-    if _tall:
+    if _wide:
+        if K > TALL_MAX_EXPERTS or D > WIDE_MAX_DIMS:
+            raise ValueError('wide linear-model energies take at most 2**20 experts and 4096 dims (W is %d x %d)' % (K, D))
+    elif _tall:
         if K > TALL_MAX_EXPERTS or D > 512:
             raise ValueError('tall linear-model energies take at most 2**20 experts and 512 dims (W is %d x %d)' % (K, D))
     elif K > 512 or D > 512:
@@ -128,6 +132,11 @@ def linear_arrays(W, b, params=(), expert_params=None, _tall=False):
 def tall_linear_arrays(W, b, params=(), expert_params=None):
     """linear_arrays for a tall model (mjhmc_energy_create_linear_tall): W (K, D) with D <= 512 and K <= 2**20."""
     return linear_arrays(W, b, params, expert_params, _tall=True)
+
+
+def wide_linear_arrays(W, b, params=(), expert_params=None):
+    """linear_arrays for a wide model (mjhmc_energy_create_linear_wide): W (K, D) with D <= 4096 and K <= 2**20."""
+    return linear_arrays(W, b, params, expert_params, _wide=True)
 
 
 GROUP_MAX = 16                  # mjhmc_energy_create_linear_grouped: members of a group
@@ -220,6 +229,16 @@ class DeviceEnergy(object):
         return self
 
     @classmethod
+    def from_linear_wide(cls, ctx, W, b, energy_expr, grad_expr, params=(), expert_params=None):
+        """The same form with more dims than the tile kernels hold (mjhmc_energy_create_linear_wide): W (K, D),
+        1 <= D <= 4096, 1 <= K <= 2**20, blocks of 512 experts x chunks of 512 dims under one fused matrix-core kernel; ``j``
+        in the expressions is the global expert index.  Samplers of it run the engine's multi-pass path."""
+        self = cls._linear(ctx, 'mjhmc_energy_create_linear_wide', wide_linear_arrays(W, b, params, expert_params), energy_expr,
+                           grad_expr)
+        self.wide = True
+        return self
+
+    @classmethod
     def from_linear_grouped(cls, ctx, W, b, groups, energy_expr, grad_expr, params=(), expert_params=None):
         """The tall form with a log-sum-exp over groups of experts (mjhmc_energy_create_linear_grouped):
             E(x) = sum_j f(u_j, j) + sum_{g<G} LSE_{c<C} u_{gC+c},   dE/dx = W^T (f'(u) + softmax within the groups);
@@ -234,7 +253,7 @@ class DeviceEnergy(object):
 
     @classmethod
     def _linear(cls, ctx, create, arrays, energy_expr, grad_expr, groups=()):
-        """Behind from_linear, from_linear_tall and from_linear_grouped: the checked arrays (W, b, params, expert_params)
+        """Behind from_linear, from_linear_tall, from_linear_wide and from_linear_grouped: the checked arrays (W, b, params, expert_params)
         handed to the entry point ``create``, which takes ``groups`` (C, G; the grouped form alone) behind b."""
         W, b, params, q = arrays
         self = cls.__new__(cls)

@@ -47,13 +47,14 @@ class Distribution(object):
             kind, params = self.device_energy()
             if kind == _lib.E_USER_EXPR:                   # params = (energy_expr, grad_expr, float64 parameters, stats, energy0_expr)
                 self._dev = engine.DeviceEnergy.from_expr(engine.context(device), self.ndims, *params)
-            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=[, tall=][, groups=])
+            elif kind == _lib.E_LINEAR_EXPR:               # params = dict(W=, b=, energy=, grad=, params=, expert_params=[, tall=][, wide=][, groups=])
                 if params.get('groups'):
                     self._dev = engine.DeviceEnergy.from_linear_grouped(
                         engine.context(device), params['W'], params.get('b'), params['groups'], params['energy'], params['grad'],
                         params.get('params', ()), params.get('expert_params'))
                 else:
-                    make = engine.DeviceEnergy.from_linear_tall if params.get('tall') else engine.DeviceEnergy.from_linear
+                    make = (engine.DeviceEnergy.from_linear_wide if params.get('wide') else
+                            engine.DeviceEnergy.from_linear_tall if params.get('tall') else engine.DeviceEnergy.from_linear)
                     self._dev = make(engine.context(device), params['W'], params.get('b'), params['energy'], params['grad'],
                                      params.get('params', ()), params.get('expert_params'))
             elif kind == _lib.E_HOST:                      # params = (energy_func, energy_grad_func): opaque callables
@@ -176,6 +177,11 @@ class LambdaDistribution(Distribution):
       fused matrix-core kernel that walks the experts in blocks of the padded D (mjhmc_energy_create_linear_tall); ``j`` is
       the global expert index.  Samplers run the engine's multi-pass path with either ``state_dtype``; the callables are
       checked at the same float32-force bar;
+    * ``device_linear_wide=dict(W=, b=, energy=, grad=, params=(), expert_params=None)``: the same contract for a model
+      with more dims than 512 -- W (K, D), D <= 4096, K <= 2**20 (a regression with a thousand coefficients) -- on one fused
+      matrix-core kernel that walks blocks of 512 experts x chunks of 512 dims (mjhmc_energy_create_linear_wide); ``j`` is
+      the global expert index.  The multi-pass path with either ``state_dtype``, the same bar; the per-expert passes
+      (``pointwise``, ``waic``, ``influence``) and ``cv_expectations`` take at most 512 dims and refuse it;
     * ``device_linear_grouped=dict(W=, b=, groups=(C, G), energy=, grad=, params=(), expert_params=None)``: the tall contract
       plus a log-sum-exp over groups of experts, ``E(x) = sum_j energy(u_j, j) + sum_{g<G} LSE_{c<C} u_{gC+c}`` -- the
       first G * C rows of W are G groups of C consecutive experts (softmax regression: a data row per group, a class per
@@ -186,7 +192,7 @@ class LambdaDistribution(Distribution):
 
     def __init__(self, energy_func=None, energy_grad_func=None, init=None, name=None, device_energy=None,
                  device_expr=None, device_params=(), device_linear=None, state_dtype='float64', device_linear_tall=None,
-                 device_linear_grouped=None):
+                 device_linear_grouped=None, device_linear_wide=None):
         self.energy_func = energy_func
         self.energy_grad_func = energy_grad_func
         self.init = np.array(init, dtype=np.float64)
@@ -194,9 +200,10 @@ class LambdaDistribution(Distribution):
         self._functor = device_energy
         self._checked = False
         self._bar32 = False
-        if sum(m is not None for m in (device_linear, device_linear_tall, device_linear_grouped)) > 1:
-            raise ValueError('give device_linear or device_linear_tall, not both' if device_linear_grouped is None else
-                             'give one of device_linear, device_linear_tall and device_linear_grouped')
+        if sum(m is not None for m in (device_linear, device_linear_tall, device_linear_grouped, device_linear_wide)) > 1:
+            raise ValueError('give device_linear or device_linear_tall, not both'
+                             if device_linear_grouped is None and device_linear_wide is None else
+                             'give one of device_linear, device_linear_tall, device_linear_wide and device_linear_grouped')
         if device_linear_grouped is not None:
             if state_dtype not in ('float32', 'float64'):
                 raise ValueError("device_linear state_dtype must be 'float32' or 'float64'")
@@ -211,18 +218,19 @@ class LambdaDistribution(Distribution):
             self._functor = (_lib.E_LINEAR_EXPR, dict(W=W, b=b, energy=str(lin['energy']), grad=str(lin['grad']), params=params,
                                                       expert_params=q, tall=True, groups=groups))
             self._bar32 = True
-        elif device_linear is not None or device_linear_tall is not None:
-            tall = device_linear_tall is not None
+        elif device_linear is not None or device_linear_tall is not None or device_linear_wide is not None:
+            tall, wide = device_linear_tall is not None, device_linear_wide is not None
             if state_dtype not in ('float32', 'float64'):
                 raise ValueError("device_linear state_dtype must be 'float32' or 'float64'")
             self.state_dtype = state_dtype
-            lin = dict(device_linear_tall if tall else device_linear)
+            lin = dict(device_linear_wide if wide else device_linear_tall if tall else device_linear)
             W, b, params, q = engine.linear_arrays(lin['W'], lin.get('b'), lin.get('params', ()), lin.get('expert_params'),
-                                                   _tall=tall)
+                                                   _tall=tall, _wide=wide)
             if W.shape[1] != self.init.shape[0]:
                 raise ValueError('W has %d columns but init has %d dims' % (W.shape[1], self.init.shape[0]))
             self._functor = (_lib.E_LINEAR_EXPR, dict(W=W, b=b, energy=str(lin['energy']), grad=str(lin['grad']),
-                                                      params=params, expert_params=q, **(dict(tall=True) if tall else {})))
+                                                      params=params, expert_params=q,
+                                                      **(dict(wide=True) if wide else dict(tall=True) if tall else {})))
             self._bar32 = True
         elif device_expr is not None:
             if isinstance(device_expr, dict):              # coupled through per-particle statistics S[k]
@@ -487,6 +495,10 @@ class GeneralizedLinearModel(Distribution):
     For the two non-Gaussian families the per-expert rows are q[0] = y and q[1] = 1 on the data rows, 0 on the prior rows
     (the expressions select the prior's term by q[1]).  K > 512 runs as a tall model on the fused block kernel
     (mjhmc_energy_create_linear_tall, D <= 512, K <= 2**20), K <= 512 on the tile kernels (mjhmc_energy_create_linear).
+    More than 512 features need ``wide=True``: the model then runs as a wide one on the fused kernel over blocks of experts
+    x chunks of dims (mjhmc_energy_create_linear_wide, D <= 4096, K <= 2**20), whatever its D; the per-expert passes
+    ``pointwise``, ``waic`` and ``influence`` take at most 512 dims and refuse a wide model.  Without it such a model is
+    refused as it always was: a caller who relies on those passes learns at construction that they are not to be had.
     ``E_host`` / ``dEdX_host`` are the same energy in float64 NumPy; ``posterior()`` is exact for the Gaussian family.
     ``gen_init_X`` draws N(0, init_scale^2) (from ``seed`` when given)."""
 
@@ -497,7 +509,7 @@ class GeneralizedLinearModel(Distribution):
     }
 
     def __init__(self, features, targets, family, prior_scale=1.0, noise_scale=1.0, nbatch=100, init_scale=0.1, seed=None,
-                 state_dtype='float64'):
+                 state_dtype='float64', wide=False):
         if state_dtype not in ('float32', 'float64'):
             raise ValueError("GeneralizedLinearModel state_dtype must be 'float32' or 'float64'")
         if family not in ('gaussian', 'logistic', 'poisson'):
@@ -527,7 +539,12 @@ class GeneralizedLinearModel(Distribution):
             self.W = np.vstack([A, prior])
             self.b = np.zeros(n + D)
             self.q = np.vstack([np.concatenate([y, np.zeros(D)]), np.concatenate([np.ones(n), np.zeros(D)])])
-        engine.tall_linear_arrays(self.W, self.b, (), self.q)        # the size limits, before anything else
+        self.wide = bool(wide)
+        if D > 512 and not self.wide:
+            raise ValueError('GeneralizedLinearModel takes at most 512 dims in its tile and tall forms (features are %d x %d); '
+                             'wide=True takes the wide form, up to 4096 dims, without pointwise / waic / influence' % (n, D))
+        # the size limits, before anything else
+        (engine.wide_linear_arrays if self.wide else engine.tall_linear_arrays)(self.W, self.b, (), self.q)
         self.nexperts = n + D
         self.state_dtype = state_dtype
         self.backend = 'hip-mfma'
@@ -541,7 +558,9 @@ class GeneralizedLinearModel(Distribution):
             e = 'q[1] != 0.f ? (%s) : (%s)' % (de, pe)
             g = 'q[1] != 0.f ? (%s) : (%s)' % (dg, pg)
         d = dict(W=self.W, b=self.b, energy=e, grad=g, params=(), expert_params=self.q)
-        if self.nexperts > 512:
+        if self.wide:
+            d['wide'] = True
+        elif self.nexperts > 512:
             d['tall'] = True
         return (_lib.E_LINEAR_EXPR, d)
 

@@ -763,6 +763,17 @@ def refuse_grouped(distribution, what, why):
                          % (what, type(distribution).__name__, params['groups'][0], why))
 
 
+def refuse_wide(distribution, what):
+    """ValueError when the distribution's energy is a wide linear model (device_linear_wide,
+    GeneralizedLinearModel(wide=True)): the passes that take at most 512 dims name it."""
+    kind, params = distribution.device_energy()
+    if kind == _lib.E_LINEAR_EXPR and params.get('wide'):
+        raise ValueError('%s: the energy of %s is a wide linear model (device_linear_wide, '
+                         'GeneralizedLinearModel(wide=True): W is %d x %d) -- this pass takes models of at most 512 dims, '
+                         'stored in one chunk of dims per block of experts'
+                         % ((what, type(distribution).__name__) + tuple(np.shape(params['W']))))
+
+
 _GROUPED_PER_EXPERT = ('the per-expert passes report in the caller\'s order on terms that each see one u_j; a grouped model '
                        'stores its experts in a permuted order and couples the members of a group (its per-row pass is '
                        'group_pointwise() / group_waic())')
@@ -782,6 +793,7 @@ def pointwise_request(distribution, n_iter, values=None, log_mean_exp=None, comp
                          'device_linear, device_linear_tall, GeneralizedLinearModel); the energy of %s is %s'
                          % (type(distribution).__name__, names.get(kind, kind)))
     refuse_grouped(distribution, 'pointwise', _GROUPED_PER_EXPERT)
+    refuse_wide(distribution, 'pointwise')
     if values is None:
         if not hasattr(distribution, 'pointwise_values'):
             raise ValueError('pointwise: %s has no pointwise_values(); pass values=' % type(distribution).__name__)
@@ -919,6 +931,7 @@ def influence_request(distribution, n_iter, value=None, experts=None, sharded=Fa
                          'device_linear, device_linear_tall, GeneralizedLinearModel); the energy of %s is %s'
                          % (type(distribution).__name__, names.get(kind, kind)))
     refuse_grouped(distribution, 'influence', _GROUPED_PER_EXPERT)
+    refuse_wide(distribution, 'influence')
     if value is None:
         if not hasattr(distribution, 'influence_value'):
             raise ValueError('influence: %s has no influence_value(); pass value=' % type(distribution).__name__)
@@ -1480,13 +1493,14 @@ class HMCBase(object):
         promise of the error of ``mean``.
 
         ValueError, before anything runs: n_iter < 1; n_iter * nbatch <= 2 * ndims (the regression is not determined);
-        ndims > 512 or K > 512; an energy given as opaque callables; a grouped linear model (its sampler runs the multi-pass
-        path, which has no single-launch dE/dX; named); a sharded sampler (the sums are additive over ranks,
-        but that is out of scope here: it has not been proved on a multi-rank machine)."""
+        ndims > 512 or K > 512; a wide linear model (named); an energy given as opaque callables; a grouped linear model
+        (its sampler runs the multi-pass path, which has no single-launch dE/dX; named); a sharded sampler (the sums are
+        additive over ranks, but that is out of scope here: it has not been proved on a multi-rank machine)."""
         n_iter = int(n_iter)
         if n_iter < 1:
             raise ValueError('n_iter must be >= 1, got %d' % n_iter)
         K = int(self.ndims) if of is None else int(of.n_values)
+        refuse_wide(self.distribution, 'cv_expectations')
         if int(self.ndims) > 512 or K > 512:
             raise ValueError('cv_expectations takes ndims <= 512 and K <= 512 values, got ndims = %d, K = %d' % (self.ndims, K))
         if n_iter * int(self.nbatch) <= 2 * int(self.ndims):
@@ -1538,9 +1552,9 @@ class HMCBase(object):
         counters, ``dwelling_times`` and final state, bit for bit.  Nothing is added to ``E_count`` / ``dEdX_count``
         (measurement, not sampling).  The results do not depend on ``block``, bit for bit.
 
-        ValueError, before anything runs: n_iter < 1, no value or more than 4, an energy that is not a linear model, an
-        expression that does not compile (with the compiler's message), a sharded sampler (summing over ranks is out of
-        scope here)."""
+        ValueError, before anything runs: n_iter < 1, no value or more than 4, an energy that is not a linear model, a
+        grouped or a wide one (the pass takes at most 512 dims; named), an expression that does not compile (with the
+        compiler's message), a sharded sampler (summing over ranks is out of scope here)."""
         values, flags = pointwise_request(self.distribution, n_iter, values, log_mean_exp)
         n_iter = int(n_iter)
         if self._comm is not None:
@@ -1570,6 +1584,7 @@ class HMCBase(object):
         that of ``pointwise(n_iter)``.  ValueError for a distribution without those two methods."""
         d = self.distribution
         refuse_grouped(d, 'waic', _GROUPED_PER_EXPERT)
+        refuse_wide(d, 'waic')
         if not (hasattr(d, 'pointwise_values') and hasattr(d, 'log_lik_constants')):
             raise ValueError('waic: %s has no pointwise_values() / log_lik_constants() (GeneralizedLinearModel has)'
                              % type(d).__name__)

@@ -35,6 +35,7 @@ GROUP_SIZES = (2, 10, 16)
 INFLUENCE_VALUES = {'u': 'u', 'glm logistic l': LOGISTIC_L}   # those of the table of section 3.3n
 NB_DIMS = {1: 100, 2: 200, 4: 400}   # ndims that pads to 128 NB
 TALL_K = 600                         # more experts than a square model takes: the blocked layout
+WIDE_D = 1000                        # more dims than a tall model takes: the wide form (one kernel whatever the sizes)
 
 
 def load(path=None):
@@ -77,6 +78,8 @@ def instances():
             yield 'mjhmc_influence_check', d, TALL_K, value
     yield 'mjhmc_functionals_check', 100, 'x*x', 'S[0]; sqrt(S[0])'
     yield 'mjhmc_projections_check', 3, 'u > 0.0 ? u : 0.0'
+    for e in EXPRS.values():   # (behind everything else: the running numbers of the files above stay what they were)
+        yield ('mjhmc_linear_wide_check', WIDE_D, TALL_K) + e
 
 
 def main():
